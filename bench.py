@@ -28,6 +28,7 @@ episode step on the host cores through the CPU oracle; N=1 only).  At N=1 the li
   ``mfu_direct_equivalent``  the step's FLOPs counted as the REFERENCE formulation would spend them
                 (SURVEY.md 3.1 MAC counts, forward x 3) over the fp32 peak;
 ``--no-extra`` skips these legs.  At N>1 ``allreduce`` times each gradient bucket's collective.
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (see ``dump_outputs``).
 """
 from __future__ import annotations
 
@@ -544,9 +545,40 @@ def allreduce_probe(step, world):
     return res
 
 
-def run_workload(wl, args, rank, world, device, steps, warmup, probe=None, graph=None, epr=None):
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_PER_TENSOR = 4096
+
+
+def dump_outputs(path, results, model):
+    """``--dump-outputs``: what the last timed step handed back and what it changed, for an output-by-output comparison
+    of two builds (the inputs are seeded: the same arguments give the same episodes and initial weights).
+      ``<loss>.npy``        float64 [episodes, ...]: each entry of the step's per-episode loss dicts (rank 0's episodes)
+      ``state_sample.npy``  float32: a fixed sample of the model's floating-point state after the step (parameters and
+                            BatchNorm running statistics, ``state_dict`` order); from each tensor of n elements
+                            min(n, 4096 + n // 256) of them at sorted indices drawn by a generator seeded with the
+                            tensor's position, so that every tensor is represented"""
+    import numpy as np
+    arrays = {key: np.stack([r[key].detach().double().cpu().numpy() for r in results]) for key in results[0]}
+    picks = []
+    for i, t in enumerate(t for t in model.state_dict().values() if t.is_floating_point()):
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(i))[:min(n, DUMP_PER_TENSOR + n // 256)]
+        picks.append(flat[idx.sort().values.to(flat.device)].float().cpu())
+    arrays["state_sample"] = torch.cat(picks).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for key, a in arrays.items():
+        np.save(os.path.join(path, f"{key}.npy"), a)
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays, {total / 2**20:.1f} MiB in {path}", file=sys.stderr, flush=True)
+
+
+def run_workload(wl, args, rank, world, device, steps, warmup, probe=None, graph=None, epr=None, dump_dir=None):
     """Builds the model of workload ``wl`` and times ``steps`` optimizer steps after ``warmup`` (the contract's
-    timed region: barrier + synchronize on both sides, MAX over ranks).  Returns a dict of results."""
+    timed region: barrier + synchronize on both sides, MAX over ranks).  Returns a dict of results.  ``dump_dir``:
+    rank 0 writes the last timed step's outputs there (``dump_outputs``), after the timed region."""
     S, Q, intra, encoder, epr_default, desc = WORKLOADS[wl]
     epr = epr or epr_default
     if graph is None:
@@ -587,6 +619,8 @@ def run_workload(wl, args, rank, world, device, steps, warmup, probe=None, graph
     barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if dump_dir is not None and rank == 0:   # before the untimed step below changes the weights again
+        dump_outputs(dump_dir, out, model)
     sclk_after = None
     if probe is not None and world == 1:      # the headline run on one GPU: one extra untimed step, clock read under it
         was = probe.enabled
@@ -676,7 +710,12 @@ def main():
     ap.add_argument("--gemm-records", default=None, help="records file for --gemm-tuning tune / file")
     ap.add_argument("--channels-last", action="store_true", help="experiment: NHWC image trunk")
     ap.add_argument("--miopen-benchmark", action="store_true", help="experiment: MIOpen find mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's losses and a fixed sample of the updated model state as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     S, Q, intra, encoder, epr, desc = WORKLOADS[args.workload]
     if args.episodes_per_rank:
@@ -703,7 +742,7 @@ def main():
     probe = EventProbe()
     metrics.set_launch_probe(probe)
     main_run = run_workload(args.workload, args, rank, world, device, steps, warmup, probe=probe, graph=args.graph,
-                            epr=epr)
+                            epr=epr, dump_dir=args.dump_outputs)
     steps, warmup = main_run["steps"], main_run["warmup"]
     elapsed = main_run["elapsed"]
     allreduce = allreduce_probe(main_run["step"], world) if world > 1 or os.environ.get("FPSG_FORCE_DIST") else None

@@ -189,8 +189,56 @@ def gradient_goldens():
     print("gradient_goldens.npz", {k: v.shape for k, v in out.items()})
 
 
+def pointnet_f64_goldens():
+    """The PointNet outputs and training-mode gradients of pointnet_goldens / gradient_goldens (same checkpoint, same
+    inputs ``x_<tag>`` and weights ``pn_w_<tag>``), computed in float64 and stored rounded to float32, one file per
+    input: the host port's reference.  In float32 the training-mode outputs of input "b" move by 1e-4 with the thread
+    count and the CPU, and the gradients of the biases in front of a training-mode BatchNorm are zero, so their
+    float32 goldens are rounding noise of the CPU that made them; rounding a float64 result once is the same on every
+    machine (relative error 6e-8)."""
+    ckpt = os.path.join(REF, "checkpoint/pretrain_pointnet/pretrained_pcencoder_pointnet.pt")
+    sd = torch.load(ckpt, map_location="cpu", weights_only=True)
+    pref = "pc_encoder.pointnet_feat_extractor."
+    inner = {k[len(pref):]: v.double() for k, v in sd.items()}
+    f32 = lambda t: t.detach().numpy().astype(np.float32)
+    for tag, shape in (("a", (4, 3, 256)), ("b", (2, 3, 2048))):
+        g = torch.Generator().manual_seed(100 + len(tag) + shape[2])
+        x = (torch.randn(*shape, generator=g) * 0.5).double()      # = x_<tag>
+        w = torch.randn(shape[0], 1024, generator=g).double()      # = pn_w_<tag>
+        out = {}
+        for mode in ("eval", "train"):
+            m = PointNetfeat().double()
+            m.load_state_dict(inner)
+            m.train(mode == "train")
+            with torch.no_grad():
+                feat, trans, tf = m(x)
+            assert tf is None
+            out[f"feat_{mode}"], out[f"trans_{mode}"] = f32(feat), f32(trans)
+            if mode == "train":
+                out["bn3_mean_train"] = f32(m.bn3.running_mean)
+                out["stn_bn5_var_train"] = f32(m.stn.bn5.running_var)
+            else:
+                s = STN3d().double()
+                s.load_state_dict({k[4:]: v for k, v in inner.items() if k.startswith("stn.")})
+                s.eval()
+                with torch.no_grad():
+                    out["stn_eval"] = f32(s(x))
+        xg = x.clone().requires_grad_()
+        m = PointNetfeat().double()
+        m.load_state_dict(inner)
+        m.train()
+        feat, _, _ = m(xg)
+        (feat * w).sum().backward()
+        out["gx"] = f32(xg.grad)
+        for name, p in m.named_parameters():
+            out[f"g_{name}"] = f32(_rows(p.grad))
+        np.savez_compressed(os.path.join(OUT, f"pointnet_f64_{tag}.npz"), **out)
+        print(f"pointnet_f64_{tag}.npz", {k: v.shape for k, v in out.items()})
+
+
 if __name__ == "__main__":
     pointnet_goldens()
     dgcnn_goldens()
     episode_goldens()
     gradient_goldens()
+    pointnet_f64_goldens()

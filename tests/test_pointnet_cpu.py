@@ -1,4 +1,9 @@
-"""Host-side PointNet vs goldens produced by the reference's own module + checkpoint."""
+"""Host-side PointNet vs goldens produced by the reference's own module + checkpoint.
+
+The host port runs in float64 against the reference's float64 results (``pointnet_f64_<tag>.npz``, stored rounded to
+float32): in float32 the training-mode outputs of input "b" move by 1e-4 with the thread count and the CPU, and the
+gradients of the biases in front of a training-mode BatchNorm are zero, so float32 goldens of them hold only on the CPU
+that wrote them.  The float32 goldens stay the GPU tests' yardstick."""
 import os
 
 import numpy as np
@@ -15,12 +20,16 @@ def gold():
     return np.load(os.path.join(GOLDEN, "pointnet_goldens.npz"))
 
 
-def _encoder():
+def _f64(tag):
+    return np.load(os.path.join(GOLDEN, f"pointnet_f64_{tag}.npz"))
+
+
+def _encoder(dtype=torch.float32):
     from fpsg_amd.point_cloud_net import PCEncoder
     enc = PCEncoder("pointnet")
     missing = enc.load_state_dict(torch.load(CKPT, map_location="cpu", weights_only=True), strict=True)
     assert not missing.missing_keys and not missing.unexpected_keys
-    return enc
+    return enc.to(dtype)
 
 
 def test_checkpoint_loads_key_for_key():
@@ -32,44 +41,46 @@ def test_checkpoint_loads_key_for_key():
 @pytest.mark.parametrize("tag", ["a", "b"])
 @pytest.mark.parametrize("mode", ["eval", "train"])
 def test_features_match_reference(gold, tag, mode):
-    enc = _encoder()
+    ref = _f64(tag)
+    enc = _encoder(torch.float64)
     enc.train(mode == "train")
-    x = torch.from_numpy(gold[f"x_{tag}"])
+    x = torch.from_numpy(gold[f"x_{tag}"]).double()
     net = enc.pc_encoder.pointnet_feat_extractor
     with torch.no_grad():
         feat, trans, tf = net(x)
         stn = net.stn(x) if mode == "eval" else None
     assert tf is None
-    np.testing.assert_allclose(trans.numpy(), gold[f"trans_{tag}_{mode}"], rtol=1e-4, atol=1e-5)
-    np.testing.assert_allclose(feat.numpy(), gold[f"feat_{tag}_{mode}"], rtol=1e-4, atol=1e-4)
+    np.testing.assert_allclose(trans.numpy(), ref[f"trans_{mode}"], rtol=1e-4, atol=1e-5)
+    np.testing.assert_allclose(feat.numpy(), ref[f"feat_{mode}"], rtol=1e-4, atol=1e-4)
     if stn is not None:
-        np.testing.assert_allclose(stn.numpy(), gold[f"stn_{tag}_eval"], rtol=1e-4, atol=1e-5)
+        np.testing.assert_allclose(stn.numpy(), ref["stn_eval"], rtol=1e-4, atol=1e-5)
     if mode == "train":
-        np.testing.assert_allclose(net.bn3.running_mean.numpy(), gold[f"bn3_mean_{tag}_train"],
+        np.testing.assert_allclose(net.bn3.running_mean.numpy(), ref["bn3_mean_train"],
                                    rtol=1e-4, atol=1e-5)
-        np.testing.assert_allclose(net.stn.bn5.running_var.numpy(), gold[f"stn_bn5_var_{tag}_train"],
+        np.testing.assert_allclose(net.stn.bn5.running_var.numpy(), ref["stn_bn5_var_train"],
                                    rtol=1e-4, atol=1e-6)
 
 
 def test_encoder_wrapper_returns_feature_only(gold):
-    enc = _encoder().eval()
+    enc = _encoder(torch.float64).eval()
     with torch.no_grad():
-        out = enc(torch.from_numpy(gold["x_a"]))
+        out = enc(torch.from_numpy(gold["x_a"]).double())
     assert out.shape == (4, 1024)
-    np.testing.assert_allclose(out.numpy(), gold["feat_a_eval"], rtol=1e-4, atol=1e-4)
+    np.testing.assert_allclose(out.numpy(), _f64("a")["feat_eval"], rtol=1e-4, atol=1e-4)
 
 
 @pytest.mark.parametrize("tag", ["a", "b"])
 def test_training_gradients_match_reference(gold, tag):
-    """Host port against the reference module's own autograd (gradient_goldens.npz)."""
+    """Host port against the reference module's own autograd (gradient_goldens.npz's weights, float64 results)."""
     gg = np.load(os.path.join(GOLDEN, "gradient_goldens.npz"))
-    enc = _encoder().train()
+    gold64 = _f64(tag)
+    enc = _encoder(torch.float64).train()
     net = enc.pc_encoder.pointnet_feat_extractor
-    x = torch.from_numpy(gold[f"x_{tag}"]).requires_grad_()
+    x = torch.from_numpy(gold[f"x_{tag}"]).double().requires_grad_()
     feat, _, _ = net(x)
-    (feat * torch.from_numpy(gg[f"pn_w_{tag}"])).sum().backward()
-    np.testing.assert_allclose(x.grad.numpy(), gg[f"pn_gx_{tag}"], rtol=1e-3, atol=1e-5 * np.abs(gg[f"pn_gx_{tag}"]).max())
+    (feat * torch.from_numpy(gg[f"pn_w_{tag}"]).double()).sum().backward()
+    np.testing.assert_allclose(x.grad.numpy(), gold64["gx"], rtol=1e-3, atol=1e-5 * np.abs(gold64["gx"]).max())
     for name, p in net.named_parameters():
-        ref = gg[f"pn_g_{tag}_{name}"]
+        ref = gold64[f"g_{name}"]
         got = (p.grad[:64] if p.grad.numel() > 65536 else p.grad).numpy()
         assert np.abs(got - ref).max() <= 1e-3 * np.abs(ref).max() + 1e-6, name

@@ -1,5 +1,6 @@
-import torch, sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+import torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fpsg_amd import metrics as m
 dev = torch.device('cuda:0')
 def ev(fn, reps, warm=20):
