@@ -4,7 +4,8 @@
 Same command line and report lines as reference ``src/evaluate_Network.py`` (``main :65-123``):
 loads ``<model_path>/<name>/<eval_model>``, runs ``ImgPCProtoNet._return_reconstruction`` on
 every test episode (HIP Chamfer K1 + the HIP Sinkhorn divergence K2b, the form ``emd_wrapper`` calls) and prints
-``Class: <c> -- Rec CD: <mean>; Rec EMD: <mean>``.  With ``--npy_folder`` the generated and
+``Class: <c> -- Rec CD: <mean>; Rec EMD: <mean>`` (``--exact_emd``: followed by ``; Exact EMD: <mean>``, the
+exact transport distance of K12 divided by n_query like the other two).  With ``--npy_folder`` the generated and
 ground-truth clouds (+ a side-by-side PNG) of every item are dumped instead, which is the
 reference's commented-out "OPTION 2" (``:111``).
 
@@ -44,9 +45,11 @@ def main(opt):
     model = model.to(device).eval()
 
     per_class_cd, per_class_emd = defaultdict(list), defaultdict(list)
+    exact = bool(getattr(opt, "exact_emd", False))
+    per_class_exact = defaultdict(list)
     # the weights do not change while evaluating: transformed filters, stacked decoder weights and BatchNorm coefficients
     # are made once, not per item; on a GPU the item in front of the EMD is replayed as a hipGraph (engine.EvalItem)
-    with EvalItem(model) as run_item:
+    with EvalItem(model, exact_emd=exact) as run_item:
         for item, sample in enumerate(dl_test):
             sample = to_device(sample, device)
             if getattr(opt, "npy_folder", ""):
@@ -57,9 +60,16 @@ def main(opt):
             name = sample["class"][0]
             per_class_cd[name].append(out["cd_loss"].item() / n_query)
             per_class_emd[name].append(out["emd_loss"].item() / n_query)
+            if exact:
+                per_class_exact[name].append(out["exact_emd"].item() / n_query)
     for name in sorted(per_class_cd):
-        print(f"Class: {name} -- Rec CD: {statistics.mean(per_class_cd[name])}; "
-              f"Rec EMD: {statistics.mean(per_class_emd[name])}")
+        line = (f"Class: {name} -- Rec CD: {statistics.mean(per_class_cd[name])}; "
+                f"Rec EMD: {statistics.mean(per_class_emd[name])}")
+        if exact:
+            line += f"; Exact EMD: {statistics.mean(per_class_exact[name])}"
+        print(line)
+    if exact:
+        return per_class_cd, per_class_emd, per_class_exact
     return per_class_cd, per_class_emd
 
 

@@ -10,7 +10,8 @@ working).  ``--sequential_eval`` is declared with ``store_true``: the reference'
 Additions (all optional): ``--synthetic`` (file-free corpora of the reference's shapes),
 ``--episodes_per_step`` (episodes per optimizer step across all ranks; data-parallel under
 ``torchrun``), ``--img_encoder_path`` (local VGG16-BN weights; nothing is downloaded),
-``--resident`` (keep the corpora in HBM, assemble episodes on the device).
+``--resident`` (keep the corpora in HBM, assemble episodes on the device), ``--exact_emd`` (evaluation: the exact
+EMD per class beside the two reference metrics).
 """
 from __future__ import annotations
 
@@ -79,6 +80,8 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--sequential_eval", action="store_true")
     if evaluation:
         g.add_argument("--npy_folder", type=str, default="", help="Where draw_reconstruction dumps go;")
+        g.add_argument("--exact_emd", action="store_true",
+                       help="Also report the exact EMD per class (HIP auction, fpsg_amd.metrics.emd_exact);")
     return p
 
 

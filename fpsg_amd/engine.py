@@ -223,12 +223,17 @@ class EvalItem:
     annealing schedule depends on that diameter (geomloss' rule), so the loop reads it (its one mid-item host read, as
     before) and launches K2b's ~12 kernels eagerly.  The first two items of a shape run eagerly (the libraries pick
     their kernels, the filter bank registers the layers); capture happens on the third.  A model whose ``emd_metric`` /
-    ``pc_metric`` were replaced (tests drive the module with the oracle's functions) takes the plain method."""
+    ``pc_metric`` were replaced (tests drive the module with the oracle's functions) takes the plain method.
+
+    ``exact_emd=True`` (``evaluate_Network.py --exact_emd``): every item also returns ``"exact_emd"``, the summed exact EMD
+    of its query clouds (``metrics.emd_exact``, K12), computed eagerly after the item -- after the replay on the same
+    ``syn_pc`` / ``ref_pc_q`` the graph produced, never inside a capture."""
 
     _KEYS = ("xs", "xq", "xad", "pcs", "pcq", "pcad")
 
-    def __init__(self, model, graph: bool | None = None):
+    def __init__(self, model, graph: bool | None = None, exact_emd: bool = False):
         self.model = model
+        self.exact_emd = bool(exact_emd)
         on_gpu = next(model.parameters()).is_cuda
         if graph is None:
             graph = os.environ.get("FPSG_EVAL_GRAPH", "1") != "0"
@@ -261,18 +266,27 @@ class EvalItem:
         return self.model.emd_metric is emd_wrapper and self.model.pc_metric is chamfer_distance
 
     def __call__(self, sample):
+        if not self.exact_emd:
+            return self._item(sample)
+        from .metrics import emd_exact
+        out = self._item(sample, clouds=True)
+        syn_pc, ref_pc_q = out.pop("syn_pc"), out.pop("ref_pc_q")
+        out["exact_emd"] = emd_exact(syn_pc.contiguous(), ref_pc_q.contiguous()).sum()
+        return out
+
+    def _item(self, sample, clouds: bool = False):
         from .metrics import sinkhorn_divergence
         model = self.model
         if self._block is None:
             raise RuntimeError("EvalItem: call it inside its `with` block")
         if not self.use_graph or not self._default_metrics() or model.training:
-            return model._return_reconstruction(sample)
+            return model._return_reconstruction(sample, return_clouds=clouds)
         key = tuple((k, tuple(sample[k].shape)) for k in self._KEYS)
         if key not in self._graphs:
             n = self._eager.get(key, 0)
             if n < 2:
                 self._eager[key] = n + 1
-                return model._return_reconstruction(sample)
+                return model._return_reconstruction(sample, return_clouds=clouds)
             # (pruned evaluation reads only the query images and the support / query clouds: the other three inputs --
             # 2 x 19 MB of images at 32 shots -- are neither cloned nor copied per item)
             used = ("xq", "pcs", "pcq") if model._eval_prune() else self._KEYS
@@ -287,4 +301,6 @@ class EvalItem:
         winograd.check_bank_before_replay()
         g.replay()
         emd = sinkhorn_divergence(syn_pc, ref_pc_q, diameter=float(diameter)).sum()      # emd_wrapper's value
+        if clouds:
+            return {"cd_loss": cd_loss.clone(), "emd_loss": emd, "syn_pc": syn_pc, "ref_pc_q": ref_pc_q}
         return {"cd_loss": cd_loss.clone(), "emd_loss": emd}

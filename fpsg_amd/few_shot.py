@@ -216,7 +216,9 @@ class ImgPCProtoNet(nn.Module):
         diameter = (pts.amax(0) - pts.amin(0)).norm()
         return syn_pc, ref_pc_q, self.query_factor * loss_rec_q, diameter
 
-    def _return_reconstruction(self, sample):
+    def _return_reconstruction(self, sample, return_clouds: bool = False):
+        """``{"cd_loss", "emd_loss"}`` of one test item; ``return_clouds=True`` also returns the generated and reference
+        query clouds (``"syn_pc"``, ``"ref_pc_q"``) the two were computed on."""
         if self._eval_prune():
             img_zq, pc_z_proto = self._encode_for_eval(sample["xq"], sample["pcs"])
         else:
@@ -225,6 +227,9 @@ class ImgPCProtoNet(nn.Module):
         ref_pc_q = sample["pcq"].squeeze(0).contiguous()
         loss_rec_q = self.pc_metric(syn_pc, ref_pc_q).sum()
         emd_loss = self.emd_metric(syn_pc, ref_pc_q).sum()
+        if return_clouds:
+            return {"cd_loss": self.query_factor * loss_rec_q, "emd_loss": emd_loss, "syn_pc": syn_pc,
+                    "ref_pc_q": ref_pc_q}
         return {"cd_loss": self.query_factor * loss_rec_q, "emd_loss": emd_loss}
 
     @torch.no_grad()

@@ -251,6 +251,103 @@ def emd_approx(p1: torch.Tensor, p2: torch.Tensor) -> torch.Tensor:
     return _EmdApprox.apply(p1, p2)
 
 
+EMD_EXACT_MAX_N = 2048          # FPSG_EMD_EXACT_MAX_N (include/fpsg_hip.h)
+EMD_EXACT_MAX_ROUNDS = 1 << 18  # default round cap of emd_exact per pair
+
+
+class EmdExactCapWarning(RuntimeWarning):
+    """``emd_exact`` stopped a pair at its round cap: its cost is that of a complete but not certified-optimal
+    assignment (still an upper bound; ``cost - gap`` is still a lower bound)."""
+
+
+def emd_exact_default_eps(p1: torch.Tensor, p2: torch.Tensor) -> float:
+    """Default final auction step of ``emd_exact``: ``2e-5 * D / N^(1/3)``, D the bounding-box diagonal of both clouds.
+
+    The exact cost is N times the mean matched distance, which for N points spread over a set of extent D is of order
+    ``D / N^(1/3)`` (about ``0.03 D`` for 2048-point unit-ball pairs); the auction's error is at most ``N * eps``, so this
+    ``eps`` keeps it near 1e-4 of a typical cost or below (measured on unit-ball pairs: DESIGN.md K12), while leaving the
+    step several fp32 ulps of the prices (at most ~D).  One host read (the diagonal)."""
+    pts = torch.cat([p1.detach().reshape(-1, 3), p2.detach().reshape(-1, 3)])
+    diag = float((pts.amax(0) - pts.amin(0)).norm())
+    n = p1.size(1)
+    return max(2e-5 * diag / n ** (1.0 / 3.0), 1e-30)
+
+
+def _emd_exact_forward(p1, p2, eps, max_rounds, need1, need2):
+    if p1.dim() == 3 and p2.dim() == 3:
+        if p1.size(1) != p2.size(1):
+            raise ValueError(f"emd_exact needs clouds of equal size, got N={p1.size(1)} and M={p2.size(1)}")
+        if p1.size(1) > EMD_EXACT_MAX_N:
+            raise ValueError(f"emd_exact supports at most {EMD_EXACT_MAX_N} points per cloud, got {p1.size(1)}")
+    _check_clouds(p1, p2)
+    B, N, _ = p1.shape
+    if eps is None:
+        eps = emd_exact_default_eps(p1, p2)
+    if max_rounds is None:
+        max_rounds = EMD_EXACT_MAX_ROUNDS
+    lib = _hip.load()
+    dev = p1.device
+    cost = torch.empty((B,), dtype=torch.float32, device=dev)
+    gap = torch.empty((B,), dtype=torch.float32, device=dev)
+    assign = torch.empty((B, N), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    g1 = torch.empty_like(p1) if need1 else None
+    g2 = torch.empty_like(p2) if need2 else None
+    ws = torch.empty((lib.fpsg_emd_exact_workspace_floats(B, N),), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _probe("emd_exact", B, N, N):
+        rc = lib.fpsg_emd_exact(_hip.ptr(p1), _hip.ptr(p2), B, N, float(eps), int(max_rounds), _hip.ptr(cost),
+                                _hip.ptr(gap), _hip.ptr(assign), _hip.ptr(status), _hip.ptr(g1) if need1 else None,
+                                _hip.ptr(g2) if need2 else None, _hip.ptr(ws), _hip.stream_of(p1))
+    _hip.check(rc, "fpsg_emd_exact")
+    stats = ws.view(torch.int32).reshape(B, 4)
+    info = {"assign": assign, "gap": gap, "status": status, "rounds": stats[:, 0], "eps": float(eps)}
+    return cost, g1, g2, info
+
+
+class _EmdExact(torch.autograd.Function):
+    """cost [B] of the exact assignment (K12); the gradients (assignment held constant) come from the same launch."""
+
+    @staticmethod
+    def forward(ctx, p1, p2, eps, max_rounds, info_out):
+        cost, g1, g2, info = _emd_exact_forward(p1, p2, eps, max_rounds, ctx.needs_input_grad[0],
+                                                ctx.needs_input_grad[1])
+        info_out.update(info)
+        ctx.grads = (g1, g2)
+        return cost
+
+    @staticmethod
+    def backward(ctx, gcost):
+        g1, g2 = ctx.grads
+        gc = gcost.reshape(-1, 1, 1)
+        return (None if g1 is None else g1 * gc), (None if g2 is None else g2 * gc), None, None, None
+
+
+def emd_exact(p1: torch.Tensor, p2: torch.Tensor, eps: float | None = None, max_rounds: int | None = None,
+              return_info: bool = False):
+    """Exact Earth Mover's Distance ``[B]`` between equal-size clouds ``p1, p2 [B,N,3]`` (N <= 2048): the minimum over
+    permutations of the sum of Euclidean distances of matched points (not divided by N) -- what K2 (``emd_approx``)
+    and K2b (``sinkhorn_divergence``) approximate.  A bounded auction (K12, HIP) finds it to within ``N * eps``.
+
+    ``eps``: the final auction step (default ``emd_exact_default_eps``: the error bound ``N * eps`` is ~1e-4 of a
+    typical cost); ``max_rounds``: round cap per pair (default ``EMD_EXACT_MAX_ROUNDS``).  Differentiable in both clouds
+    with the assignment held constant (K2's convention).  ``return_info=True``: returns ``(cost, info)`` with
+    ``info["assign"] [B,N]`` int32 (a permutation), ``info["gap"] [B]`` (certificate: ``cost - gap <= exact EMD <=
+    cost``), ``info["status"] [B]`` int32 (0 converged, 1 round cap hit) and ``info["rounds"] [B]``.
+
+    A pair that hits the round cap is not an error: its cost is that of a complete assignment and its gap still
+    brackets the exact value, so ``emd_exact`` issues an ``EmdExactCapWarning`` naming the pairs (one host read of
+    ``status``) and returns.  Raises ``ValueError`` for clouds of different sizes or beyond 2048 points."""
+    info = {}
+    cost = _EmdExact.apply(p1, p2, eps, max_rounds, info)
+    capped = torch.nonzero(info["status"]).flatten().tolist()
+    if capped:
+        import warnings
+        warnings.warn(f"emd_exact: pairs {capped} hit the round cap (max_rounds="
+                      f"{EMD_EXACT_MAX_ROUNDS if max_rounds is None else max_rounds}); their cost is an upper bound "
+                      f"within gap {info['gap'][capped].tolist()} of the exact EMD", EmdExactCapWarning, stacklevel=2)
+    return (cost, info) if return_info else cost
+
+
 def softmin(x: torch.Tensor, y: torch.Tensor, h: torch.Tensor, eps: float) -> torch.Tensor:
     """``out[b,i] = -eps * logsumexp_j(h[b,j] - |x_i - y_j|^2 / (2 eps))`` (K2b), no grad."""
     _check_clouds(x, y)

@@ -202,6 +202,36 @@ int fpsg_emd_approx(const float* xyz1, const float* xyz2, int B, int N, int M, f
 int fpsg_emd_approx_variant(const float* xyz1, const float* xyz2, int B, int N, int M, float* cost,
                             float* gxyz1, float* gxyz2, float* ws, int variant, fpsg_stream_t stream);
 
+/* ---- K12: exact EMD, forward auction with eps-scaling -------------------------------
+ * The exact transport distance that K2 (approximate assignment) and K2b (Sinkhorn divergence) stand in
+ * for: between equal-size clouds xyz1, xyz2 [B,N,3] fp32,  cost[b] = min over permutations a of
+ * sum_i |xyz1_i - xyz2_a(i)|  (Euclidean, not squared, not divided by N), to within N * eps_final.
+ * Evaluation metric only; the reference has no exact form (its emd_loss packages are absent).
+ * One workgroup per pair; a Bertsekas forward auction (bidders = xyz1, objects = xyz2, prices start at 0)
+ * over phases eps_0 = bbox diagonal / 4, eps_0 / 4, ... down to eps_final.  Outputs:
+ *   cost [B]   sum_i |xyz1_i - xyz2_assign(i)| (fixed summation order);
+ *   gap [B]    certificate cost - D, D = sum_i min_j (c_ij + p_j) - sum_j p_j the LP dual value of the final
+ *              prices, so cost - gap <= exact EMD <= cost; 0 <= gap <= N * eps_final (up to fp32 rounding)
+ *              when status = 0;
+ *   assign [B,N] int32, a permutation of 0..N-1 (also when capped);
+ *   status [B] int32: 0 = converged, 1 = the round cap max_rounds was hit (the assignment was completed
+ *              with the free objects in index order; cost and gap still hold for it);
+ *   gxyz1, gxyz2 [B,N,3] (each may be NULL): d cost / d xyz with the assignment held constant (K2's
+ *              convention): (xyz1_i - xyz2_a(i)) / |xyz1_i - xyz2_a(i)|, 0 where that distance is 0, and its
+ *              negative at a(i) for gxyz2;
+ *   ws         fpsg_emd_exact_workspace_floats(B,N) device floats: per pair the int32 statistics (rounds in
+ *              all, rounds of the last phase, phases, bits of eps_0).
+ * Bounded work: at most max_rounds auction rounds per pair, no spin-wait, no communication between
+ * workgroups.  Deterministic (bit-identical across runs).  1 <= N <= FPSG_EMD_EXACT_MAX_N; eps_final > 0
+ * and finite; max_rounds >= 1; otherwise FPSG_E_SHAPE before any launch (FPSG_E_NULL for a null required
+ * pointer).
+ */
+#define FPSG_EMD_EXACT_MAX_N 2048
+size_t fpsg_emd_exact_workspace_floats(int B, int N);
+int fpsg_emd_exact(const float* xyz1, const float* xyz2, int B, int N, float eps_final, int max_rounds,
+                   float* cost, float* gap, int* assign, int* status,
+                   float* gxyz1, float* gxyz2, float* ws, fpsg_stream_t stream);
+
 /* ---- K4b: fused EdgeConv (gather + BatchNorm statistics + max over k) -----------------
  * Replaces the chain get_graph_feature -> Conv2d 1x1 -> BatchNorm2d -> LeakyReLU -> max_k of
  * src/dgcnn/model.py:23-42,53-56,63-76 without materialising [B,2C,N,k].  The caller first
