@@ -5,7 +5,9 @@ Same command line and report lines as reference ``src/evaluate_Network.py`` (``m
 loads ``<model_path>/<name>/<eval_model>``, runs ``ImgPCProtoNet._return_reconstruction`` on
 every test episode (HIP Chamfer K1 + the HIP Sinkhorn divergence K2b, the form ``emd_wrapper`` calls) and prints
 ``Class: <c> -- Rec CD: <mean>; Rec EMD: <mean>`` (``--exact_emd``: followed by ``; Exact EMD: <mean>``, the
-exact transport distance of K12 divided by n_query like the other two).  With ``--npy_folder`` the generated and
+exact transport distance of K12 divided by n_query like the other two; ``--set_metrics``: then
+``; MMD-CD: <v>; COV-CD: <v>; 1-NNA-CD: <v>``, the set-level generation metrics of ``fpsg_amd.set_metrics`` over all
+the class's generated and reference query clouds, from K13's Chamfer matrices).  With ``--npy_folder`` the generated and
 ground-truth clouds (+ a side-by-side PNG) of every item are dumped instead, which is the
 reference's commented-out "OPTION 2" (``:111``).
 
@@ -47,9 +49,11 @@ def main(opt):
     per_class_cd, per_class_emd = defaultdict(list), defaultdict(list)
     exact = bool(getattr(opt, "exact_emd", False))
     per_class_exact = defaultdict(list)
+    sets = bool(getattr(opt, "set_metrics", False))
+    per_class_gen, per_class_ref = defaultdict(list), defaultdict(list)
     # the weights do not change while evaluating: transformed filters, stacked decoder weights and BatchNorm coefficients
     # are made once, not per item; on a GPU the item in front of the EMD is replayed as a hipGraph (engine.EvalItem)
-    with EvalItem(model, exact_emd=exact) as run_item:
+    with EvalItem(model, exact_emd=exact, return_clouds=sets) as run_item:
         for item, sample in enumerate(dl_test):
             sample = to_device(sample, device)
             if getattr(opt, "npy_folder", ""):
@@ -62,15 +66,24 @@ def main(opt):
             per_class_emd[name].append(out["emd_loss"].item() / n_query)
             if exact:
                 per_class_exact[name].append(out["exact_emd"].item() / n_query)
+            if sets:                                    # kept on the device; one set per class after the loop
+                per_class_gen[name].append(out["syn_pc"])
+                per_class_ref[name].append(out["ref_pc_q"])
+    per_class_set = {}
+    if sets:
+        from fpsg_amd.set_metrics import generation_metrics
+        for name in sorted(per_class_gen):
+            per_class_set[name] = generation_metrics(torch.cat(per_class_gen[name]), torch.cat(per_class_ref[name]))
     for name in sorted(per_class_cd):
         line = (f"Class: {name} -- Rec CD: {statistics.mean(per_class_cd[name])}; "
                 f"Rec EMD: {statistics.mean(per_class_emd[name])}")
         if exact:
             line += f"; Exact EMD: {statistics.mean(per_class_exact[name])}"
+        if sets:
+            m = per_class_set[name]
+            line += f"; MMD-CD: {m['mmd_cd']}; COV-CD: {m['cov_cd']}; 1-NNA-CD: {m['nna_cd']}"
         print(line)
-    if exact:
-        return per_class_cd, per_class_emd, per_class_exact
-    return per_class_cd, per_class_emd
+    return (per_class_cd, per_class_emd) + ((per_class_exact,) if exact else ()) + ((per_class_set,) if sets else ())
 
 
 if __name__ == "__main__":

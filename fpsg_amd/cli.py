@@ -11,7 +11,8 @@ Additions (all optional): ``--synthetic`` (file-free corpora of the reference's 
 ``--episodes_per_step`` (episodes per optimizer step across all ranks; data-parallel under
 ``torchrun``), ``--img_encoder_path`` (local VGG16-BN weights; nothing is downloaded),
 ``--resident`` (keep the corpora in HBM, assemble episodes on the device), ``--exact_emd`` (evaluation: the exact
-EMD per class beside the two reference metrics).
+EMD per class beside the two reference metrics), ``--set_metrics`` (evaluation: MMD, COV and 1-NNA under the Chamfer
+distance per class, over the class's generated and reference query clouds).
 """
 from __future__ import annotations
 
@@ -82,6 +83,9 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
         g.add_argument("--npy_folder", type=str, default="", help="Where draw_reconstruction dumps go;")
         g.add_argument("--exact_emd", action="store_true",
                        help="Also report the exact EMD per class (HIP auction, fpsg_amd.metrics.emd_exact);")
+        g.add_argument("--set_metrics", action="store_true",
+                       help="Also report MMD-CD, COV-CD and 1-NNA-CD per class over all its generated and reference "
+                            "query clouds (HIP Chamfer matrix, fpsg_amd.set_metrics);")
     return p
 
 

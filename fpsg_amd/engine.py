@@ -227,13 +227,18 @@ class EvalItem:
 
     ``exact_emd=True`` (``evaluate_Network.py --exact_emd``): every item also returns ``"exact_emd"``, the summed exact EMD
     of its query clouds (``metrics.emd_exact``, K12), computed eagerly after the item -- after the replay on the same
-    ``syn_pc`` / ``ref_pc_q`` the graph produced, never inside a capture."""
+    ``syn_pc`` / ``ref_pc_q`` the graph produced, never inside a capture.
+
+    ``return_clouds=True`` (``evaluate_Network.py --set_metrics``): every item also returns ``"syn_pc"`` and
+    ``"ref_pc_q"``, the generated and reference query clouds, as clones: on the replay path they are the graph's static
+    output buffers, which the next replay overwrites."""
 
     _KEYS = ("xs", "xq", "xad", "pcs", "pcq", "pcad")
 
-    def __init__(self, model, graph: bool | None = None, exact_emd: bool = False):
+    def __init__(self, model, graph: bool | None = None, exact_emd: bool = False, return_clouds: bool = False):
         self.model = model
         self.exact_emd = bool(exact_emd)
+        self.return_clouds = bool(return_clouds)
         on_gpu = next(model.parameters()).is_cuda
         if graph is None:
             graph = os.environ.get("FPSG_EVAL_GRAPH", "1") != "0"
@@ -266,12 +271,15 @@ class EvalItem:
         return self.model.emd_metric is emd_wrapper and self.model.pc_metric is chamfer_distance
 
     def __call__(self, sample):
-        if not self.exact_emd:
+        if not self.exact_emd and not self.return_clouds:
             return self._item(sample)
-        from .metrics import emd_exact
         out = self._item(sample, clouds=True)
         syn_pc, ref_pc_q = out.pop("syn_pc"), out.pop("ref_pc_q")
-        out["exact_emd"] = emd_exact(syn_pc.contiguous(), ref_pc_q.contiguous()).sum()
+        if self.exact_emd:
+            from .metrics import emd_exact
+            out["exact_emd"] = emd_exact(syn_pc.contiguous(), ref_pc_q.contiguous()).sum()
+        if self.return_clouds:
+            out["syn_pc"], out["ref_pc_q"] = syn_pc.clone(), ref_pc_q.clone()
         return out
 
     def _item(self, sample, clouds: bool = False):

@@ -213,6 +213,41 @@ def chamfer_distance(p1: torch.Tensor, p2: torch.Tensor, w1: float = 1.0, w2: fl
     return w1 * dist_to_p2 + w2 * dist_to_p1
 
 
+
+CHAMFER_CROSS_MAX_N = 4096      # FPSG_CHAMFER_CROSS_MAX_N (include/fpsg_hip.h)
+
+
+def chamfer_matrix(A: torch.Tensor, B: torch.Tensor | None = None) -> torch.Tensor:
+    """All-pairs Chamfer matrix ``[Na,Nb]`` (K13, HIP): ``out[a][b] = chamfer_distance(A[a:a+1], B[b:b+1])`` for clouds
+    ``A [Na,N,3]`` and ``B [Nb,M,3]`` (N, M <= 4096), with the same per-point minima as K1 bit for bit and only the
+    order of the two means' summation different (``include/fpsg_hip.h``, K13).  ``B=None``: ``A`` against itself, each
+    unordered pair evaluated once, an exact-zero diagonal, bitwise symmetric and equal to ``chamfer_matrix(A, A)``.
+
+    Deterministic: every entry is bitwise the same whatever set, slice or call it is computed in, and
+    ``chamfer_matrix(B, A) == chamfer_matrix(A, B).T`` bitwise.  Forward only: the result never requires grad (it is
+    an evaluation metric; there is no backward).  No CPU path: CPU tensors raise ``FpsgHipError``."""
+    sym = B is None
+    other = A if sym else B
+    if A.dim() != 3 or other.dim() != 3 or A.size(2) != 3 or other.size(2) != 3:
+        raise ValueError(f"expected [Na,N,3] and [Nb,M,3] clouds, got {tuple(A.shape)} and {tuple(other.shape)}")
+    if A.device != other.device:
+        raise ValueError(f"device mismatch: {A.device} vs {other.device}")
+    if A.numel() == 0 or other.numel() == 0:
+        raise ValueError(f"empty sets or clouds are not supported (got {tuple(A.shape)} and {tuple(other.shape)})")
+    A = A.detach()
+    other = other.detach()
+    _hip.dev_tensor(A, torch.float32, "A")
+    _hip.dev_tensor(other, torch.float32, "B")
+    Na, N, _ = A.shape
+    Nb, M, _ = other.shape
+    lib = _hip.load()
+    out = torch.empty((Na, Nb), dtype=torch.float32, device=A.device)
+    with torch.cuda.device(A.device), _probe("chamfer_cross", Na * Nb, N, M):
+        rc = lib.fpsg_chamfer_cross(_hip.ptr(A), None if sym else _hip.ptr(other), Na, Nb, N, M, _hip.ptr(out),
+                                    _hip.stream_of(A))
+    _hip.check(rc, "fpsg_chamfer_cross")
+    return out
+
 class _EmdApprox(torch.autograd.Function):
     """cost [B] of the approximate-assignment solver; the gradients (assignment held
     constant) are produced by the same solver run and cached for backward."""

@@ -232,6 +232,28 @@ int fpsg_emd_exact(const float* xyz1, const float* xyz2, int B, int N, float eps
                    float* cost, float* gap, int* assign, int* status,
                    float* gxyz1, float* gxyz2, float* ws, fpsg_stream_t stream);
 
+/* ---- K13: all-pairs Chamfer matrix -----------------------------------------------------
+ * Between every cloud of xyz1 [Na,N,3] and every cloud of xyz2 [Nb,M,3] (fp32, contiguous, device):
+ *   out[a][b] = mean_i min_j d(xyz1[a,i], xyz2[b,j]) + mean_j min_i d(xyz2[b,j], xyz1[a,i]),
+ *   d(p,q) = fma(dz,dz, fma(dy,dy, dx*dx)), dx = q.x - p.x, ...
+ * i.e. chamfer_distance (K1, Kaolin 0.9.0's convention) of the pair.  Evaluation metric only (the set-level
+ * generation metrics MMD / COV / 1-NNA); forward only, no indices, no per-point outputs, no workspace.
+ * Output: out [Na,Nb] fp32.  xyz2 == NULL selects the symmetric mode, xyz1 against itself (Nb = Na and
+ * M = N required): each unordered pair is evaluated once and mirrored; the diagonal is exactly 0.
+ * Arithmetic: every per-point minimum is bit-identical to K1's dist1 / dist2.  Each of the two means is
+ * S / n, S the sum of the n per-point minima of one cloud in a fixed order that depends on n alone:
+ * 256 partial sums, partial t = the minima of points t*K .. t*K+K-1 added in ascending order (K = 2, 4, 8,
+ * 16 for n <= 512, 1024, 2048, 4096), combined by a fixed tree.  That order is the only difference from
+ * chamfer_distance.  out[a][b] = S_a / N + S_b / M.
+ * Determinism: no floating-point atomics; out[a][b] is bitwise the same on every run and whatever Na, Nb,
+ * slice or launch it was computed in; the matrix of (xyz2, xyz1) is bitwise the transpose of this one.
+ * Errors, all before any launch: FPSG_E_NULL for a null xyz1 or out; FPSG_E_SHAPE for Na, Nb, N or M < 1
+ * (or, in the symmetric mode, Nb != Na or M != N); FPSG_E_LIMIT for N or M > FPSG_CHAMFER_CROSS_MAX_N.
+ */
+#define FPSG_CHAMFER_CROSS_MAX_N 4096
+int fpsg_chamfer_cross(const float* xyz1, const float* xyz2, int Na, int Nb, int N, int M, float* out,
+                       fpsg_stream_t stream);
+
 /* ---- K4b: fused EdgeConv (gather + BatchNorm statistics + max over k) -----------------
  * Replaces the chain get_graph_feature -> Conv2d 1x1 -> BatchNorm2d -> LeakyReLU -> max_k of
  * src/dgcnn/model.py:23-42,53-56,63-76 without materialising [B,2C,N,k].  The caller first
