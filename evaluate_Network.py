@@ -7,7 +7,9 @@ every test episode (HIP Chamfer K1 + the HIP Sinkhorn divergence K2b, the form `
 ``Class: <c> -- Rec CD: <mean>; Rec EMD: <mean>`` (``--exact_emd``: followed by ``; Exact EMD: <mean>``, the
 exact transport distance of K12 divided by n_query like the other two; ``--set_metrics``: then
 ``; MMD-CD: <v>; COV-CD: <v>; 1-NNA-CD: <v>``, the set-level generation metrics of ``fpsg_amd.set_metrics`` over all
-the class's generated and reference query clouds, from K13's Chamfer matrices).  With ``--npy_folder`` the generated and
+the class's generated and reference query clouds, from K13's Chamfer matrices; ``--set_metrics_emd``: then
+``; MMD-EMD: <v>; COV-EMD: <v>; 1-NNA-EMD: <v>``, the same under the exact EMD from K14's matrices, followed by
+``; EMD-uncertified: <cov>/<nna>`` when some nearest-neighbour decisions are not certified by the EMD bounds).  With ``--npy_folder`` the generated and
 ground-truth clouds (+ a side-by-side PNG) of every item are dumped instead, which is the
 reference's commented-out "OPTION 2" (``:111``).
 
@@ -50,10 +52,11 @@ def main(opt):
     exact = bool(getattr(opt, "exact_emd", False))
     per_class_exact = defaultdict(list)
     sets = bool(getattr(opt, "set_metrics", False))
+    sets_emd = bool(getattr(opt, "set_metrics_emd", False))
     per_class_gen, per_class_ref = defaultdict(list), defaultdict(list)
     # the weights do not change while evaluating: transformed filters, stacked decoder weights and BatchNorm coefficients
     # are made once, not per item; on a GPU the item in front of the EMD is replayed as a hipGraph (engine.EvalItem)
-    with EvalItem(model, exact_emd=exact, return_clouds=sets) as run_item:
+    with EvalItem(model, exact_emd=exact, return_clouds=sets or sets_emd) as run_item:
         for item, sample in enumerate(dl_test):
             sample = to_device(sample, device)
             if getattr(opt, "npy_folder", ""):
@@ -66,7 +69,7 @@ def main(opt):
             per_class_emd[name].append(out["emd_loss"].item() / n_query)
             if exact:
                 per_class_exact[name].append(out["exact_emd"].item() / n_query)
-            if sets:                                    # kept on the device; one set per class after the loop
+            if sets or sets_emd:                        # kept on the device; one set per class after the loop
                 per_class_gen[name].append(out["syn_pc"])
                 per_class_ref[name].append(out["ref_pc_q"])
     per_class_set = {}
@@ -74,6 +77,12 @@ def main(opt):
         from fpsg_amd.set_metrics import generation_metrics
         for name in sorted(per_class_gen):
             per_class_set[name] = generation_metrics(torch.cat(per_class_gen[name]), torch.cat(per_class_ref[name]))
+    per_class_set_emd = {}
+    if sets_emd:
+        from fpsg_amd.set_metrics import emd_generation_metrics
+        for name in sorted(per_class_gen):
+            per_class_set_emd[name] = emd_generation_metrics(torch.cat(per_class_gen[name]),
+                                                             torch.cat(per_class_ref[name]))
     for name in sorted(per_class_cd):
         line = (f"Class: {name} -- Rec CD: {statistics.mean(per_class_cd[name])}; "
                 f"Rec EMD: {statistics.mean(per_class_emd[name])}")
@@ -82,8 +91,14 @@ def main(opt):
         if sets:
             m = per_class_set[name]
             line += f"; MMD-CD: {m['mmd_cd']}; COV-CD: {m['cov_cd']}; 1-NNA-CD: {m['nna_cd']}"
+        if sets_emd:
+            m = per_class_set_emd[name]
+            line += f"; MMD-EMD: {m['mmd_emd']}; COV-EMD: {m['cov_emd']}; 1-NNA-EMD: {m['nna_emd']}"
+            if m["cov_uncertified"] or m["nna_uncertified"]:
+                line += f"; EMD-uncertified: {m['cov_uncertified']}/{m['nna_uncertified']}"
         print(line)
-    return (per_class_cd, per_class_emd) + ((per_class_exact,) if exact else ()) + ((per_class_set,) if sets else ())
+    return (per_class_cd, per_class_emd) + ((per_class_exact,) if exact else ()) + ((per_class_set,) if sets else ()) + \
+        ((per_class_set_emd,) if sets_emd else ())
 
 
 if __name__ == "__main__":

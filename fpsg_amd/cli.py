@@ -12,7 +12,8 @@ Additions (all optional): ``--synthetic`` (file-free corpora of the reference's 
 ``torchrun``), ``--img_encoder_path`` (local VGG16-BN weights; nothing is downloaded),
 ``--resident`` (keep the corpora in HBM, assemble episodes on the device), ``--exact_emd`` (evaluation: the exact
 EMD per class beside the two reference metrics), ``--set_metrics`` (evaluation: MMD, COV and 1-NNA under the Chamfer
-distance per class, over the class's generated and reference query clouds).
+distance per class, over the class's generated and reference query clouds), ``--set_metrics_emd`` (the same under the
+exact EMD).
 """
 from __future__ import annotations
 
@@ -86,6 +87,9 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
         g.add_argument("--set_metrics", action="store_true",
                        help="Also report MMD-CD, COV-CD and 1-NNA-CD per class over all its generated and reference "
                             "query clouds (HIP Chamfer matrix, fpsg_amd.set_metrics);")
+        g.add_argument("--set_metrics_emd", action="store_true",
+                       help="Also report MMD-EMD, COV-EMD and 1-NNA-EMD per class over all its generated and reference "
+                            "query clouds (HIP exact EMD matrix, fpsg_amd.set_metrics);")
     return p
 
 

@@ -26,7 +26,7 @@
 //     capped pair too; a converged pair has gap <= N eps_final (eps-complementary slackness).
 // LDS: both clouds + prices (2 x 32 KB as float4 rows), owners, assignment, bidder list (3 x 8 KB), bids (16 KB) at
 // N = 2048 = FPSG_EMD_EXACT_MAX_N: 104 KB of the CU's 160 KB, one workgroup of 16 waves per CU.
-#include "fpsg_common.h"
+#include "emd_auction.h"
 
 namespace fpsg {
 namespace {
@@ -34,41 +34,7 @@ namespace {
 constexpr int kExThreads = 1024;
 constexpr int kExWaves = kExThreads / 64;
 constexpr int kExMaxN = FPSG_EMD_EXACT_MAX_N;
-constexpr float kExTheta = 0.25f;            // eps_{k+1} = eps_k / 4
-constexpr int kExPhaseRoundsPerPoint = 16;   // round cap of an intermediate phase: 16 N + 256
 constexpr int kExStats = 4;                  // ints of per-pair statistics in the workspace
-
-__device__ __forceinline__ float ex_cost(float ax, float ay, float az, float bx, float by, float bz) {
-  const float dx = ax - bx, dy = ay - by, dz = az - bz;
-  return __builtin_amdgcn_sqrtf(fma_rn(dz, dz, fma_rn(dy, dy, dx * dx)));
-}
-
-template <int M>
-__device__ __forceinline__ float xor_f(float v) { return __uint_as_float(lane_xor<M>(__float_as_uint(v))); }
-
-template <int M>
-__device__ __forceinline__ int xor_i(int v) { return (int)lane_xor<M>((unsigned)v); }
-
-// (best value, its rank, second-best value) of two lanes: the lower (value, rank) wins; the second best is the smaller
-// of the loser's best and the winner's second best.
-template <int M>
-__device__ __forceinline__ void fold_best2(float& b1, int& r1, float& b2) {
-  const float o1 = xor_f<M>(b1), o2 = xor_f<M>(b2);
-  const int orr = xor_i<M>(r1);
-  if (o1 < b1 || (o1 == b1 && orr < r1)) {
-    b2 = __builtin_fminf(b1, o2);
-    b1 = o1;
-    r1 = orr;
-  } else {
-    b2 = __builtin_fminf(b2, o1);
-  }
-}
-
-template <int M>
-__device__ __forceinline__ void fold_minmax(float& lo, float& hi) {
-  lo = __builtin_fminf(lo, xor_f<M>(lo));
-  hi = __builtin_fmaxf(hi, xor_f<M>(hi));
-}
 
 __global__ __launch_bounds__(kExThreads) void emd_exact_kernel(const float* __restrict__ xyz1,
                                                               const float* __restrict__ xyz2, int N, float eps_final,
@@ -106,8 +72,7 @@ __global__ __launch_bounds__(kExThreads) void emd_exact_kernel(const float* __re
   }
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
-    fold_minmax<1>(lo[d], hi[d]); fold_minmax<2>(lo[d], hi[d]); fold_minmax<4>(lo[d], hi[d]);
-    fold_minmax<8>(lo[d], hi[d]); fold_minmax<16>(lo[d], hi[d]); fold_minmax<32>(lo[d], hi[d]);
+    fold_minmax_wave(lo[d], hi[d]);
   }
   if (lane == 0) {
 #pragma unroll
@@ -121,9 +86,8 @@ __global__ __launch_bounds__(kExThreads) void emd_exact_kernel(const float* __re
     for (int w = 1; w < kExWaves; ++w) { l = __builtin_fminf(l, wred[w][d]); h = __builtin_fmaxf(h, wred[w][3 + d]); }
     ext[d] = h - l;
   }
-  const float diag = __builtin_amdgcn_sqrtf(fma_rn(ext[2], ext[2], fma_rn(ext[1], ext[1], ext[0] * ext[0])));
-  const float eps0 = __builtin_fmaxf(diag * 0.25f, eps_final);
-  const int phase_cap = kExPhaseRoundsPerPoint * N + 256;
+  const float eps0 = ex_eps0(ext, eps_final);
+  const int phase_cap = ex_phase_cap(N);
 
   int rounds = 0, phases = 0, last_rounds = 0;
   bool capped = false;
@@ -153,23 +117,16 @@ __global__ __launch_bounds__(kExThreads) void emd_exact_kernel(const float* __re
         int r1 = 0x7fffffff;
         for (int j = lane; j < N; j += 64) {
           const float4 o = objects[j];
-          const float v = ex_cost(xi.x, xi.y, xi.z, o.x, o.y, o.z) + o.w;
-          int rk = j - i;
-          if (rk < 0) rk += N;
-          if (v < b1 || (v == b1 && rk < r1)) { b2 = b1; b1 = v; r1 = rk; }
-          else b2 = __builtin_fminf(b2, v);
+          ex_scan(ex_cost(xi.x, xi.y, xi.z, o.x, o.y, o.z) + o.w, ex_rank(j, i, N), b1, r1, b2);
         }
         fold_best2<1>(b1, r1, b2); fold_best2<2>(b1, r1, b2); fold_best2<4>(b1, r1, b2);
         fold_best2<8>(b1, r1, b2); fold_best2<16>(b1, r1, b2); fold_best2<32>(b1, r1, b2);
         if (lane == 0) {
-          int j1 = r1 + i;
-          if (j1 >= N) j1 -= N;
+          const int j1 = ex_unrank(r1, i, N);
           if (N == 1) b2 = b1;                         // no second object
           const float pj = objects[j1].w;
-          const float nb = pj + ((b2 - b1) + eps);
-          // the increment is at least one ulp of the price, whatever eps is
-          const unsigned bits = nb > pj ? __float_as_uint(nb) : __float_as_uint(pj) + 1u;
-          atomicMax(&bid[j1], ((unsigned long long)bits << 32) | (unsigned)(~i));
+          const unsigned bits = ex_bid_bits(pj, b1, b2, eps);
+          atomicMax(&bid[j1], ex_bid_key(bits, i));
         }
       }
       __syncthreads();
@@ -177,12 +134,12 @@ __global__ __launch_bounds__(kExThreads) void emd_exact_kernel(const float* __re
       for (int j = tid; j < N; j += kExThreads) {
         const unsigned long long key = bid[j];
         if (key) {
-          const int w = (int)(~(unsigned)key);
+          const int w = ex_key_bidder(key);
           const int o = owner[j];
           if (o >= 0) asg[o] = -1;
           owner[j] = w;
           asg[w] = j;
-          objects[j].w = __uint_as_float((unsigned)(key >> 32));
+          objects[j].w = ex_key_price(key);
           bid[j] = 0ull;
         }
       }
@@ -197,16 +154,7 @@ __global__ __launch_bounds__(kExThreads) void emd_exact_kernel(const float* __re
   }
 
   if (capped) {                                        // complete the permutation: free objects in index order
-    if (tid == 0) {
-      int i = 0;
-      for (int j = 0; j < N; ++j) {
-        if (owner[j] >= 0) continue;
-        while (i < N && asg[i] >= 0) ++i;              // as many unassigned bidders as free objects
-        if (i == N) break;
-        asg[i] = j;
-        owner[j] = i;
-      }
-    }
+    if (tid == 0) ex_complete(owner, asg, N);
     __syncthreads();
   }
 

@@ -7,6 +7,8 @@ contiguity / dtype / device assertions.  There is no CPU path.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from . import _hip
@@ -381,6 +383,72 @@ def emd_exact(p1: torch.Tensor, p2: torch.Tensor, eps: float | None = None, max_
                       f"{EMD_EXACT_MAX_ROUNDS if max_rounds is None else max_rounds}); their cost is an upper bound "
                       f"within gap {info['gap'][capped].tolist()} of the exact EMD", EmdExactCapWarning, stacklevel=2)
     return (cost, info) if return_info else cost
+
+
+def emd_matrix(A: torch.Tensor, B: torch.Tensor | None = None, eps: float | None = None, max_rounds: int | None = None,
+               return_info: bool = False):
+    """All-pairs exact EMD matrix ``[Na,Nb]`` (K14, HIP): ``out[a][b]`` is the exact EMD of ``(A[a], B[b])`` as
+    ``emd_exact`` computes it (sum of matched distances, not divided by N) for clouds ``A [Na,N,3]`` and ``B [Nb,N,3]``
+    of equal size N <= 2048.  ``B=None``: ``A`` against itself, each unordered pair solved once with ``A[a]`` (a < b)
+    as bidders and mirrored, an exact-zero diagonal.
+
+    One ``eps`` serves the whole call: by default ``emd_exact_default_eps`` over the union of both sets, so an entry
+    is reproduced by ``emd_exact(A[a:a+1], B[b:b+1], eps=that_eps)`` -- same rounds and status, same cost and gap.
+    Deterministic: every entry is bitwise the same whatever set, slice or call it is computed in.  ``emd_matrix(B, A).T``
+    agrees with ``emd_matrix(A, B)`` within the gaps only (the bidder and object roles swap).
+
+    ``return_info=True``: returns ``(cost, info)`` with ``info["gap"] [Na,Nb]`` (``cost - gap <= EMD <= cost``),
+    ``info["status"]`` and ``info["rounds"]`` (int32 ``[Na,Nb]``) and ``info["eps"]``.  A pair capped at ``max_rounds``
+    (default ``EMD_EXACT_MAX_ROUNDS``) issues an ``EmdExactCapWarning`` naming its ``(a, b)``.  Forward only; no CPU
+    path (CPU tensors raise ``FpsgHipError``).  Raises ``ValueError`` for unequal N, N > 2048, empty sets and bad
+    shapes."""
+    sym = B is None
+    other = A if sym else B
+    if A.dim() != 3 or other.dim() != 3 or A.size(2) != 3 or other.size(2) != 3:
+        raise ValueError(f"expected [Na,N,3] and [Nb,N,3] clouds, got {tuple(A.shape)} and {tuple(other.shape)}")
+    if A.numel() == 0 or other.numel() == 0:
+        raise ValueError(f"empty sets or clouds are not supported (got {tuple(A.shape)} and {tuple(other.shape)})")
+    if A.size(1) != other.size(1):
+        raise ValueError(f"emd_matrix needs clouds of equal size, got N={A.size(1)} and N={other.size(1)}")
+    if A.size(1) > EMD_EXACT_MAX_N:
+        raise ValueError(f"emd_matrix supports at most {EMD_EXACT_MAX_N} points per cloud, got {A.size(1)}")
+    if A.device != other.device:
+        raise ValueError(f"device mismatch: {A.device} vs {other.device}")
+    if max_rounds is not None and int(max_rounds) < 1:
+        raise ValueError(f"max_rounds must be at least 1, got {max_rounds}")
+    if eps is not None and not (float(eps) > 0.0 and math.isfinite(float(eps))):
+        raise ValueError(f"eps must be positive and finite, got {eps}")
+    A = A.detach()
+    other = other.detach()
+    _hip.dev_tensor(A, torch.float32, "A")
+    _hip.dev_tensor(other, torch.float32, "B")
+    Na, N, _ = A.shape
+    Nb = other.size(0)
+    if eps is None:
+        eps = emd_exact_default_eps(A, other)
+    if max_rounds is None:
+        max_rounds = EMD_EXACT_MAX_ROUNDS
+    lib = _hip.load()
+    dev = A.device
+    cost = torch.empty((Na, Nb), dtype=torch.float32, device=dev)
+    gap = torch.empty((Na, Nb), dtype=torch.float32, device=dev)
+    status = torch.empty((Na, Nb), dtype=torch.int32, device=dev)
+    rounds = torch.empty((Na, Nb), dtype=torch.int32, device=dev)
+    ws_bytes = lib.fpsg_emd_cross_workspace_bytes(Na, Nb, N)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _probe("emd_cross", Na * Nb, N, N):
+        rc = lib.fpsg_emd_cross(_hip.ptr(A), None if sym else _hip.ptr(other), Na, Nb, N, float(eps), int(max_rounds),
+                                _hip.ptr(cost), _hip.ptr(gap), _hip.ptr(status), _hip.ptr(rounds), _hip.ptr(ws),
+                                ws_bytes, _hip.stream_of(A))
+    _hip.check(rc, "fpsg_emd_cross")
+    capped = [tuple(x) for x in torch.nonzero(status).tolist()]
+    if capped:
+        import warnings
+        warnings.warn(f"emd_matrix: pairs {capped} (a, b) hit the round cap (max_rounds={max_rounds}); their cost is an "
+                      f"upper bound within its gap of the exact EMD", EmdExactCapWarning, stacklevel=2)
+    if return_info:
+        return cost, {"gap": gap, "status": status, "rounds": rounds, "eps": float(eps)}
+    return cost
 
 
 def softmin(x: torch.Tensor, y: torch.Tensor, h: torch.Tensor, eps: float) -> torch.Tensor:

@@ -254,6 +254,29 @@ int fpsg_emd_exact(const float* xyz1, const float* xyz2, int B, int N, float eps
 int fpsg_chamfer_cross(const float* xyz1, const float* xyz2, int Na, int Nb, int N, int M, float* out,
                        fpsg_stream_t stream);
 
+/* ---- K14: all-pairs exact EMD matrix ---------------------------------------------------
+ * Between every cloud of xyz1 [Na,N,3] and every cloud of xyz2 [Nb,N,3] (fp32, contiguous, device, equal N):
+ * cost[a][b] = the exact EMD of the pair as fpsg_emd_exact computes it (sum of matched Euclidean distances,
+ * not divided by N), by K12's auction (same bids, same eps schedule from the pair's own bounding box, same
+ * caps): for the same eps_final and max_rounds, status and rounds equal K12's, and cost and gap are bitwise
+ * K12's.  Evaluation metric only (MMD / COV / 1-NNA under EMD); forward only, no assignment, no gradients.
+ * Outputs, all [Na,Nb]: cost, gap (cost - gap <= EMD <= cost), status (int32: 0 converged, 1 capped at
+ * max_rounds and completed) and, when not NULL, rounds (int32: auction rounds of the pair in all).
+ * xyz2 == NULL selects the symmetric mode, xyz1 against itself (Nb = Na): each unordered pair a < b is solved
+ * once with xyz1[a] as bidders and mirrored; the diagonal is exact zeros (cost, gap, status, rounds 0).
+ * ws: fpsg_emd_cross_workspace_bytes(Na,Nb,N) bytes, 8-byte aligned (the pair counter, zeroed on the
+ * stream before the launch).  One workgroup per pair; persistent workgroups, no floating-point atomics:
+ * every entry is bitwise the same whatever Na, Nb, slice or launch it was computed in.  Bounded work: at
+ * most max_rounds rounds per pair, no spin-wait.
+ * Errors, all before any launch: FPSG_E_NULL for a null xyz1, cost, gap, status or ws; FPSG_E_ALIGN for a
+ * misaligned xyz2, rounds or ws; FPSG_E_SHAPE for Na, Nb or N < 1, Nb != Na in the symmetric mode, eps_final
+ * not positive and finite, max_rounds < 1 or a workspace too small; FPSG_E_LIMIT for N > FPSG_EMD_EXACT_MAX_N.
+ */
+size_t fpsg_emd_cross_workspace_bytes(int Na, int Nb, int N);
+int fpsg_emd_cross(const float* xyz1, const float* xyz2, int Na, int Nb, int N, float eps_final, int max_rounds,
+                   float* cost, float* gap, int* status, int* rounds, void* ws, size_t ws_bytes,
+                   fpsg_stream_t stream);
+
 /* ---- K4b: fused EdgeConv (gather + BatchNorm statistics + max over k) -----------------
  * Replaces the chain get_graph_feature -> Conv2d 1x1 -> BatchNorm2d -> LeakyReLU -> max_k of
  * src/dgcnn/model.py:23-42,53-56,63-76 without materialising [B,2C,N,k].  The caller first
