@@ -16,18 +16,24 @@ Workloads (BASELINE.json ``configs``; synthetic data, random-init weights, fp32)
   c2            configs[1]: 1-way 1-shot 1-query, 1 episode per step
   c4            configs[3]: c3 with the DGCNN encoder
 
-Rank 0 prints ONE JSON line with ``roofline`` (the K1 Chamfer forward launches of the timed
-region, bracketed with HIP events on the launch stream) and ``cpu_baseline`` (the same
-episode step on the host cores through the CPU oracle; N=1 only).  At N=1 the line also carries
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes ``--dump-outputs`` if
+asked and prints rank 0's ONE JSON line.  Besides the headline the line carries figures that cost no run of their own:
+  ``roofline``  the K1 Chamfer forward launches of the timed region, bracketed with HIP events on the launch stream
+                (K1's backward likewise, as ``kernels.K1_chamfer_bwd_in_step``),
+  ``mfu_direct_equivalent``  the step's FLOPs counted as the REFERENCE formulation would spend them
+                (SURVEY.md 3.1 MAC counts, forward x 3) over the fp32 peak.
+``--full`` also measures everything else, after the timed region:
+  ``cpu_baseline``  the same episode step on the host cores through the CPU oracle (N=1 only),
   ``configs``   short legs of the other BASELINE workloads (c2, c3, c4: episodes/s each) and ``eval``: items/s of the
                 evaluation loop (``_return_reconstruction``: forward + Chamfer + Sinkhorn-form EMD) on the configs[2]
-                episode with K1's and K2b's event-timed shares,
+                episode with K1's and K2b's event-timed shares (N=1 only),
   ``kernels``   event-timed rooflines of the other hand-written distance / graph kernels at the
-                BASELINE shapes (K1 backward in-step; K2, K2b, K3, K4b as micro-legs), each with its
-                bound (valu / mfma / hbm), algorithmic work and fraction of peak,
-  ``mfu_direct_equivalent``  the step's FLOPs counted as the REFERENCE formulation would spend them
-                (SURVEY.md 3.1 MAC counts, forward x 3) over the fp32 peak;
-``--no-extra`` skips these legs.  At N>1 ``allreduce`` times each gradient bucket's collective.
+                BASELINE shapes (K2, K2b, K3, K4b, K5-K8 as micro-legs), each with its
+                bound (valu / mfma / hbm), algorithmic work and fraction of peak (N=1 only),
+  ``clock``     its second reading, under one more untimed step; for a graphed workload, ``roofline`` from an eager
+                replica of its episodes,
+  ``allreduce`` at N>1 (or with FPSG_FORCE_DIST): each gradient bucket's collective, timed on its own.
+``--no-extra`` skips ``configs`` and the micro-legs of ``kernels``, ``--no-cpu-baseline`` the CPU leg.
 ``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (see ``dump_outputs``).
 """
 from __future__ import annotations
@@ -575,10 +581,13 @@ def dump_outputs(path, results, model):
     print(f"[bench] --dump-outputs: {len(arrays)} arrays, {total / 2**20:.1f} MiB in {path}", file=sys.stderr, flush=True)
 
 
-def run_workload(wl, args, rank, world, device, steps, warmup, probe=None, graph=None, epr=None, dump_dir=None):
+def run_workload(wl, args, rank, world, device, steps, warmup, probe=None, graph=None, epr=None, dump_dir=None,
+                 full=False):
     """Builds the model of workload ``wl`` and times ``steps`` optimizer steps after ``warmup`` (the contract's
     timed region: barrier + synchronize on both sides, MAX over ranks).  Returns a dict of results.  ``dump_dir``:
-    rank 0 writes the last timed step's outputs there (``dump_outputs``), after the timed region."""
+    rank 0 writes the last timed step's outputs there (``dump_outputs``), after the timed region.  ``full``: with a
+    ``probe``, also run what only ``--full`` reports (the clock under one more step, a graphed workload's eager K1
+    replica) after the timed region."""
     S, Q, intra, encoder, epr_default, desc = WORKLOADS[wl]
     epr = epr or epr_default
     if graph is None:
@@ -622,14 +631,14 @@ def run_workload(wl, args, rank, world, device, steps, warmup, probe=None, graph
     if dump_dir is not None and rank == 0:   # before the untimed step below changes the weights again
         dump_outputs(dump_dir, out, model)
     sclk_after = None
-    if probe is not None and world == 1:      # the headline run on one GPU: one extra untimed step, clock read under it
+    if full and probe is not None and world == 1:   # the headline run on one GPU: one extra untimed step, clock read under it
         was = probe.enabled
         probe.enabled = False
         step(episodes, n_episodes_global=epr * world)
         sclk_after = gpu_clock_mhz(device)
         torch.cuda.synchronize()
         probe.enabled = was
-    if probe is not None and graph:
+    if full and probe is not None and graph:
         # HIP events cannot be timed inside a captured graph: the K1 launches are bracketed in
         # an eager replica of the same episodes (same tensors, same neighbouring kernels) run
         # right after the timed region; profiles/ holds the rocprofv3 durations of the replays.
@@ -692,10 +701,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c5")
     ap.add_argument("--episodes-per-rank", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what the headline does not need: the CPU baseline, "
+                         "the N=1 extra legs, the clock under one more step, a graphed workload's eager K1 replica, "
+                         "the per-bucket all-reduce at N>1")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the N=1 extra legs (other workloads' episodes/s, per-kernel rooflines)")
+                    help="with --full: skip the N=1 extra legs (other workloads' episodes/s, per-kernel rooflines)")
     ap.add_argument("--bucket-mb", type=float, default=80.0)
     ap.add_argument("--graph", dest="graph", action="store_true", default=None,
                     help="replay each episode's fwd+bwd as a captured hipGraph [default: only for the "
@@ -742,10 +755,12 @@ def main():
     probe = EventProbe()
     metrics.set_launch_probe(probe)
     main_run = run_workload(args.workload, args, rank, world, device, steps, warmup, probe=probe, graph=args.graph,
-                            epr=epr, dump_dir=args.dump_outputs)
+                            epr=epr, dump_dir=args.dump_outputs, full=args.full)
     steps, warmup = main_run["steps"], main_run["warmup"]
     elapsed = main_run["elapsed"]
-    allreduce = allreduce_probe(main_run["step"], world) if world > 1 or os.environ.get("FPSG_FORCE_DIST") else None
+    allreduce = None
+    if args.full and (world > 1 or os.environ.get("FPSG_FORCE_DIST")):
+        allreduce = allreduce_probe(main_run["step"], world)
 
     n_l, sec, pairs, nbytes, flops = probe.summary("chamfer_fwd")
     nb_l, bsec, bpairs, _, _ = probe.summary("chamfer_bwd")
@@ -815,7 +830,7 @@ def main():
                 "work": "114,688 algorithmic bytes per cloud pair (idx + clouds read, gradients written; the loss sums' per-pair "
                         "constants are formed in the kernel); one workgroup per (pair, side): LDS sort of the "
                         "argmin list + blocked ascending sums, time independent of the in-degree distribution"}
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             del main_run["step"]
             torch.cuda.empty_cache()
             configs = {}
@@ -867,7 +882,7 @@ def main():
         if allreduce is not None:
             res["allreduce"] = {"buckets": allreduce, "note": "one blocking all_reduce per gradient bucket after the "
                                 "timed region (in the step they are launched from autograd hooks and overlap backward)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(S, Q, intra, encoder, args.cpu_baseline_seconds)
             except Exception as e:  # the GPU numbers stay valid without the CPU leg

@@ -24,7 +24,7 @@ def _free_port():
 def test_single_rank_rccl_step(gpu, extra):
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(_free_port()), FPSG_FORCE_DIST="1", PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "c2", "--steps", "3", "--warmup", "4",
+    r = subprocess.run([sys.executable, "bench.py", "--workload", "c2", "--steps", "3", "--warmup", "4", "--full",
                         "--no-cpu-baseline", "--no-extra"] + extra, cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -44,7 +44,7 @@ def test_two_ranks_share_the_gpu_over_gloo(gpu):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
-                        "--workload", "c3", "--steps", "2", "--warmup", "1", "--episodes-per-rank", "2"],
+                        "--workload", "c3", "--steps", "2", "--warmup", "1", "--episodes-per-rank", "2", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -19,7 +19,7 @@ if not os.path.exists(out) and os.path.exists(seed) and "--fresh" not in sys.arg
     shutil.copyfile(seed, out)          # keep the existing records, time only shapes that are new
 for wl, extra in (("c5", []), ("c4", []), ("c2", ["--no-graph"]), ("c3", [])):
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", wl, "--gemm-tuning", "tune", "--gemm-records", out,
-           "--no-cpu-baseline", "--steps", "1", "--warmup", "1"] + extra
+           "--full", "--no-cpu-baseline", "--steps", "1", "--warmup", "1"] + extra
     print("[tune_gemm]", " ".join(cmd), flush=True)
     rc = subprocess.call(cmd, stdout=subprocess.DEVNULL)
     n = sum(1 for line in open(out) if not line.startswith("Validator")) if os.path.exists(out) else 0
