@@ -23,9 +23,13 @@
 // read 512 contiguous bytes (conflict-free).  Two stages in LDS, one barrier per k-step: global loads of step k+1 are
 // issued before the MFMAs of step k, converted and written after them.
 //
-// Work split: 512 threads = 8 waves as 2 x 4 (rows x columns), one 32x32 accumulator block per (32 rows, 32 columns) of
-// the wave's share; workgroup tile 256 x 256 x 16 (variant 0) or 256 x 128 x 32 (variant 1).  Workgroups that share an
+// Work split: 4 or 8 waves as rows x columns of the workgroup tile, one 32x32 accumulator block per (32 rows, 32 columns)
+// of the wave's share; the tiles are listed in kTiles (`variant` = tile + 10 * splits; -1 picks).  Workgroups that share an
 // XCD (blockIdx mod 8) get consecutive tiles of one batch (they share A[b] through that XCD's L2).
+//
+// Every build in this file computes the product: the entry points refuse, on the host, every variant id they do not list.
+// The measurement-only builds of round 5 (loops without their loads, stores or split; delayed starts; no wave priorities)
+// are gone from the tree; what they measured is in profiles/r05/gemm_split_ablation.txt and DESIGN.md (K10).
 #include "fpsg_common.h"
 
 namespace fpsg {
@@ -50,9 +54,6 @@ struct GemmArgs {
   int nt_c;                  // non-temporal stores of C
   long packed_floats;        // PACKA builds: A is the packed image (fpsg_gemm_split_pack_a, 128-row tiles), this many floats
   int stages_a;              //               and ceil(K / 16) stages per row tile
-  int stagger_mode;          // measurement (variant >= 100000): the first round's workgroups of one CU start stagger_ticks
-  int stagger_per_cu;        //   (10 ns units) apart, so that their tile stores do not coincide; mode 1: co-resident
-  int stagger_ticks;         //   workgroups = blockIdx 256 apart, mode 2: consecutive blockIdx
 };
 
 __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
@@ -88,8 +89,6 @@ __device__ __forceinline__ void set_wave_priority(int p) {
 // v_lshrrev + v_perm pair: 8 vector instructions per fragment, 6 per MFMA in these kernels, on the critical path of
 // every product (found with SQ_INSTS_VALU: 37 M in a build that should have had none; the first versions of this
 // file ran at half their MFMA rate because of it).
-__device__ __forceinline__ void keep_alive(const f32x16& v) { asm volatile("" ::"v"(v)); }   // measurement builds
-
 typedef u32x4 frag_t;      // carried as four dwords through the control flow, cast to 8 x bf16 only AT the MFMA
 __device__ __forceinline__ frag_t lds_frag(const unsigned char* p) { return *reinterpret_cast<const u32x4*>(p); }
 __device__ __forceinline__ f32x16 mfma_bf16(frag_t a, frag_t b, f32x16 c) {
@@ -183,15 +182,6 @@ struct ContigStage {
       for (int j = 0; j < 8; ++j) v[n][j] = k + j < k_end ? v[n][j] : 0.f;
     }
   }
-  __device__ __forceinline__ void split_only() {        // ablation builds: the arithmetic kept alive, nothing stored
-#pragma unroll
-    for (int n = 0; n < ITEMS; ++n) {
-      u32x4 p1, p2, p3;
-      split8(v[n], p1, p2, p3);
-      asm volatile("" ::"v"(p1), "v"(p2), "v"(p3));
-      v[n][0] = __uint_as_float(p3[0] ^ p2[1]);
-    }
-  }
   __device__ __forceinline__ void store(unsigned char* lds, int tid) const {
 #pragma unroll
     for (int n = 0; n < ITEMS; ++n) {
@@ -243,7 +233,6 @@ struct PackedStage {
         p[n][t] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off[n] + t * (KG * (R / 64) * 1024), sbase, 0));
   }
   __device__ __forceinline__ void mask_tail(int, int, int) {}
-  __device__ __forceinline__ void split_only() {}
   __device__ __forceinline__ void store(unsigned char* lds, int tid) const {
 #pragma unroll
     for (int n = 0; n < ITEMS; ++n) {
@@ -289,15 +278,6 @@ struct StridedStage {
         v[n][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off[n], (unsigned)(k0 + j) * ld4, 0));
   }
   __device__ __forceinline__ void mask_tail(int, int, int) {}      // rows beyond K lie beyond the buffer: zeros already
-  __device__ __forceinline__ void split_only() {
-#pragma unroll
-    for (int n = 0; n < ITEMS; ++n) {
-      u32x4 p1, p2, p3;
-      split8(v[n], p1, p2, p3);
-      asm volatile("" ::"v"(p1), "v"(p2), "v"(p3));
-      v[n][0] = __uint_as_float(p3[0] ^ p2[1]);
-    }
-  }
   __device__ __forceinline__ void store(unsigned char* lds, int tid) const {
 #pragma unroll
     for (int n = 0; n < ITEMS; ++n) {
@@ -315,8 +295,7 @@ struct StridedStage {
 };
 
 // WR x WC waves (rows x columns of the tile); MINW: waves per SIMD the register allocation must leave room for
-// ABL (measurements only, results wrong): 1 = no global loads in the loop, 2 = nor LDS stores, 3 = nor the split
-template <int BM, int BN, int BK, int WR, int WC, int MINW, bool TRANSB, bool PRIO, bool PIPE = false, int ABL = 0, bool PACKA = false>
+template <int BM, int BN, int BK, int WR, int WC, int MINW, bool TRANSB, bool PIPE = false, bool PACKA = false>
 __global__ __launch_bounds__(64 * WR * WC, MINW) void gemm_split_kernel(const GemmArgs g) {
   constexpr int kThreads = 64 * WR * WC;
   constexpr int WM = BM / WR, WN = BN / WC, TI = WM / 32, TJ = WN / 32;
@@ -338,18 +317,11 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void gemm_split_kernel(const Ge
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform for the compiler too (scalar offsets, no waterfall)
-  if (g.stagger_mode && bid < 256 * g.stagger_per_cu) {
-    const int phase = g.stagger_mode == 1 ? (bid / 256) % g.stagger_per_cu : bid % g.stagger_per_cu;
-    if (phase) {
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime(), wait = (unsigned long long)phase * g.stagger_ticks;
-      while (__builtin_amdgcn_s_memrealtime() - t0 < wait) __builtin_amdgcn_s_sleep(32);
-    }
-  }
   // Co-resident waves of one SIMD run the same program; under the default (round-robin) arbitration they fall into
   // lock-step -- all in their MFMA block, then all in their conversion block with the matrix pipe idle (measured:
   // SQ_WAIT_INST_ANY = 3x the MFMA busy time, pipe 46 % busy).  Distinct static priorities make the arbitration strict:
   // the higher wave runs its MFMA block at full rate and the others fill the pipe while it converts.
-  if (PRIO) set_wave_priority(WR * WC >= 8 ? (2 * (bid & 1) + (wave >= WR * WC / 2 ? 1 : 0)) : bid % 3);
+  set_wave_priority(WR * WC >= 8 ? (2 * (bid & 1) + (wave >= WR * WC / 2 ? 1 : 0)) : bid % 3);
   const int m0 = tm * BM, n0 = tn * BN;
   const int k_begin = split * g.k_per_split;
   const int k_end = min(g.K, k_begin + g.k_per_split);
@@ -366,23 +338,16 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void gemm_split_kernel(const Ge
   rb.init(g.ldb, n0, g.N, tid);
   auto load = [&](int kt) {                             // stage kt -> registers
     const int k0 = k_begin + kt * BK;
-    if (ABL >= 1 && kt > 1) return;
     ra.load(rsA, k0);
     rb.load(rsB, k0);
   };
   auto store = [&](int kt) {                            // registers -> split -> LDS stage kt & 1
     const int k0 = k_begin + kt * BK;
-    if (ABL >= 3 && kt > 1) return;
     if (k0 + BK > k_end) {                              // workgroup-uniform
       ra.mask_tail(k0, k_end, tid);
       rb.mask_tail(k0, k_end, tid);
     }
     unsigned char* d = lds + (kt & 1) * STAGE;
-    if (ABL == 2 && kt > 1) {                           // the split's arithmetic without its LDS stores
-      ra.split_only();
-      rb.split_only();
-      return;
-    }
     ra.store(d, tid);
     rb.store(d + StageA::BYTES, tid);
   };
@@ -756,9 +721,7 @@ struct PersistArgs {
 
 constexpr int kMaxPieces = 40;
 
-// ABL (measurements only, wrong results): 1 = no DMA in the loop, 2 = no B loads / split / LDS stores, 3 = neither,
-// 4 = 3 without the tiles' stores
-template <int BN, bool KTAIL, int ABL = 0>       // KTAIL: K is no multiple of 16 (the last k-step's rows beyond K are zeroed)
+template <int BN, bool KTAIL>       // KTAIL: K is no multiple of 16 (the last k-step's rows beyond K are zeroed)
 __global__ __launch_bounds__(512, 2) void gemm_split_pnn_kernel(const PersistArgs g) {
   // 8 waves, each 32 rows x BN columns of the tile: the COLUMNS are the serial dimension of a wave (TJ blocks of 32), so a
   // piece narrower than BN costs every wave proportionally less -- equal column shares are equal times, whatever the
@@ -942,7 +905,7 @@ __global__ __launch_bounds__(512, 2) void gemm_split_pnn_kernel(const PersistArg
       for (int t = 0; t < 3; ++t)
         fa[t] = lds_frag((cur + a_off + t * KG * PSA));
       read_b(0, fb[0]);
-      if (ABL != 2 && ABL < 3) mask_b(kt_b1);
+      mask_b(kt_b1);
 #pragma unroll
       for (int j = 0; j < TJ; ++j) {
         if (j < nj) {                                                       // wave-uniform
@@ -958,23 +921,20 @@ __global__ __launch_bounds__(512, 2) void gemm_split_pnn_kernel(const PersistArg
           acc[j] = c;
         }
         // the split of B(s+1) in four parts behind the first column blocks' MFMAs (11 vector instructions each)
-        if (ABL != 2 && ABL < 3 && j < 4 && converts) split_pair(j);
+        if (j < 4 && converts) split_pair(j);
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (ABL != 2 && ABL < 3) {
-        if (TJ < 4) {
+      if (TJ < 4) {
 #pragma unroll
-          for (int q = TJ; q < 4; ++q) split_pair(q);
-        }
-        store_b(slot1);
-        kt_b1 = cb.kt;
-        load_b(cb);                      // (beyond the end of the stream: a harmless repeat of the last stage)
+        for (int q = TJ; q < 4; ++q) split_pair(q);
       }
+      store_b(slot1);
+      kt_b1 = cb.kt;
+      load_b(cb);                        // (beyond the end of the stream: a harmless repeat of the last stage)
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (s + 2 < S && ABL != 1 && ABL < 3) dma_a(ca, slot2);                // the youngest operations of the iteration
-    if (ABL) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    else if (s + 2 < S) asm volatile("s_waitcnt vmcnt(11) lgkmcnt(0)" ::: "memory");
+    if (s + 2 < S) dma_a(ca, slot2);                                       // the youngest operations of the iteration
+    if (s + 2 < S) asm volatile("s_waitcnt vmcnt(11) lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -982,14 +942,6 @@ __global__ __launch_bounds__(512, 2) void gemm_split_pnn_kernel(const PersistArg
     advance(cb);
     slot = slot1;
     if (++kt == nsteps) {                                                  // tile finished: its stores go out behind the barrier
-      if (ABL == 4) {                                                      // (measurement: the products kept alive, nothing stored)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) {
-          keep_alive(acc[j]);
-#pragma unroll
-          for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-        }
-      } else
       epilogue(piece);
       kt = 0;
       ++piece;
@@ -1010,11 +962,9 @@ __global__ __launch_bounds__(512, 2) void gemm_split_pnn_kernel(const PersistArg
 // the raw stage that landed a step ago from LDS into the bf16 planes.  Every vmcnt wait is written by hand; one
 // workgroup-wide s_barrier per step hands a ring slot over.  Same ranges / pieces as gemm_split_pnn_kernel; tile 256 x BN.
 // Needs ldb, sB, the range starts (multiples of 32) and B itself aligned to 4 floats (16-byte DMA of B rows).
-// ABL (measurement builds, results meaningless): 1 = producers only meet the barriers, 3 = no B path, 4 = consumers only
-// meet the barriers, 5 = consumers without the tile stores, 6 = 1 + 5
 // Two builds: BM 256 / rings of 3 (one workgroup per CU, 138 KB of LDS), and BM 128 / A ring of 2 (two workgroups per CU,
 // 76 KB each, 128 registers: one workgroup's store burst and barrier waits overlap the other's products).
-template <int BM, int BN, int RA, int RR, int MINW, bool KTAIL, int ABL = 0>
+template <int BM, int BN, int RA, int RR, int MINW, bool KTAIL>
 __global__ __launch_bounds__(512, MINW) void gemm_split_ws_kernel(const PersistArgs g) {
   constexpr int BK = 16, KG = 2, NC = 4, NP = 4;                           // consumer / producer waves
   constexpr int TI = BM / NC / 32, TJ = BN / 32;                           // a consumer: BM / 4 rows x BN columns
@@ -1075,11 +1025,6 @@ __global__ __launch_bounds__(512, MINW) void gemm_split_ws_kernel(const PersistA
   if (wave >= NC) {
     // ------------------------------------------------------------------ producers
     const int pw = wave - NC, pt = tid - 64 * NC;
-    if constexpr (ABL == 1 || ABL == 6) {
-      __builtin_amdgcn_s_barrier();
-      for (int s = 0; s < S; ++s) __builtin_amdgcn_s_barrier();
-      return;
-    }
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<u32x4*>(g.Ap), 0, (int)((long)g.batchq * nsteps * (CHUNKS * 1024)), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
@@ -1154,21 +1099,20 @@ __global__ __launch_bounds__(512, MINW) void gemm_split_ws_kernel(const PersistA
       const int sa_new = sa == 0 ? RA - 1 : sa - 1;  // (s + RA - 1) % RA: the slot stage s - 1 was read from
       const int sr1 = sr == RR - 1 ? 0 : sr + 1;
       // raw B(s+1) landed before the previous barrier
-      if constexpr (ABL != 3) convert_b(sr1, sb ^ 1);
+      convert_b(sr1, sb ^ 1);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       // before stage s+1 is handed over, A(s+1) and raw B(s+2) must have landed: with RA = 3 both were issued a step ago
       // (only this step's operations may be outstanding); with RA = 2 A(s+1) is issued now, FIRST, and only this step's raw
       // B(s+RR) may be outstanding
       if constexpr (RA == 3) {
-        if constexpr (ABL != 3) dma_b(cb, sr);       // raw(s+RR) -> the slot of raw(s), converted in step s-1
+        dma_b(cb, sr);                               // raw(s+RR) -> the slot of raw(s), converted in step s-1
         dma_a(ca, sa_new);
-        if constexpr (ABL != 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_A + DMA_B) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_A) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_A + DMA_B) : "memory");
       } else {
         dma_a(ca, sa_new);
-        if constexpr (ABL != 3) dma_b(cb, sr);
-        if constexpr (ABL != 3 && RR == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_B) : "memory");
+        dma_b(cb, sr);
+        if constexpr (RR == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_B) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       __builtin_amdgcn_s_barrier();
@@ -1194,12 +1138,8 @@ __global__ __launch_bounds__(512, MINW) void gemm_split_ws_kernel(const PersistA
   const int r = lane & 31, h = lane >> 5;
   const int a_off = h * PSA + (wave * (BM / NC) + r) * 16;                 // + 512 per row block
   const int b_off = h * PSB + r * 16;                                      // + 512 per column block
-  if constexpr (ABL != 1 && ABL != 6) __builtin_amdgcn_s_barrier();        // (P)
+  __builtin_amdgcn_s_barrier();                                            // (P)
   __builtin_amdgcn_s_barrier();                                            // (0)
-  if constexpr (ABL == 4) {
-    for (int s = 0; s < S; ++s) __builtin_amdgcn_s_barrier();
-    return;
-  }
   int kt = 0, piece = 0, sa = 0, sb = 0;
   int nj = (piece_w(0) + 31) / 32;
   for (int s = 0; s < S; ++s) {
@@ -1237,14 +1177,7 @@ __global__ __launch_bounds__(512, MINW) void gemm_split_ws_kernel(const PersistA
     if (++kt == nsteps) {                                                  // tile finished: stores nobody waits for
       const int q = piece_q(piece), c0 = piece_c(piece), w = piece_w(piece);
       const int batch = q / g.tiles_m, tm = q - batch * g.tiles_m;
-      if ((ABL != 5 && ABL != 6) || g.M < 0)
-        store_tile<TI, TJ>(acc, g.C + batch * g.sC, g.M, g.N, g.ldc, tm * BM + wave * (BM / NC), c0, c0 + w, lane, 0);
-      else {
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-          for (int j = 0; j < TJ; ++j) keep_alive(acc[i][j]);
-      }
+      store_tile<TI, TJ>(acc, g.C + batch * g.sC, g.M, g.N, g.ldc, tm * BM + wave * (BM / NC), c0, c0 + w, lane, 0);
 #pragma unroll
       for (int i = 0; i < TI; ++i)
 #pragma unroll
@@ -1515,24 +1448,13 @@ constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
 
 struct Plan {
   int tile, bm, bn, bk, tiles_m, tiles_n, splits, k_per_split;
-  bool prio;
-  int abl;
-  int stagger_mode, stagger_us;
 };
 
-// variant: -1 automatic; else tile + 10 * splits (splits 0 = automatic)
+// variant: -1 automatic; else tile + 10 * splits (tile 0-7, splits 0-99, 0 = automatic); false for every other id
 bool plan_for(int batch, int M, int N, int K, int transB, int variant, Plan* p) {
-  p->stagger_mode = p->stagger_us = 0;
-  if (variant >= 100000) {      // measurement: 100000 * mode + 10 * microseconds + tile (GemmArgs::stagger_*)
-    p->stagger_mode = variant / 100000;
-    p->stagger_us = (variant % 100000) / 10;
-    if (p->stagger_mode > 2) return false;
-    variant %= 10;
-  }
+  if (variant < -1 || variant >= 1000) return false;
   int tile = variant < 0 ? -1 : variant % 10;
-  int splits = variant < 0 ? 0 : (variant / 10) % 100;
-  p->prio = variant < 0 || variant < 1000 || variant >= 2000;   // + 1000: without the static wave priorities (A/B)
-  p->abl = variant >= 2000 ? variant / 1000 - 1 : 0;             // + 2000 / 3000 / 4000: ablation builds (tiles 0, 2; NN)
+  int splits = variant < 0 ? 0 : variant / 10;
   if (tile >= kNumTiles) return false;
   const long cus = 256;
   // measured (tools/bench_gemm_split.py, profiles/r05/gemm_split_variants.txt): the 128 x 128 tiles with three
@@ -1574,13 +1496,13 @@ struct PaTile { int bm, bn, bk, threads; };
 // registers from the image packed for variant 2
 constexpr PaTile kPaTiles[] = {{256, 128, 16, 512}, {256, 256, 16, 512}, {128, 128, 16, 256}, {128, 128, 16, 256}};
 constexpr int kNumPaTiles = sizeof(kPaTiles) / sizeof(kPaTiles[0]);
-inline int pa_tile(int variant) { return variant < 0 ? 0 : variant; }
+inline int pa_tile(int variant) { return variant == -1 ? 0 : variant; }   // < -1 or >= kNumPaTiles: refused
 }  // namespace
 }  // namespace fpsg
 
 extern "C" size_t fpsg_gemm_split_packed_a_bytes(int batch, int M, int K, int variant) {
   const int t = fpsg::pa_tile(variant);
-  if (batch <= 0 || M <= 0 || K <= 0 || t >= fpsg::kNumPaTiles) return 0;
+  if (batch <= 0 || M <= 0 || K <= 0 || t < 0 || t >= fpsg::kNumPaTiles) return 0;
   const fpsg::PaTile& p = fpsg::kPaTiles[t];
   const long tiles_m = (M + p.bm - 1) / p.bm, stages = (K + p.bk - 1) / p.bk;
   return (size_t)batch * tiles_m * stages * 3 * (p.bk / 8) * p.bm * 16;
@@ -1591,7 +1513,7 @@ extern "C" int fpsg_gemm_split_pack_a(const float* A, int batch, int M, int K, i
   using namespace fpsg;
   const int t = pa_tile(variant);
   FPSG_REQUIRE(batch > 0 && M > 0 && K > 0 && lda >= K, FPSG_E_SHAPE, "fpsg_gemm_split_pack_a: bad shape");
-  FPSG_REQUIRE(t < kNumPaTiles, FPSG_E_SHAPE, "fpsg_gemm_split_pack_a: unknown variant %d", variant);
+  FPSG_REQUIRE(t >= 0 && t < kNumPaTiles, FPSG_E_SHAPE, "fpsg_gemm_split_pack_a: unknown variant %d", variant);
   FPSG_REQUIRE_PTR(A);
   FPSG_REQUIRE_PTR(Ap);
   FPSG_REQUIRE((reinterpret_cast<uintptr_t>(Ap) & 15) == 0, FPSG_E_ALIGN, "fpsg_gemm_split_pack_a: Ap must be 16-byte aligned");
@@ -1612,7 +1534,7 @@ extern "C" int fpsg_gemm_split_nn_packed(const void* Ap, const float* B, float* 
   using namespace fpsg;
   const int t = pa_tile(variant);
   FPSG_REQUIRE(batch > 0 && M > 0 && N > 0 && K > 0 && ldb >= N && ldc >= N, FPSG_E_SHAPE, "fpsg_gemm_split_nn_packed: bad shape");
-  FPSG_REQUIRE(t < kNumPaTiles, FPSG_E_SHAPE, "fpsg_gemm_split_nn_packed: unknown variant %d", variant);
+  FPSG_REQUIRE(t >= 0 && t < kNumPaTiles, FPSG_E_SHAPE, "fpsg_gemm_split_nn_packed: unknown variant %d", variant);
   FPSG_REQUIRE_PTR(Ap);
   FPSG_REQUIRE_PTR(B);
   FPSG_REQUIRE_PTR(C);
@@ -1629,7 +1551,7 @@ extern "C" int fpsg_gemm_split_nn_packed(const void* Ap, const float* B, float* 
     FPSG_REQUIRE(a.packed_floats < (1L << 30), FPSG_E_LIMIT, "fpsg_gemm_split_nn_packed: the packed A must stay below 4 GiB");
     const long blocks = (long)batch * a.tiles_m * a.tiles_n;
     FPSG_REQUIRE(blocks < (1L << 30), FPSG_E_LIMIT, "fpsg_gemm_split_nn_packed: too many tiles");
-    hipLaunchKernelGGL((gemm_split_kernel<128, 128, 16, 2, 2, 3, false, true, true, 0, true>), dim3((unsigned)blocks), dim3(256), 0,
+    hipLaunchKernelGGL((gemm_split_kernel<128, 128, 16, 2, 2, 3, false, true, true>), dim3((unsigned)blocks), dim3(256), 0,
                        static_cast<hipStream_t>(stream), a);
     return launch_status("fpsg_gemm_split_nn_packed (register-staged)");
   }
@@ -1654,7 +1576,9 @@ extern "C" int fpsg_gemm_split_nn_persistent(const void* Ap, const float* B, flo
                                              int ldc, long sB, long sC, int variant, fpsg_stream_t stream) {
   using namespace fpsg;
   FPSG_REQUIRE(batch > 0 && M > 0 && N > 0 && K > 0 && ldb >= N && ldc >= N, FPSG_E_SHAPE, "fpsg_gemm_split_nn_persistent: bad shape");
-  FPSG_REQUIRE(variant >= -1 && variant <= 14, FPSG_E_SHAPE, "fpsg_gemm_split_nn_persistent: unknown variant %d", variant);
+  // -1 / 0 / 1: every wave stages and multiplies (256 / 256 / 128 columns); 6, 12, 13, 14: specialised waves
+  FPSG_REQUIRE(variant == -1 || variant == 0 || variant == 1 || variant == 6 || (variant >= 12 && variant <= 14), FPSG_E_SHAPE,
+               "fpsg_gemm_split_nn_persistent: unknown variant %d", variant);
   FPSG_REQUIRE_PTR(Ap);
   FPSG_REQUIRE_PTR(B);
   FPSG_REQUIRE_PTR(C);
@@ -1679,33 +1603,18 @@ extern "C" int fpsg_gemm_split_nn_persistent(const void* Ap, const float* B, flo
     FPSG_REQUIRE(ldb % 4 == 0 && sB % 4 == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0, FPSG_E_SHAPE,
                  "fpsg_gemm_split_nn_persistent: the specialised-wave form moves B rows by 16-byte DMA (ldb, sB, B aligned to 4 floats)");
     // 6 / 12: 256 x 128 tiles, one workgroup per CU (12: staggered first pieces); 13 / 14: 128 x 128 tiles, two per CU
-    // (A packed for 128-row tiles: fpsg_gemm_split_pack_a variant 2); 7..11: ablation builds of 6 (ABL 1, 6, 3, 4, 5)
+    // (A packed for 128-row tiles: fpsg_gemm_split_pack_a variant 2)
     const dim3 gr((unsigned)grid), bl(512);
-#define FPSG_WS(BM_, RA_, RR_, MINW_, ABL_)                                                                               \
-  do {                                                                                                                    \
-    if (ktail) hipLaunchKernelGGL((gemm_split_ws_kernel<BM_, 128, RA_, RR_, MINW_, true, ABL_>), gr, bl, 0, s, g);        \
-    else hipLaunchKernelGGL((gemm_split_ws_kernel<BM_, 128, RA_, RR_, MINW_, false, ABL_>), gr, bl, 0, s, g);             \
+#define FPSG_WS(BM_, RA_, RR_, MINW_)                                                                               \
+  do {                                                                                                              \
+    if (ktail) hipLaunchKernelGGL((gemm_split_ws_kernel<BM_, 128, RA_, RR_, MINW_, true>), gr, bl, 0, s, g);        \
+    else hipLaunchKernelGGL((gemm_split_ws_kernel<BM_, 128, RA_, RR_, MINW_, false>), gr, bl, 0, s, g);             \
   } while (0)
-    switch (variant) {
-      case 12: g.nt_c |= 2; [[fallthrough]];
-      case 6: FPSG_WS(256, 3, 3, 2, 0); break;
-      case 14: g.nt_c |= 2; [[fallthrough]];
-      case 13: FPSG_WS(128, 2, 3, 4, 0); break;
-      case 7: FPSG_WS(256, 3, 3, 2, 1); break;
-      case 8: FPSG_WS(256, 3, 3, 2, 6); break;
-      case 9: FPSG_WS(256, 3, 3, 2, 3); break;
-      case 10: FPSG_WS(256, 3, 3, 2, 4); break;
-      default: FPSG_WS(256, 3, 3, 2, 5); break;
-    }
+    if (variant == 12 || variant == 14) g.nt_c |= 2;
+    if (variant >= 13) FPSG_WS(128, 2, 3, 4);
+    else FPSG_WS(256, 3, 3, 2);
 #undef FPSG_WS
     return launch_status("fpsg_gemm_split_nn_persistent (specialised waves)");
-  }
-  if (variant >= 2) {       // ablation builds (measurements: tools/bench_gemm_split.py --persistent 2,3,4,5)
-    if (variant == 2) hipLaunchKernelGGL((gemm_split_pnn_kernel<256, false, 1>), dim3((unsigned)grid), dim3(512), 0, s, g);
-    else if (variant == 3) hipLaunchKernelGGL((gemm_split_pnn_kernel<256, false, 2>), dim3((unsigned)grid), dim3(512), 0, s, g);
-    else if (variant == 4) hipLaunchKernelGGL((gemm_split_pnn_kernel<256, false, 3>), dim3((unsigned)grid), dim3(512), 0, s, g);
-    else hipLaunchKernelGGL((gemm_split_pnn_kernel<256, false, 4>), dim3((unsigned)grid), dim3(512), 0, s, g);
-    return launch_status("fpsg_gemm_split_nn_persistent (ablation)");
   }
   if (bn == 256) {
     if (ktail) hipLaunchKernelGGL((gemm_split_pnn_kernel<256, true>), dim3((unsigned)grid), dim3(512), 0, s, g);
@@ -1729,11 +1638,11 @@ extern "C" int fpsg_gemm_split(const float* A, const float* B, float* C, int bat
   using namespace fpsg;
   FPSG_REQUIRE(batch > 0 && M > 0 && N > 0 && K > 0, FPSG_E_SHAPE, "fpsg_gemm_split: batch, M, N, K must be positive");
   FPSG_REQUIRE(lda >= K && ldc >= N && ldb >= (transB ? K : N), FPSG_E_SHAPE, "fpsg_gemm_split: leading dimension below the row length");
+  Plan p;
+  FPSG_REQUIRE(plan_for(batch, M, N, K, transB, variant, &p), FPSG_E_SHAPE, "fpsg_gemm_split: unknown variant %d", variant);
   FPSG_REQUIRE_PTR(A);
   FPSG_REQUIRE_PTR(B);
   FPSG_REQUIRE_PTR(C);
-  Plan p;
-  FPSG_REQUIRE(plan_for(batch, M, N, K, transB, variant, &p), FPSG_E_SHAPE, "fpsg_gemm_split: unknown variant %d", variant);
   const long blocks = (long)batch * p.tiles_m * p.tiles_n * p.splits;
   FPSG_REQUIRE(blocks < (1L << 30), FPSG_E_LIMIT, "fpsg_gemm_split: too many tiles");
   GemmArgs g{};
@@ -1750,53 +1659,27 @@ extern "C" int fpsg_gemm_split(const float* A, const float* B, float* C, int bat
   } else {
     g.C = C; g.ldc = ldc; g.sC = sC; g.s_split = 0;
   }
-  g.stagger_mode = p.stagger_mode; g.stagger_per_cu = kTiles[p.tile].per_cu; g.stagger_ticks = p.stagger_us * 100;
   g.nt_c = 0;     // measured: non-temporal stores of an output beyond the Infinity Cache (128 -> 128 @112: 535 MB) 260 -> 480 us
   FPSG_REQUIRE((long)M * lda < (1L << 29) && (long)(transB ? N : K) * ldb < (1L << 29) && (long)M * ldc < (1L << 29),
                FPSG_E_LIMIT, "fpsg_gemm_split: a matrix of one batch entry must stay below 2 GiB (32-bit buffer offsets)");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)blocks), block(kTiles[p.tile].threads);
-  const bool prio = p.prio;
-#define FPSG_GEMM_LAUNCH_PIPE(BM, BN, BK, WR, WC, MINW)                                                           \
+#define FPSG_GEMM_LAUNCH(BM, BN, BK, WR, WC, MINW, PIPE)                                                          \
   do {                                                                                                            \
-    if (transB) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, BK, WR, WC, MINW, true, true, true>), grid, block, 0, s, g);  \
-    else hipLaunchKernelGGL((gemm_split_kernel<BM, BN, BK, WR, WC, MINW, false, true, true>), grid, block, 0, s, g);        \
+    if (transB) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, BK, WR, WC, MINW, true, PIPE>), grid, block, 0, s, g);  \
+    else hipLaunchKernelGGL((gemm_split_kernel<BM, BN, BK, WR, WC, MINW, false, PIPE>), grid, block, 0, s, g);        \
   } while (0)
-#define FPSG_GEMM_LAUNCH(BM, BN, BK, WR, WC, MINW)                                                                \
-  do {                                                                                                            \
-    if (prio) {                                                                                                    \
-      if (transB) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, BK, WR, WC, MINW, true, true>), grid, block, 0, s, g);  \
-      else hipLaunchKernelGGL((gemm_split_kernel<BM, BN, BK, WR, WC, MINW, false, true>), grid, block, 0, s, g);        \
-    } else {                                                                                                       \
-      if (transB) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, BK, WR, WC, MINW, true, false>), grid, block, 0, s, g); \
-      else hipLaunchKernelGGL((gemm_split_kernel<BM, BN, BK, WR, WC, MINW, false, false>), grid, block, 0, s, g);       \
-    }                                                                                                              \
-  } while (0)
-  if (p.abl > 0) {        // measurement builds (tools/bench_gemm_split.py --variants 2000 ...): wrong results by design
-    FPSG_REQUIRE(!transB && (p.tile == 0 || p.tile == 2) && p.abl <= 3, FPSG_E_SHAPE, "fpsg_gemm_split: no such ablation build");
-#define FPSG_ABL(A)                                                                                                     \
-    do {                                                                                                                \
-      if (p.tile == 0) hipLaunchKernelGGL((gemm_split_kernel<256, 256, 16, 2, 4, 2, false, true, false, A>), grid, block, 0, s, g); \
-      else hipLaunchKernelGGL((gemm_split_kernel<128, 128, 16, 2, 2, 3, false, true, false, A>), grid, block, 0, s, g);             \
-    } while (0)
-    if (p.abl == 1) FPSG_ABL(1);
-    else if (p.abl == 2) FPSG_ABL(2);
-    else FPSG_ABL(3);
-#undef FPSG_ABL
-    return launch_status("fpsg_gemm_split (ablation)");
-  }
   switch (p.tile) {
-    case 0: FPSG_GEMM_LAUNCH(256, 256, 16, 2, 4, 2); break;
-    case 1: FPSG_GEMM_LAUNCH(256, 128, 32, 2, 4, 2); break;
-    case 2: FPSG_GEMM_LAUNCH(128, 128, 16, 2, 2, 3); break;
-    case 3: FPSG_GEMM_LAUNCH(128, 256, 16, 1, 4, 2); break;
-    case 4: FPSG_GEMM_LAUNCH_PIPE(256, 256, 16, 2, 4, 2); break;
-    case 5: FPSG_GEMM_LAUNCH_PIPE(128, 128, 16, 2, 2, 3); break;
-    case 6: FPSG_GEMM_LAUNCH_PIPE(128, 256, 16, 1, 4, 2); break;
-    default: FPSG_GEMM_LAUNCH_PIPE(256, 128, 16, 2, 4, 4); break;
+    case 0: FPSG_GEMM_LAUNCH(256, 256, 16, 2, 4, 2, false); break;
+    case 1: FPSG_GEMM_LAUNCH(256, 128, 32, 2, 4, 2, false); break;
+    case 2: FPSG_GEMM_LAUNCH(128, 128, 16, 2, 2, 3, false); break;
+    case 3: FPSG_GEMM_LAUNCH(128, 256, 16, 1, 4, 2, false); break;
+    case 4: FPSG_GEMM_LAUNCH(256, 256, 16, 2, 4, 2, true); break;
+    case 5: FPSG_GEMM_LAUNCH(128, 128, 16, 2, 2, 3, true); break;
+    case 6: FPSG_GEMM_LAUNCH(128, 256, 16, 1, 4, 2, true); break;
+    default: FPSG_GEMM_LAUNCH(256, 128, 16, 2, 4, 4, true); break;
   }
 #undef FPSG_GEMM_LAUNCH
-#undef FPSG_GEMM_LAUNCH_PIPE
   int rc = launch_status("fpsg_gemm_split");
   if (rc != 0 || p.splits == 1) return rc;
   const long n = (long)batch * M * N;

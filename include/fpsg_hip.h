@@ -608,7 +608,11 @@ int fpsg_wino_filter_grad_transform(int m, const float* dU, int K, int C, float*
  * Row-major, leading dimensions lda / ldb / ldc and batch strides sA / sB / sC in floats.  Every fp32 operand x enters as
  * bf16(x) + bf16(x - x1) + bf16(x - x1 - x2) (an exact split) and the six products of order <= 2^-18 are accumulated in
  * fp32 by v_mfma_f32_32x32x16_bf16: fp32-grade results (error against float64: profiles/r05/), not the library's bits.
- * variant: -1 automatic; else tile + 10 * splits, tile 0 = 256x256x16, 1 = 256x128x32, splits 0 = automatic.
+ * variant: -1 automatic; else tile + 10 * splits (0-999) with splits 0 = automatic, 1-99 = that many ranges of the
+ * reduction (transB = 1), and tile 0 = 256x256x16, 1 = 256x128x32, 2 = 128x128x16, 3 = 128x256x16, 4 / 5 / 6 = tiles
+ * 0 / 2 / 3 with the split placed among the MFMAs (5 is what -1 picks but for long weight-gradient reductions: 0),
+ * 7 = 256x128x16 in the same form.  Every other id (tile 8 or 9, anything >= 1000 or below -1) is refused on the host
+ * with FPSG_E_SHAPE, and fpsg_gemm_split_workspace_floats returns 0 for it.
  * ws: fpsg_gemm_split_workspace_floats(...) floats (0 when the reduction is not split; then ws may be NULL); a split
  * reduction needs a dense output (ldc == N, sC == M*N).  One batch entry of each matrix must stay below 2 GiB. */
 size_t fpsg_gemm_split_workspace_floats(int batch, int M, int N, int K, int transB, int variant);
@@ -621,7 +625,8 @@ int fpsg_gemm_split(const float* A, const float* B, float* C, int batch, int M, 
  * (fpsg_gemm_split_packed_a_bytes bytes, 16-byte aligned; about 1.5x the fp32 matrix); fpsg_gemm_split_nn_packed computes
  * C[b] [M x N] = A[b] . B[b] [K x N] with A brought in by LDS-DMA and only B split on the way into LDS: the same values as
  * fpsg_gemm_split(transB = 0), bit for bit.  variant (the same for the three calls): -1 / 0 = 256 x 128 x 16 tiles, two
- * workgroups per CU; 1 = 256 x 256 x 16; 2 = 128 x 128 x 16. */
+ * workgroups per CU; 1 = 256 x 256 x 16; 2 = 128 x 128 x 16; 3 = the tiled kernel of fpsg_gemm_split (tile 5) with A staged
+ * through registers from the image packed for 2.  Every other id: FPSG_E_SHAPE (0 bytes from fpsg_gemm_split_packed_a_bytes). */
 size_t fpsg_gemm_split_packed_a_bytes(int batch, int M, int K, int variant);
 int fpsg_gemm_split_pack_a(const float* A, int batch, int M, int K, int lda, long sA, int variant, void* Ap,
                            fpsg_stream_t stream);
@@ -635,9 +640,10 @@ int fpsg_gemm_split_nn_packed(const void* Ap, const float* B, float* C, int batc
  * 6 / 12 = the form with specialised waves (4 waves only multiply, 4 only stage: LDS-DMA of both operands, the split of B
  * from LDS), 256 x 128 tiles, 12 with staggered first pieces; 13 / 14 = the same with 128 x 128 tiles and two workgroups
  * per CU (Ap packed with variant 2).  6 and 12-14 move B rows by 16-byte DMA: B, ldb and sB aligned to 4 floats
- * (FPSG_E_SHAPE otherwise).  2-5 and 7-11 are measurement builds (wrong results by design).  Measured: none of the
- * persistent forms beats the tiled kernel (profiles/r05/gemm_split_ablation.txt); they are kept as measured evidence and
- * are not on any product path.  B below 4 GiB in total, one C matrix and the packed A below 2 GiB. */
+ * (FPSG_E_SHAPE otherwise).  Every other id is refused on the host with FPSG_E_SHAPE (2-5 and 7-11 once named
+ * measurement builds that computed wrong results by design: removed).  Measured: none of the persistent forms beats the
+ * tiled kernel (profiles/r05/gemm_split_ablation.txt); they are kept as measured evidence and are not on any product
+ * path.  B below 4 GiB in total, one C matrix and the packed A below 2 GiB. */
 int fpsg_gemm_split_nn_persistent(const void* Ap, const float* B, float* C, int batch, int M, int N, int K, int ldb, int ldc,
                                   long sB, long sC, int variant, fpsg_stream_t stream);
 
@@ -649,8 +655,9 @@ int fpsg_gemm_split_nn_persistent(const void* Ap, const float* B, float* C, int 
  * library's, so results agree to fp32 round-off, not bit for bit).  One persistent launch: a workgroup per CU walks an
  * equal share of the flattened (batch, row tile, column) space; four waves stage both operands by LDS-DMA, four multiply.
  * K, lda, ldb, sA, sB multiples of 4 floats, A and B 16-byte aligned (FPSG_E_ALIGN otherwise: the caller then takes the
- * library GEMM); A and B below 4 GiB each in total, one C matrix below 2 GiB.  variant: -1 / 0 default, 1 = staggered
- * first pieces.  Deterministic. */
+ * library GEMM); A and B below 4 GiB each in total, one C matrix below 2 GiB.  variant: 0 = 256 x 128 tiles, one workgroup per CU;
+ * 2 (and -1) = 128 x 128 tiles, two per CU; 1 / 3 = 0 / 2 with staggered first pieces; every other id: FPSG_E_SHAPE.
+ * Deterministic. */
 int fpsg_gemm_f32_nn(const float* A, const float* B, float* C, int batch, int M, int N, int K, int lda, int ldb, int ldc,
                      long sA, long sB, long sC, int variant, fpsg_stream_t stream);
 

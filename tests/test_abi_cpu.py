@@ -74,6 +74,37 @@ def test_round4_entry_points_check_their_arguments(lib):
     assert lib.fpsg_bn_max_dz_offset(64, 1024, 2048) + 64 * 1024 == lib.fpsg_bn_max_workspace_floats(64, 1024, 2048)
 
 
+def test_gemm_variant_ids_outside_the_documented_lists_are_refused_on_the_host(lib):
+    """K10's entry points take the variant ids include/fpsg_hip.h lists and nothing else: the ids that once selected
+    measurement-only builds (kernels without their loads, stores or split, delayed starts, no wave priorities) get
+    FPSG_E_SHAPE (-2) with the id in the message, before any HIP call and before the pointer checks -- never a launch, never
+    an alias of a kept id.  The kept ids pass the variant check (and then stop at the null pointers: -1)."""
+    def split(variant, transB=0):
+        return lib.fpsg_gemm_split(None, None, None, 1, 256, 256, 4096, 4096, 4096 if transB else 256, 256, 256 * 4096,
+                                   256 * 4096, 256 * 256, transB, variant, None, 0, None)
+
+    def persistent(variant):
+        return lib.fpsg_gemm_split_nn_persistent(None, None, None, 1, 256, 256, 64, 256, 256, 64 * 256, 256 * 256, variant, None)
+
+    for v in (1000, 2000, 4002, 100010, 200052, 8, 9):
+        for transB in (0, 1):
+            assert split(v, transB) == -2, v
+            msg = lib.fpsg_last_error()
+            assert b"fpsg_gemm_split" in msg and b"variant %d" % v in msg, (v, msg)
+            assert lib.fpsg_gemm_split_workspace_floats(1, 256, 256, 4096, transB, v) == 0, v
+    for v in (2, 3, 4, 5, 7, 8, 9, 10, 11, 15):
+        assert persistent(v) == -2, v
+        msg = lib.fpsg_last_error()
+        assert b"fpsg_gemm_split_nn_persistent" in msg and b"variant %d" % v in msg, (v, msg)
+    # kept ids: -1 and one explicit id per entry point get past the variant check
+    for v in (-1, 5, 73):
+        assert split(v, 1) == -1 and b"null pointer" in lib.fpsg_last_error(), v
+    assert lib.fpsg_gemm_split_workspace_floats(1, 256, 256, 4096, 1, -1) > 0      # (the shape does split its reduction)
+    assert lib.fpsg_gemm_split_workspace_floats(1, 256, 256, 4096, 1, 70) == 7 * 256 * 256
+    for v in (-1, 0, 1, 6, 12, 13, 14):
+        assert persistent(v) == -1 and b"null pointer" in lib.fpsg_last_error(), v
+
+
 def test_product_path_has_no_cpu_fallback():
     import torch
     from fpsg_amd._hip import FpsgHipError

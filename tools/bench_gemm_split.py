@@ -39,10 +39,10 @@ def _errors(C, ref64):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variants", default="-1")
-    ap.add_argument("--packed", default="", help="variants of the packed-A forward form to time (v100.. columns)")
-    ap.add_argument("--persistent", default="", help="variants of the persistent forward form to time (v200.. columns)")
-    ap.add_argument("--f32", default="", help="variants of K11 (fpsg_gemm_f32_nn, fp32 MFMA) to time on the forward leg (v300.. columns)")
+    ap.add_argument("--variants", default="-1", help="variants of the tiled form: -1, or tile + 10 * splits (tile 0-7, splits 0-99)")
+    ap.add_argument("--packed", default="", help="variants of the packed-A forward form to time: 0-3 (v100.. columns)")
+    ap.add_argument("--persistent", default="", help="variants of the persistent forward form to time: 0, 1, 6, 12, 13, 14 (v200.. columns)")
+    ap.add_argument("--f32", default="", help="variants of K11 (fpsg_gemm_f32_nn, fp32 MFMA) to time on the forward leg: 0-3 (v300.. columns)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--n-img", type=int, default=37)
