@@ -9,7 +9,9 @@ exact transport distance of K12 divided by n_query like the other two; ``--set_m
 ``; MMD-CD: <v>; COV-CD: <v>; 1-NNA-CD: <v>``, the set-level generation metrics of ``fpsg_amd.set_metrics`` over all
 the class's generated and reference query clouds, from K13's Chamfer matrices; ``--set_metrics_emd``: then
 ``; MMD-EMD: <v>; COV-EMD: <v>; 1-NNA-EMD: <v>``, the same under the exact EMD from K14's matrices, followed by
-``; EMD-uncertified: <cov>/<nna>`` when some nearest-neighbour decisions are not certified by the EMD bounds).  With ``--npy_folder`` the generated and
+``; EMD-uncertified: <cov>/<nna>`` when some nearest-neighbour decisions are not certified by the EMD bounds;
+``--jsd``: last, ``; JSD: <v>``, the Jensen-Shannon divergence between the voxel-occupancy distributions of the class's
+generated and reference query clouds, from K15's grids, accumulated as the items arrive).  With ``--npy_folder`` the generated and
 ground-truth clouds (+ a side-by-side PNG) of every item are dumped instead, which is the
 reference's commented-out "OPTION 2" (``:111``).
 
@@ -54,9 +56,11 @@ def main(opt):
     sets = bool(getattr(opt, "set_metrics", False))
     sets_emd = bool(getattr(opt, "set_metrics_emd", False))
     per_class_gen, per_class_ref = defaultdict(list), defaultdict(list)
+    want_jsd = bool(getattr(opt, "jsd", False))
+    grid_gen, grid_ref = {}, {}                         # per class: the two occupancy grids, accumulated per item
     # the weights do not change while evaluating: transformed filters, stacked decoder weights and BatchNorm coefficients
     # are made once, not per item; on a GPU the item in front of the EMD is replayed as a hipGraph (engine.EvalItem)
-    with EvalItem(model, exact_emd=exact, return_clouds=sets or sets_emd) as run_item:
+    with EvalItem(model, exact_emd=exact, return_clouds=sets or sets_emd or want_jsd) as run_item:
         for item, sample in enumerate(dl_test):
             sample = to_device(sample, device)
             if getattr(opt, "npy_folder", ""):
@@ -72,6 +76,10 @@ def main(opt):
             if sets or sets_emd:                        # kept on the device; one set per class after the loop
                 per_class_gen[name].append(out["syn_pc"])
                 per_class_ref[name].append(out["ref_pc_q"])
+            if want_jsd:                                # two K15 launches per item; no cloud is kept for this
+                from fpsg_amd.metrics import occupancy_grid
+                grid_gen[name] = occupancy_grid(out["syn_pc"].contiguous(), out=grid_gen.get(name))
+                grid_ref[name] = occupancy_grid(out["ref_pc_q"].contiguous(), out=grid_ref.get(name))
     per_class_set = {}
     if sets:
         from fpsg_amd.set_metrics import generation_metrics
@@ -83,6 +91,11 @@ def main(opt):
         for name in sorted(per_class_gen):
             per_class_set_emd[name] = emd_generation_metrics(torch.cat(per_class_gen[name]),
                                                              torch.cat(per_class_ref[name]))
+    per_class_jsd = {}
+    if want_jsd:
+        from fpsg_amd.set_metrics import jsd_from_grids
+        for name in sorted(grid_gen):
+            per_class_jsd[name] = jsd_from_grids(grid_gen[name], grid_ref[name])
     for name in sorted(per_class_cd):
         line = (f"Class: {name} -- Rec CD: {statistics.mean(per_class_cd[name])}; "
                 f"Rec EMD: {statistics.mean(per_class_emd[name])}")
@@ -96,9 +109,11 @@ def main(opt):
             line += f"; MMD-EMD: {m['mmd_emd']}; COV-EMD: {m['cov_emd']}; 1-NNA-EMD: {m['nna_emd']}"
             if m["cov_uncertified"] or m["nna_uncertified"]:
                 line += f"; EMD-uncertified: {m['cov_uncertified']}/{m['nna_uncertified']}"
+        if want_jsd:
+            line += f"; JSD: {per_class_jsd[name]['jsd']}"
         print(line)
     return (per_class_cd, per_class_emd) + ((per_class_exact,) if exact else ()) + ((per_class_set,) if sets else ()) + \
-        ((per_class_set_emd,) if sets_emd else ())
+        ((per_class_set_emd,) if sets_emd else ()) + ((per_class_jsd,) if want_jsd else ())
 
 
 if __name__ == "__main__":

@@ -13,7 +13,8 @@ Additions (all optional): ``--synthetic`` (file-free corpora of the reference's 
 ``--resident`` (keep the corpora in HBM, assemble episodes on the device), ``--exact_emd`` (evaluation: the exact
 EMD per class beside the two reference metrics), ``--set_metrics`` (evaluation: MMD, COV and 1-NNA under the Chamfer
 distance per class, over the class's generated and reference query clouds), ``--set_metrics_emd`` (the same under the
-exact EMD).
+exact EMD), ``--jsd`` (evaluation: the Jensen-Shannon divergence between the voxel-occupancy distributions of the class's
+generated and reference query clouds).
 """
 from __future__ import annotations
 
@@ -90,6 +91,9 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
         g.add_argument("--set_metrics_emd", action="store_true",
                        help="Also report MMD-EMD, COV-EMD and 1-NNA-EMD per class over all its generated and reference "
                             "query clouds (HIP exact EMD matrix, fpsg_amd.set_metrics);")
+        g.add_argument("--jsd", action="store_true",
+                       help="Also report the Jensen-Shannon divergence per class between the voxel-occupancy distributions "
+                            "of its generated and reference query clouds (HIP occupancy grid, fpsg_amd.set_metrics.jsd);")
     return p
 
 

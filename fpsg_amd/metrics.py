@@ -451,6 +451,71 @@ def emd_matrix(A: torch.Tensor, B: torch.Tensor | None = None, eps: float | None
     return cost
 
 
+OCCUPANCY_MAX_RES = 64          # FPSG_OCCUPANCY_MAX_RES (include/fpsg_hip.h)
+
+
+def occupancy_grid(clouds: torch.Tensor, resolution: int = 28, half_extent: float = 1.0, in_sphere: bool = True,
+                   out: dict | None = None, return_cells: bool = False) -> dict:
+    """Voxel-occupancy grid of the clouds ``[S,N,3]`` (K15, HIP; the definition is in ``include/fpsg_hip.h``): a dict
+    with ``"counts"`` (points per cell) and ``"clouds_hit"`` (clouds with at least one point in the cell), int32
+    ``[r,r,r]`` on the clouds' device, ``"outside"`` int32 ``[3]`` (finite points with a coordinate beyond the half
+    extent, finite points beyond the sphere of that radius, non-finite points -- the last have no cell),
+    ``"n_clouds"`` and ``"n_points"`` (Python ints) and the parameters.  ``resolution`` 2..64 (3.. with ``in_sphere``:
+    only the nodes inside the sphere inscribed in the grid are cells, a point that rounds to another node goes to the
+    nearest retained one).  ``half_extent``: 1.0 for clouds in the unit ball, 0.5 for the unit cube.
+
+    ``out``: a dict returned by an earlier call with the same parameters: this call's clouds are accumulated into it
+    (running totals; ``ValueError`` on a parameter mismatch) and it is returned.  ``return_cells=True`` adds
+    ``"cells"``, int32 ``[S,N]``, the linear cell index ``(i r + j) r + k`` of every point of this call (-1: none).
+
+    Integers formed with integer atomics: bitwise the same on every run and whatever the split into calls.  Forward
+    only; no CPU path (CPU tensors raise ``FpsgHipError``); ``ValueError`` for bad shapes or parameters."""
+    if not isinstance(clouds, torch.Tensor) or clouds.dim() != 3 or clouds.size(2) != 3:
+        raise ValueError(f"expected [S,N,3] clouds, got {tuple(getattr(clouds, 'shape', ()))}")
+    if clouds.size(0) < 1 or clouds.size(1) < 1:
+        raise ValueError(f"empty sets or clouds are not supported (got {tuple(clouds.shape)})")
+    r = int(resolution)
+    if r != resolution or r < 2 or r > OCCUPANCY_MAX_RES:
+        raise ValueError(f"resolution must be an integer from 2 to {OCCUPANCY_MAX_RES}, got {resolution}")
+    in_sphere = bool(in_sphere)
+    if in_sphere and r < 3:
+        raise ValueError("in_sphere retains no node at resolution 2; use at least 3")
+    E = float(half_extent)
+    if not (E > 0.0 and math.isfinite(E)):
+        raise ValueError(f"half_extent must be positive and finite, got {half_extent}")
+    params = {"resolution": r, "half_extent": E, "in_sphere": in_sphere}
+    if out is not None:
+        for k, v in params.items():
+            if out.get(k) != v:
+                raise ValueError(f"out= was made with {k}={out.get(k)!r}, this call has {k}={v!r}")
+        if out["counts"].device != clouds.device:
+            raise ValueError(f"device mismatch: out= on {out['counts'].device}, clouds on {clouds.device}")
+    clouds = clouds.detach()
+    _hip.dev_tensor(clouds, torch.float32, "clouds")
+    S, N, _ = clouds.shape
+    dev = clouds.device
+    if out is None:
+        out = dict(params, counts=torch.zeros((r, r, r), dtype=torch.int32, device=dev),
+                   clouds_hit=torch.zeros((r, r, r), dtype=torch.int32, device=dev),
+                   outside=torch.zeros((3,), dtype=torch.int32, device=dev), n_clouds=0, n_points=0)
+    cells = torch.empty((S, N), dtype=torch.int32, device=dev) if return_cells else None
+    lib = _hip.load()
+    ws_bytes = lib.fpsg_occupancy_grid_workspace_bytes(S, N, r)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if ws_bytes else None
+    with torch.cuda.device(dev), _probe("occupancy_grid", S, N, r):
+        rc = lib.fpsg_occupancy_grid(_hip.ptr(clouds), S, N, r, E, int(in_sphere), _hip.ptr(out["counts"]),
+                                     _hip.ptr(out["clouds_hit"]), _hip.ptr(out["outside"]),
+                                     None if cells is None else _hip.ptr(cells), None if ws is None else _hip.ptr(ws),
+                                     ws_bytes, _hip.stream_of(clouds))
+    _hip.check(rc, "fpsg_occupancy_grid")
+    out["n_clouds"] += S
+    out["n_points"] += S * N
+    out.pop("cells", None)
+    if return_cells:
+        out["cells"] = cells
+    return out
+
+
 def softmin(x: torch.Tensor, y: torch.Tensor, h: torch.Tensor, eps: float) -> torch.Tensor:
     """``out[b,i] = -eps * logsumexp_j(h[b,j] - |x_i - y_j|^2 / (2 eps))`` (K2b), no grad."""
     _check_clouds(x, y)

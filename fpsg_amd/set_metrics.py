@@ -15,6 +15,12 @@ The same three metrics under the exact EMD (``emd_generation_metrics``, K14 ``me
 ``from_matrices`` applied to the EMD matrices divided by N (the mean matched distance).  Each EMD entry comes with a
 certificate ``cost - gap <= EMD <= cost``; ``certify_nearest`` says which nearest-neighbour decisions behind COV and
 1-NNA the bounds settle.
+
+The seventh column of the usual table, the Jensen-Shannon divergence between the voxel-occupancy distributions of the
+two sets (``jsd``, K15 ``metrics.occupancy_grid``; ``evaluate_Network.py --jsd``), looks at where in space the sets put
+their points rather than at cloud-to-cloud distances: ``jsd_from_counts`` and ``occupancy_entropy_from_counts`` work on
+histograms already computed (pure torch float64, any device).  The published implementations are not pinned; the
+definition in DESIGN.md (K15) is the specification.
 """
 from __future__ import annotations
 
@@ -133,3 +139,82 @@ def emd_generation_metrics(gen: torch.Tensor, ref: torch.Tensor, eps: float | No
     c_gg, i_gg = emd_matrix(gen, eps=eps, max_rounds=max_rounds, return_info=True)
     c_rr, i_rr = emd_matrix(ref, eps=eps, max_rounds=max_rounds, return_info=True)
     return emd_from_matrices(c_gr, i_gr["gap"], c_gg, i_gg["gap"], c_rr, i_rr["gap"], gen.size(1))
+
+
+def retained_nodes(resolution: int, in_sphere: bool = True) -> torch.Tensor:
+    """bool ``[r,r,r]``: the grid nodes that are cells of the occupancy grid.  With ``in_sphere``, node ``(i,j,k)`` is
+    retained iff ``(2i-(r-1))^2 + (2j-(r-1))^2 + (2k-(r-1))^2 <= (r-1)^2`` (integers: nodes exactly on the sphere
+    inscribed in the grid are kept); without, every node."""
+    r = int(resolution)
+    if r < 2 or (in_sphere and r < 3):
+        raise ValueError(f"resolution must be at least {3 if in_sphere else 2}, got {resolution}")
+    if not in_sphere:
+        return torch.ones((r, r, r), dtype=torch.bool)
+    a = (2 * torch.arange(r, dtype=torch.int64) - (r - 1)) ** 2
+    return a[:, None, None] + a[None, :, None] + a[None, None, :] <= (r - 1) ** 2
+
+
+def _entropy_bits(p: torch.Tensor) -> torch.Tensor:
+    p = p[p > 0]                                                   # 0 log 0 = 0
+    return -(p * torch.log2(p)).sum()
+
+
+def jsd_from_counts(counts_g: torch.Tensor, counts_r: torch.Tensor) -> float:
+    """Jensen-Shannon divergence in bits between the distributions ``P = counts_g / sum`` and ``Q = counts_r / sum``:
+    ``H((P + Q) / 2) - (H(P) + H(Q)) / 2`` in float64.  In [0, 1]; symmetric; 0.0 exactly for proportional histograms
+    whose quotients round alike (equal ones always); 1 for disjoint supports.  ``ValueError`` for mismatched shapes
+    or an all-zero histogram."""
+    if tuple(counts_g.shape) != tuple(counts_r.shape):
+        raise ValueError(f"histograms of different shapes: {tuple(counts_g.shape)} and {tuple(counts_r.shape)}")
+    g, r = counts_g.reshape(-1).double(), counts_r.reshape(-1).double()
+    sg, sr = g.sum(), r.sum()
+    if not (float(sg) > 0 and float(sr) > 0):
+        raise ValueError("a histogram without any point has no distribution")
+    P, Q = g / sg, r / sr
+    M = (P + Q) / 2
+    v = float(_entropy_bits(M) - (_entropy_bits(P) + _entropy_bits(Q)) / 2)      # P = Q: M = P, the same three sums
+    return min(max(v, 0.0), 1.0)                                   # rounding may leave the interval by an ulp or two
+
+
+def occupancy_entropy_from_counts(clouds_hit: torch.Tensor, n_clouds: int, retained: torch.Tensor) -> float:
+    """Mean over the retained nodes of the binary entropy in bits of ``clouds_hit / n_clouds``, the share of the set's
+    clouds with a point in the node (float64)."""
+    if tuple(clouds_hit.shape) != tuple(retained.shape):
+        raise ValueError(f"clouds_hit {tuple(clouds_hit.shape)} and retained {tuple(retained.shape)} differ in shape")
+    if int(n_clouds) < 1:
+        raise ValueError(f"n_clouds must be positive, got {n_clouds}")
+    keep = retained.to(clouds_hit.device)
+    n = int(keep.sum())
+    if n < 1:
+        raise ValueError("no retained node")
+    p = clouds_hit[keep].double() / float(n_clouds)
+    q = 1.0 - p
+    h = -(torch.where(p > 0, p * torch.log2(p.clamp_min(1e-300)), torch.zeros_like(p))
+          + torch.where(q > 0, q * torch.log2(q.clamp_min(1e-300)), torch.zeros_like(q)))
+    return float(h.sum() / n)
+
+
+def jsd(gen: torch.Tensor, ref: torch.Tensor, resolution: int = 28, half_extent: float = 1.0,
+        in_sphere: bool = True) -> dict:
+    """The Jensen-Shannon divergence between the occupancy distributions of generated clouds ``gen [G,N,3]`` and
+    reference clouds ``ref [R,M,3]`` (fp32 on the GPU): two K15 launches (``metrics.occupancy_grid``), then
+    ``jsd_from_counts``.  ``{"jsd", "entropy_gen", "entropy_ref"}`` as Python floats (the entropies:
+    ``occupancy_entropy_from_counts`` of each set) and ``"outside_gen"``, ``"outside_ref"``, lists of three ints (the
+    grids' ``outside``).  ``half_extent`` 1.0 suits clouds in the unit ball, 0.5 the unit cube."""
+    from .metrics import occupancy_grid
+    g = occupancy_grid(gen, resolution, half_extent, in_sphere)
+    r = occupancy_grid(ref, resolution, half_extent, in_sphere)
+    return jsd_from_grids(g, r)
+
+
+def jsd_from_grids(g: dict, r: dict) -> dict:
+    """``jsd``'s result from two grids of ``metrics.occupancy_grid`` made with the same parameters (e.g. accumulated
+    with ``out=`` while the clouds arrive)."""
+    for k in ("resolution", "half_extent", "in_sphere"):
+        if g[k] != r[k]:
+            raise ValueError(f"the two grids differ in {k}: {g[k]!r} and {r[k]!r}")
+    keep = retained_nodes(g["resolution"], g["in_sphere"])
+    return {"jsd": jsd_from_counts(g["counts"], r["counts"]),
+            "entropy_gen": occupancy_entropy_from_counts(g["clouds_hit"], g["n_clouds"], keep),
+            "entropy_ref": occupancy_entropy_from_counts(r["clouds_hit"], r["n_clouds"], keep),
+            "outside_gen": g["outside"].tolist(), "outside_ref": r["outside"].tolist()}

@@ -277,6 +277,35 @@ int fpsg_emd_cross(const float* xyz1, const float* xyz2, int Na, int Nb, int N, 
                    float* cost, float* gap, int* status, int* rounds, void* ws, size_t ws_bytes,
                    fpsg_stream_t stream);
 
+/* ---- K15: voxel-occupancy grid of a set of clouds (for the Jensen-Shannon divergence) ----------
+ * The seventh column of the generation-metrics table (Achlioptas et al. 2018): the JSD between the occupancy
+ * distributions of a generated and a reference set.  The published packages are not pinned; the definition
+ * below is the specification.
+ * xyz [S,N,3] fp32.  Grid of res^3 nodes (i,j,k) at -E + 2 E i / (res-1) per axis, E = half_extent, linear index
+ * (i res + j) res + k.  in_sphere != 0: a node is retained iff (2i-(res-1))^2 + (2j-(res-1))^2 + (2k-(res-1))^2 <=
+ * (res-1)^2 (integers); otherwise every node is retained.
+ * Per point p, per axis, fp32 without fused multiply-add: t = fl(fl(p s) + c), s = fl((res-1) / (2E)),
+ * c = fl((res-1) / 2) (formed in double, rounded once); n0 = clamp(rint(t), 0, res-1), round half to even.  The
+ * point's cell is n0 if retained, else the retained node minimising d = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)),
+ * dx = fl(t_x - i), ..., ties to the lowest linear index.  A point with a NaN or infinite coordinate has no
+ * cell (-1).
+ * Outputs, all int32 and all ACCUMULATED INTO (the caller zeroes them once per set and may call again with more
+ * clouds of the same set): counts [res^3] += points per cell; clouds_hit [res^3] += clouds of this call with at
+ * least one point in the cell; outside [3] += {finite points with some |p| > E, finite points with
+ * fl(fl(fl(x x) + fl(y y)) + fl(z z)) > fl(E E), non-finite points}.  cells [S,N] (may be NULL) = the cell of every
+ * point, overwritten.  Integer atomics only: the results do not depend on launch order, slicing or accumulation.
+ * No workspace: fpsg_occupancy_grid_workspace_bytes returns 0 and ws may be NULL.
+ * Errors, all before any launch: FPSG_E_SHAPE for S or N < 1, res < 2, res = 2 with in_sphere, or a half_extent
+ * that is not positive and finite (or so small that s overflows); FPSG_E_LIMIT for res >
+ * FPSG_OCCUPANCY_MAX_RES; FPSG_E_NULL for a null xyz, counts, clouds_hit or outside; FPSG_E_ALIGN for a misaligned
+ * pointer.
+ */
+#define FPSG_OCCUPANCY_MAX_RES 64
+size_t fpsg_occupancy_grid_workspace_bytes(int S, int N, int res);
+int fpsg_occupancy_grid(const float* xyz, int S, int N, int res, float half_extent, int in_sphere, int32_t* counts,
+                        int32_t* clouds_hit, int32_t* outside, int32_t* cells, void* ws, size_t ws_bytes,
+                        fpsg_stream_t stream);
+
 /* ---- K4b: fused EdgeConv (gather + BatchNorm statistics + max over k) -----------------
  * Replaces the chain get_graph_feature -> Conv2d 1x1 -> BatchNorm2d -> LeakyReLU -> max_k of
  * src/dgcnn/model.py:23-42,53-56,63-76 without materialising [B,2C,N,k].  The caller first
