@@ -10,6 +10,8 @@ exact transport distance of K12 divided by n_query like the other two; ``--set_m
 the class's generated and reference query clouds, from K13's Chamfer matrices; ``--set_metrics_emd``: then
 ``; MMD-EMD: <v>; COV-EMD: <v>; 1-NNA-EMD: <v>``, the same under the exact EMD from K14's matrices, followed by
 ``; EMD-uncertified: <cov>/<nna>`` when some nearest-neighbour decisions are not certified by the EMD bounds;
+``--set_metrics_points N``: the clouds of those two are first reduced to ``N`` points each by farthest point sampling from
+index 0 (K16) and their six labels read ``MMD-CD@N``, ..., ``1-NNA-EMD@N``; every other column stays on the full clouds;
 ``--jsd``: last, ``; JSD: <v>``, the Jensen-Shannon divergence between the voxel-occupancy distributions of the class's
 generated and reference query clouds, from K15's grids, accumulated as the items arrive).  With ``--npy_folder`` the generated and
 ground-truth clouds (+ a side-by-side PNG) of every item are dumped instead, which is the
@@ -56,6 +58,8 @@ def main(opt):
     sets = bool(getattr(opt, "set_metrics", False))
     sets_emd = bool(getattr(opt, "set_metrics_emd", False))
     per_class_gen, per_class_ref = defaultdict(list), defaultdict(list)
+    set_points = getattr(opt, "set_metrics_points", None)
+    at = "" if set_points is None else f"@{set_points}"   # the labels of reduced set metrics say so
     want_jsd = bool(getattr(opt, "jsd", False))
     grid_gen, grid_ref = {}, {}                         # per class: the two occupancy grids, accumulated per item
     # the weights do not change while evaluating: transformed filters, stacked decoder weights and BatchNorm coefficients
@@ -74,8 +78,17 @@ def main(opt):
             if exact:
                 per_class_exact[name].append(out["exact_emd"].item() / n_query)
             if sets or sets_emd:                        # kept on the device; one set per class after the loop
-                per_class_gen[name].append(out["syn_pc"])
-                per_class_ref[name].append(out["ref_pc_q"])
+                gen, ref = out["syn_pc"], out["ref_pc_q"]
+                if set_points is not None:              # K16, two launches per item: only the reduced clouds are kept
+                    from fpsg_amd.sampling import farthest_point_subsample
+                    for which, c in (("generated", gen), ("reference", ref)):
+                        if set_points > c.size(1):
+                            raise ValueError(f"--set_metrics_points {set_points} exceeds the {c.size(1)} points of the "
+                                             f"{which} clouds")
+                    gen = farthest_point_subsample(gen.contiguous(), set_points, start=0)
+                    ref = farthest_point_subsample(ref.contiguous(), set_points, start=0)
+                per_class_gen[name].append(gen)
+                per_class_ref[name].append(ref)
             if want_jsd:                                # two K15 launches per item; no cloud is kept for this
                 from fpsg_amd.metrics import occupancy_grid
                 grid_gen[name] = occupancy_grid(out["syn_pc"].contiguous(), out=grid_gen.get(name))
@@ -103,10 +116,10 @@ def main(opt):
             line += f"; Exact EMD: {statistics.mean(per_class_exact[name])}"
         if sets:
             m = per_class_set[name]
-            line += f"; MMD-CD: {m['mmd_cd']}; COV-CD: {m['cov_cd']}; 1-NNA-CD: {m['nna_cd']}"
+            line += f"; MMD-CD{at}: {m['mmd_cd']}; COV-CD{at}: {m['cov_cd']}; 1-NNA-CD{at}: {m['nna_cd']}"
         if sets_emd:
             m = per_class_set_emd[name]
-            line += f"; MMD-EMD: {m['mmd_emd']}; COV-EMD: {m['cov_emd']}; 1-NNA-EMD: {m['nna_emd']}"
+            line += f"; MMD-EMD{at}: {m['mmd_emd']}; COV-EMD{at}: {m['cov_emd']}; 1-NNA-EMD{at}: {m['nna_emd']}"
             if m["cov_uncertified"] or m["nna_uncertified"]:
                 line += f"; EMD-uncertified: {m['cov_uncertified']}/{m['nna_uncertified']}"
         if want_jsd:

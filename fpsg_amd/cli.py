@@ -13,7 +13,8 @@ Additions (all optional): ``--synthetic`` (file-free corpora of the reference's 
 ``--resident`` (keep the corpora in HBM, assemble episodes on the device), ``--exact_emd`` (evaluation: the exact
 EMD per class beside the two reference metrics), ``--set_metrics`` (evaluation: MMD, COV and 1-NNA under the Chamfer
 distance per class, over the class's generated and reference query clouds), ``--set_metrics_emd`` (the same under the
-exact EMD), ``--jsd`` (evaluation: the Jensen-Shannon divergence between the voxel-occupancy distributions of the class's
+exact EMD), ``--set_metrics_points N`` (evaluation: the clouds of the two set metrics reduced to N points each by farthest
+point sampling, K16, and the labels marked ``@N``), ``--jsd`` (evaluation: the Jensen-Shannon divergence between the voxel-occupancy distributions of the class's
 generated and reference query clouds).
 """
 from __future__ import annotations
@@ -91,6 +92,10 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
         g.add_argument("--set_metrics_emd", action="store_true",
                        help="Also report MMD-EMD, COV-EMD and 1-NNA-EMD per class over all its generated and reference "
                             "query clouds (HIP exact EMD matrix, fpsg_amd.set_metrics);")
+        g.add_argument("--set_metrics_points", type=int, default=None, metavar="N",
+                       help="With --set_metrics / --set_metrics_emd: reduce every generated and reference query cloud to N "
+                            "points by farthest point sampling from index 0 (HIP, fpsg_amd.sampling) before the set metrics; "
+                            "the labels become MMD-CD@N, ...; every other column stays on the full clouds;")
         g.add_argument("--jsd", action="store_true",
                        help="Also report the Jensen-Shannon divergence per class between the voxel-occupancy distributions "
                             "of its generated and reference query clouds (HIP occupancy grid, fpsg_amd.set_metrics.jsd);")
@@ -102,6 +107,12 @@ def validate(opt) -> None:
         raise SystemExit("--config_path and --test_path are required unless --synthetic is given")
     if opt.n_way != 1:
         raise SystemExit("only 1-way episodes are defined by the model (as in the reference)")
+    points = getattr(opt, "set_metrics_points", None)
+    if points is not None:
+        if not (getattr(opt, "set_metrics", False) or getattr(opt, "set_metrics_emd", False)):
+            raise SystemExit("--set_metrics_points needs --set_metrics and / or --set_metrics_emd")
+        if points < 1:
+            raise SystemExit(f"--set_metrics_points must be at least 1 (got {points})")
 
 
 def build_datasets(opt, n_query: int, device):

@@ -306,6 +306,31 @@ int fpsg_occupancy_grid(const float* xyz, int S, int N, int res, float half_exte
                         int32_t* clouds_hit, int32_t* outside, int32_t* cells, void* ws, size_t ws_bytes,
                         fpsg_stream_t stream);
 
+/* ---- K16: farthest point sampling --------------------------------------------------------------
+ * Picks n of a cloud's N points so that every next pick is the point farthest from those already picked.  The
+ * definition below is the specification.
+ * xyz [B,N,3] fp32; start [B] int32 or NULL (index 0 for every cloud); idx [B,n] int32; min_dist [B,n] fp32 or NULL.
+ * Per cloud, with d(i,j) = fma(dz,dz, fma(dy,dy, dx dx)) on the fp32 coordinate differences (the squared distance
+ * of K1 and K13, same bits):
+ *   idx[0] = start[b];  min_dist[0] = +inf;  D_i = d(i, idx[0]) for every i;
+ *   for t = 1 .. n-1:  idx[t] = the LOWEST i at which D_i is largest;  min_dist[t] = D_idx[t] (before the update);
+ *                      D_i = min(D_i, d(i, idx[t])) for every i.
+ * A picked point has D = 0 and is picked again only when every point has D = 0 (the cloud has fewer than n
+ * distinct points): then the lowest index repeats.  That is defined behaviour, not an error.
+ * Inputs are expected finite.  With a non-finite coordinate the indices are unspecified but in [0, N), and the
+ * kernel ends after its n rounds like any other call: the loop count never depends on the data.  A start[b] outside
+ * [0, N) is clamped into the range by the kernel (the host cannot see it).
+ * Results are bitwise the same on every run, independent of B and of a cloud's position in the batch, and
+ * idx[:, :m] of a call with n equals the call with m.  No atomics, no communication between workgroups.
+ * No workspace: fpsg_fps_workspace_bytes returns 0 and ws may be NULL.
+ * Errors, all before any launch: FPSG_E_SHAPE for B or N < 1 or n outside 1..N; FPSG_E_LIMIT for N >
+ * FPSG_FPS_MAX_N; FPSG_E_NULL for a null xyz or idx; FPSG_E_ALIGN for a misaligned pointer.
+ */
+#define FPSG_FPS_MAX_N 16384
+size_t fpsg_fps_workspace_bytes(int B, int N, int n);
+int fpsg_fps(const float* xyz, int B, int N, int n, const int32_t* start, int32_t* idx, float* min_dist, void* ws,
+             size_t ws_bytes, fpsg_stream_t stream);
+
 /* ---- K4b: fused EdgeConv (gather + BatchNorm statistics + max over k) -----------------
  * Replaces the chain get_graph_feature -> Conv2d 1x1 -> BatchNorm2d -> LeakyReLU -> max_k of
  * src/dgcnn/model.py:23-42,53-56,63-76 without materialising [B,2C,N,k].  The caller first
