@@ -23,8 +23,7 @@
 // 64-channel, 37x224x224 tensor still fills the chip (the per-channel workgroup of the library
 // kernel cannot).  Deterministic: fixed partial layout, no atomics.
 #include <algorithm>
-#include <atomic>
-#include <cstdlib>
+#include <initializer_list>
 
 #include "fpsg_common.h"
 
@@ -70,34 +69,13 @@ __device__ __forceinline__ void block_reduce2(float& a, float& b, float* red /*[
   }
 }
 
-// FOLD (round 5; opt-in by FPSG_BN_FINALIZE_FOLD=1): the forward finalize runs in the LAST-ARRIVING workgroup of
-// each channel instead of in a launch of its own.  The partial sums leave the CU as agent-scope (sc1) stores, the wave
-// drains them (vmcnt 0) and takes a ticket from the channel's counter; the workgroup that draws ticket S - 1 reads all S
-// partials back with agent-scope loads (per-XCD L2s are not coherent: plain loads could be stale), sums them in the
-// finalize kernel's own order -- so the result does not depend on which workgroup came last -- and puts the counter
-// back to zero.  Counters live in the library (zero at load, every use leaves them zero), kBnFoldBanks banks handed out
-// round robin so that calls in flight on different streams do not share one.
-constexpr int kBnFoldBanks = 16, kBnFoldChannels = 4096;
-__device__ unsigned g_bn_fold_counters[kBnFoldBanks * kBnFoldChannels];
-struct BnFoldArgs {
-  const float* gamma; const float* beta;
-  double count; float eps, momentum;
-  float* chan; float* batch_mean; float* batch_var_unbiased; float* run_mean; float* run_var;
-  unsigned* counters;
-};
-__device__ __forceinline__ void wave_sum2(double& a, double& b);
-__device__ __forceinline__ void bn_fwd_finalize_channel(double s0, double s1, int c, int C, const float* gamma, const float* beta,
-                                                        double count, float eps, float* chan, float* batch_mean,
-                                                        float* batch_var_unbiased, float* run_mean, float* run_var, float momentum);
-
 // Work items of channel c: (n, seg) pairs, seg over ceil(L / kBnSeg) segments of a row.
 // Block (s, c) takes items s, s + S, ...
 // MODE 0: sums of x and x^2.   MODE 1: sums of dz and dz*xhat (dz = dy * act'(x*scale+shift)).
-template <int MODE, int ACT, bool NT = false, bool FOLD = false>
+template <int MODE, int ACT, bool NT = false>
 __global__ __launch_bounds__(kBnThreads) void bn_reduce_kernel(
     const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ chan /*[4][C]: scale, shift, mean, rstd*/,
-    const float* __restrict__ pb, int N, int C, int L, int S, float slope, float* __restrict__ part /*[C][S][2]*/,
-    const BnFoldArgs f = BnFoldArgs{}) {
+    const float* __restrict__ pb, int N, int C, int L, int S, float slope, float* __restrict__ part /*[C][S][2]*/) {
   __shared__ float red[8];
   const int c = blockIdx.y, s = blockIdx.x;
   const float b = pb ? pb[c] : 0.0f;
@@ -160,56 +138,15 @@ __global__ __launch_bounds__(kBnThreads) void bn_reduce_kernel(
     }
   }
   block_reduce2(a0, a1, red);
-  if constexpr (FOLD) {
-    __shared__ int last;
-    if (threadIdx.x == 0) {
-      __hip_atomic_store(&part[((size_t)c * S + s) * 2 + 0], a0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&part[((size_t)c * S + s) * 2 + 1], a1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned t = __hip_atomic_fetch_add(&f.counters[c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last = t == (unsigned)S - 1u;
-    }
-    __syncthreads();
-    if (!last || threadIdx.x >= 64) return;
-    const int lane = threadIdx.x;
-    double s0 = 0.0, s1 = 0.0;
-    for (int sl = lane; sl < S; sl += 64) {
-      s0 += __hip_atomic_load(&part[((size_t)c * S + sl) * 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s1 += __hip_atomic_load(&part[((size_t)c * S + sl) * 2 + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    wave_sum2(s0, s1);
-    if (lane != 0) return;
-    bn_fwd_finalize_channel(s0, s1, c, C, f.gamma, f.beta, f.count, f.eps, f.chan, f.batch_mean, f.batch_var_unbiased,
-                            f.run_mean, f.run_var, f.momentum);
-    __hip_atomic_store(&f.counters[c], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return;
-  }
   if (threadIdx.x == 0) {
     part[((size_t)c * S + s) * 2 + 0] = a0;
     part[((size_t)c * S + s) * 2 + 1] = a1;
   }
 }
 
-// forward finalize: mean / biased var -> chan = (scale, shift, mean, rstd); optional outputs of
-// the batch mean and UNBIASED variance (what running statistics are updated with).
-// One wave per channel: lane s sums slices s, s + 64, ... of the channel's partial sums in fp64 (K5's own passes
-// use S <= 64; a convolution's epilogue delivers one slice per workgroup), then a fixed shuffle tree.
 __device__ __forceinline__ void wave_sum2(double& a, double& b) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) { a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); }
-}
-
-__global__ __launch_bounds__(64) void bn_fwd_finalize_kernel(const float* __restrict__ part, const float* __restrict__ gamma,
-                                       const float* __restrict__ beta, int C, int S, double count, float eps,
-                                       float* __restrict__ chan, float* __restrict__ batch_mean,
-                                       float* __restrict__ batch_var_unbiased, float* __restrict__ run_mean,
-                                       float* __restrict__ run_var, float momentum) {
-  const int c = blockIdx.x, lane = threadIdx.x;
-  double s0 = 0.0, s1 = 0.0;
-  for (int sl = lane; sl < S; sl += 64) { s0 += part[((size_t)c * S + sl) * 2]; s1 += part[((size_t)c * S + sl) * 2 + 1]; }
-  wave_sum2(s0, s1);
-  if (lane != 0) return;
-  bn_fwd_finalize_channel(s0, s1, c, C, gamma, beta, count, eps, chan, batch_mean, batch_var_unbiased, run_mean, run_var, momentum);
 }
 
 __device__ __forceinline__ void bn_fwd_finalize_channel(double s0, double s1, int c, int C, const float* gamma, const float* beta,
@@ -232,6 +169,23 @@ __device__ __forceinline__ void bn_fwd_finalize_channel(double s0, double s1, in
     run_mean[c] = fma_rn(momentum, (float)mean, (1.0f - momentum) * run_mean[c]);
     run_var[c] = fma_rn(momentum, unbiased, (1.0f - momentum) * run_var[c]);
   }
+}
+
+// forward finalize: mean / biased var -> chan = (scale, shift, mean, rstd); optional outputs of
+// the batch mean and UNBIASED variance (what running statistics are updated with).
+// One wave per channel: lane s sums slices s, s + 64, ... of the channel's partial sums in fp64 (K5's own passes
+// use S <= 64; a convolution's epilogue delivers one slice per workgroup), then a fixed shuffle tree.
+__global__ __launch_bounds__(64) void bn_fwd_finalize_kernel(const float* __restrict__ part, const float* __restrict__ gamma,
+                                       const float* __restrict__ beta, int C, int S, double count, float eps,
+                                       float* __restrict__ chan, float* __restrict__ batch_mean,
+                                       float* __restrict__ batch_var_unbiased, float* __restrict__ run_mean,
+                                       float* __restrict__ run_var, float momentum) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  double s0 = 0.0, s1 = 0.0;
+  for (int sl = lane; sl < S; sl += 64) { s0 += part[((size_t)c * S + sl) * 2]; s1 += part[((size_t)c * S + sl) * 2 + 1]; }
+  wave_sum2(s0, s1);
+  if (lane != 0) return;
+  bn_fwd_finalize_channel(s0, s1, c, C, gamma, beta, count, eps, chan, batch_mean, batch_var_unbiased, run_mean, run_var, momentum);
 }
 
 // eval mode: chan from running statistics
@@ -1106,77 +1060,158 @@ int check_dims(const char* fn, int N, int C, int L, int act) {
   return 0;
 }
 
-}  // namespace
-}  // namespace fpsg
-
-extern "C" size_t fpsg_bn_workspace_floats(int N, int C, int L) {
-  if (N <= 0 || C <= 0 || L <= 0) return 0;
-  const size_t segs = ((size_t)L + fpsg::kBnSeg - 1) / fpsg::kBnSeg;
-  return (size_t)C * fpsg::kBnSlices * 2 + (size_t)N * C * segs;     // channel partials + sum(dx) partials
+// FPSG_REQUIRE_PTR for the helpers below: the message names the entry point and its argument, not the helper.
+int require_ptr(const char* fn, const void* p, const char* name) {
+  FPSG_REQUIRE(p != nullptr, FPSG_E_NULL, "%s: null pointer '%s'", fn, name);
+  FPSG_REQUIRE(!misaligned4(p), FPSG_E_ALIGN, "%s: '%s' not 4-byte aligned", fn, name);
+  return 0;
 }
 
-extern "C" int fpsg_bn_act_fwd(const float* x, const float* pre_bias, const float* gamma, const float* beta,
-                               float* running_mean, float* running_var, float momentum, int N, int C, int L,
-                               int training, float eps, int act, float slope, float* y, float* chan,
-                               float* batch_mean, float* batch_var_unbiased, float* ws, fpsg_stream_t stream) {
-  using namespace fpsg;
-  int rc = check_dims("fpsg_bn_act_fwd", N, C, L, act);
-  if (rc) return rc;
-  FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(y); FPSG_REQUIRE_PTR(chan);
-  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0, FPSG_E_ALIGN,
-               "fpsg_bn_act_fwd: x and y must be 16-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // training == 2: evaluation mode with `chan` already holding the channel coefficients (the caller computed them once
-  // for a block of calls during which the running statistics do not change: fpsg_bn_stats(training = 0))
-  const bool chan_given = training == 2;
-  if (chan_given) training = 0;
-  if (!training && !chan_given) { FPSG_REQUIRE_PTR(running_mean); FPSG_REQUIRE_PTR(running_var); }
-  if ((long)N * L <= kBnSmallMax) {
-    if (!training && !chan_given) {
-      hipLaunchKernelGGL(bn_eval_chan_kernel, dim3((C + 255) / 256), dim3(256), 0, s, running_mean, running_var,
-                         gamma, beta, C, eps, chan);
-      if ((rc = launch_status("fpsg_bn_act_fwd(eval)"))) return rc;
-    }
-    launch_small<0>(act, x, nullptr, gamma, beta, pre_bias, N, C, L, training, eps, slope, y, chan, batch_mean,
-                    batch_var_unbiased, nullptr, nullptr, nullptr, running_mean, running_var, momentum, s);
-    return launch_status("fpsg_bn_act_fwd(small)");
+bool aligned16(std::initializer_list<const void*> ptrs) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+  return (bits & 15) == 0;
+}
+
+// launch_status for stage `stage` of entry point `fn`
+int stage_status(const char* fn, const char* stage) {
+  char what[96];
+  snprintf(what, sizeof what, "%s(%s)", fn, stage);
+  return launch_status(what);
+}
+
+// training == 2: evaluation mode with `chan` already holding the channel coefficients (the caller computed them once for
+// a block of calls during which the running statistics do not change: fpsg_bn_stats(training = 0)).  Returns whether
+// that is so, and makes `training` the plain evaluation mode the kernels know.
+bool take_chan_given(int& training) {
+  if (training != 2) return false;
+  training = 0;
+  return true;
+}
+
+// ---- the workspace of a call --------------------------------------------------------------------
+// In floats from the start of `ws`; the size functions of the C ABI and every entry point read their numbers here, so
+// what the one sizes is what the other slices.
+//   [0, rows)       channel partial sums [C][kBnSlices][2]
+//   [rows, dz)      per-(row, item) words [N*C][items of a row]: plain and pooled forms, one sum(dx) partial each; max
+//                   form, four each (a RowExt in the forward; the backward's sum(dx) partials reuse the block)
+//   [dz, floats)    max form only: dz [N*C]
+struct BnWorkspace { size_t rows, dz, floats; };
+
+BnWorkspace workspace(int N, int C, size_t row_words, bool with_dz) {
+  BnWorkspace w;
+  w.rows = (size_t)C * kBnSlices * 2;
+  w.dz = w.rows + (size_t)N * C * row_words;
+  w.floats = w.dz + (with_dz ? (size_t)N * C : 0);
+  return w;
+}
+size_t row_segs(int L) { return ((size_t)L + kBnSeg - 1) / kBnSeg; }
+int pool_items_per_plane(int H, int W) {
+  const int RP = pool_rows_per_item(W);
+  return (H / 2 + RP - 1) / RP;
+}
+BnWorkspace plain_workspace(int N, int C, int L) { return workspace(N, C, row_segs(L), false); }
+BnWorkspace pool_workspace(int N, int C, int H, int W) { return workspace(N, C, pool_items_per_plane(H, W), false); }
+BnWorkspace max_workspace(int N, int C, int L) { return workspace(N, C, row_segs(L) * 4, true); }
+
+// ---- channel coefficients of a forward ------------------------------------------------------------
+// Leaves chan [4][C] ready for the apply kernel of entry point `fn`:
+//   training, own statistics : the form's pass over x, then bn_fwd_finalize_kernel (ws needed)
+//   training, parts given    : bn_fwd_finalize_kernel on the caller's [C][n_parts][2] sums
+//   evaluation               : bn_eval_chan_kernel on the running statistics (both needed)
+//   chan_given               : nothing (take_chan_given)
+// All argument checks come before the first launch.
+enum BnStatsPass {
+  kStatsSliced,     // launch_reduce<0>: sums of slices_for(N, L) slices per channel
+  kStatsRowExt      // bn_reduce_ext_kernel: the max form's pass, which also leaves each row's extremes in the workspace
+                    // and therefore runs in every mode (evaluation: extremes only)
+};
+
+int channel_coefficients(const char* fn, BnStatsPass pass, const float* x, const float* pre_bias, const float* gamma,
+                         const float* beta, float* running_mean, float* running_var, float momentum, int N, int C, int L,
+                         int training, bool chan_given, float eps, float* chan, float* batch_mean,
+                         float* batch_var_unbiased, float* ws, const float* parts, int n_parts, hipStream_t s) {
+  int rc;
+  if (training) {
+    if (parts) FPSG_REQUIRE(n_parts > 0, FPSG_E_SHAPE, "%s: n_parts must be positive with parts (got %d)", fn, n_parts);
+    else if ((rc = require_ptr(fn, ws, "ws"))) return rc;
+  } else if (!chan_given) {
+    if ((rc = require_ptr(fn, running_mean, "running_mean")) || (rc = require_ptr(fn, running_var, "running_var"))) return rc;
+  }
+  int S = n_parts;
+  if (pass == kStatsRowExt) {
+    // one item per WAVE and pass: S workgroups of 4 waves per channel
+    const int items_max = N * (int)row_segs(L);
+    S = items_max >= 4 * kBnSlices ? kBnSlices : (items_max + 3) / 4;
+    RowExt* ext = reinterpret_cast<RowExt*>(ws + max_workspace(N, C, L).rows);
+    dim3 grid(C, S);
+    if (!training) hipLaunchKernelGGL(bn_reduce_ext_kernel<0>, grid, dim3(kBnThreads), 0, s, x, pre_bias, N, C, L, S, ws, ext);
+    else if (beyond_cache((size_t)N * C * L * sizeof(float))) hipLaunchKernelGGL((bn_reduce_ext_kernel<1, true>), grid, dim3(kBnThreads), 0, s, x, pre_bias, N, C, L, S, ws, ext);
+    else hipLaunchKernelGGL(bn_reduce_ext_kernel<1>, grid, dim3(kBnThreads), 0, s, x, pre_bias, N, C, L, S, ws, ext);
+    if ((rc = stage_status(fn, training ? "stats" : "extremes"))) return rc;
+  } else if (training && !parts) {
+    S = slices_for(N, L);
+    launch_reduce<0>(kActNone, x, nullptr, nullptr, pre_bias, N, C, L, S, 0.0f, ws, s);
+    if ((rc = stage_status(fn, "stats"))) return rc;
   }
   if (training) {
-    FPSG_REQUIRE_PTR(ws);
-    const int S = slices_for(N, L);
-    const char* fold = getenv("FPSG_BN_FINALIZE_FOLD");
-    if (fold && fold[0] == '1' && C <= kBnFoldChannels) {      // opt-in: the finalize in the last-arriving workgroup
-      static std::atomic<unsigned> next_bank{0};
-      unsigned* counters = nullptr;
-      FPSG_REQUIRE(hipGetSymbolAddress(reinterpret_cast<void**>(&counters), HIP_SYMBOL(g_bn_fold_counters)) == hipSuccess &&
-                       counters, FPSG_E_LIMIT, "fpsg_bn_act_fwd: the fold counters are not addressable");
-      BnFoldArgs f{gamma, beta, (double)N * (double)L, eps, momentum, chan, batch_mean, batch_var_unbiased, running_mean,
-                   running_var, counters + (size_t)(next_bank.fetch_add(1) % kBnFoldBanks) * kBnFoldChannels};
-      const dim3 grid(S, C);
-      if (beyond_cache((size_t)N * C * L * sizeof(float)))
-        hipLaunchKernelGGL((bn_reduce_kernel<0, kActNone, true, true>), grid, dim3(kBnThreads), 0, s, x, nullptr, nullptr, pre_bias, N, C, L, S, 0.0f, ws, f);
-      else
-        hipLaunchKernelGGL((bn_reduce_kernel<0, kActNone, false, true>), grid, dim3(kBnThreads), 0, s, x, nullptr, nullptr, pre_bias, N, C, L, S, 0.0f, ws, f);
-      if ((rc = launch_status("fpsg_bn_act_fwd(stats + finalize)"))) return rc;
-    } else {
-      launch_reduce<0>(kActNone, x, nullptr, nullptr, pre_bias, N, C, L, S, 0.0f, ws, s);
-      if ((rc = launch_status("fpsg_bn_act_fwd(stats)"))) return rc;
-      hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(C), dim3(64), 0, s, ws, gamma, beta, C, S,
-                         (double)N * (double)L, eps, chan, batch_mean, batch_var_unbiased, running_mean, running_var,
-                         momentum);
-      if ((rc = launch_status("fpsg_bn_act_fwd(finalize)"))) return rc;
-    }
-  } else if (!chan_given) {
+    hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(C), dim3(64), 0, s, parts ? parts : ws, gamma, beta, C, S,
+                       (double)N * (double)L, eps, chan, batch_mean, batch_var_unbiased, running_mean, running_var,
+                       momentum);
+    return stage_status(fn, "finalize");
+  }
+  if (!chan_given) {
     hipLaunchKernelGGL(bn_eval_chan_kernel, dim3((C + 255) / 256), dim3(256), 0, s, running_mean, running_var,
                        gamma, beta, C, eps, chan);
-    if ((rc = launch_status("fpsg_bn_act_fwd(eval)"))) return rc;
+    return stage_status(fn, "eval");
   }
-  launch_apply<0>(act, x, nullptr, chan, nullptr, pre_bias, N, C, L, slope, y, nullptr, s);
-  return launch_status("fpsg_bn_act_fwd(apply)");
+  return 0;
 }
 
-namespace fpsg {
-namespace {
+// ---- the backward after its sums ----------------------------------------------------------------
+// dgamma, dbeta and coef [3][C] from the [C][S][2] sums of dz and dz*xhat
+int backward_finalize(const char* fn, const float* sums, int S, const float* chan, int C, double count, int training,
+                      float* dgamma, float* dbeta, float* coef, hipStream_t s) {
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, s, sums, chan, C, S, count, training, dgamma, dbeta, coef);
+  return stage_status(fn, "finalize");
+}
+
+// apply(dxpart) launches the form's dx kernel; with dpre_bias it gets the workspace's per-(row, item) block for its
+// sum(dx) partials (row_items per row), which bn_dxsum_kernel then adds up per channel.
+template <class Apply>
+int apply_and_dxsum(const char* fn, Apply apply, int N, int C, int row_items, float* dpre_bias, float* ws,
+                    const BnWorkspace& w, hipStream_t s) {
+  int rc;
+  float* dxpart = dpre_bias ? ws + w.rows : nullptr;
+  apply(dxpart);
+  if ((rc = stage_status(fn, "apply"))) return rc;
+  if (dpre_bias) {
+    hipLaunchKernelGGL(bn_dxsum_kernel, dim3(C), dim3(64), 0, s, dxpart, N, C, row_items, dpre_bias);
+    return stage_status(fn, "dpre_bias");
+  }
+  return 0;
+}
+
+// The backward tail: bn_bwd_finalize_kernel, the form's apply, bn_dxsum_kernel when dpre_bias is wanted.
+template <class Apply>
+int backward_tail(const char* fn, const float* sums, int S, const float* chan, int N, int C, double count, int training,
+                  float* dgamma, float* dbeta, float* coef, Apply apply, int row_items, float* dpre_bias, float* ws,
+                  const BnWorkspace& w, hipStream_t s) {
+  int rc = backward_finalize(fn, sums, S, chan, C, count, training, dgamma, dbeta, coef, s);
+  if (rc) return rc;
+  return apply_and_dxsum(fn, apply, N, C, row_items, dpre_bias, ws, w, s);
+}
+
+// The max form's sums and coefficients in one kernel (N values per channel): dz [N*C], dgamma, dbeta, coef.
+void launch_max_bwd_coef(int act, const float* x, const float* pb, const float* gout, const int32_t* idx,
+                         const float* chan, int N, int C, int L, int training, float slope, float* dz, float* dgamma,
+                         float* dbeta, float* coef, hipStream_t s) {
+#define FPSG_MAXB(A) hipLaunchKernelGGL(bn_max_bwd_coef_kernel<A>, dim3(C), dim3(64), 0, s, x, pb, gout, idx, chan, \
+                                        N, C, L, training, slope, dz, dgamma, dbeta, coef)
+  if (act == kActRelu) FPSG_MAXB(kActRelu); else if (act == kActLeaky) FPSG_MAXB(kActLeaky); else FPSG_MAXB(kActNone);
+#undef FPSG_MAXB
+}
+
 int rows_segments(const char* fn, int ld, const int* seg_off, const int* seg_len, int nseg, int C, int act, bool backward,
                   BnSegs& g) {
   FPSG_REQUIRE(C > 0 && C <= 65535 * 64 && ld > 0, FPSG_E_SHAPE, "%s: C, ld must be positive (got %d, %d)", fn, C, ld);
@@ -1198,8 +1233,41 @@ int rows_segments(const char* fn, int ld, const int* seg_off, const int* seg_len
   }
   return 0;
 }
+
 }  // namespace
 }  // namespace fpsg
+
+extern "C" size_t fpsg_bn_workspace_floats(int N, int C, int L) {
+  if (N <= 0 || C <= 0 || L <= 0) return 0;
+  return fpsg::plain_workspace(N, C, L).floats;
+}
+
+extern "C" int fpsg_bn_act_fwd(const float* x, const float* pre_bias, const float* gamma, const float* beta,
+                               float* running_mean, float* running_var, float momentum, int N, int C, int L,
+                               int training, float eps, int act, float slope, float* y, float* chan,
+                               float* batch_mean, float* batch_var_unbiased, float* ws, fpsg_stream_t stream) {
+  using namespace fpsg;
+  const char* fn = "fpsg_bn_act_fwd";
+  int rc = check_dims(fn, N, C, L, act);
+  if (rc) return rc;
+  FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(y); FPSG_REQUIRE_PTR(chan);
+  FPSG_REQUIRE(aligned16({x, y}), FPSG_E_ALIGN, "%s: x and y must be 16-byte aligned", fn);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool chan_given = take_chan_given(training);
+  // a small tensor's training statistics are the small kernel's own: only evaluation needs coefficients in front of it
+  const bool small = (long)N * L <= kBnSmallMax;
+  if (!(small && training) &&
+      (rc = channel_coefficients(fn, kStatsSliced, x, pre_bias, gamma, beta, running_mean, running_var, momentum, N, C, L,
+                                 training, chan_given, eps, chan, batch_mean, batch_var_unbiased, ws, nullptr, 0, s)))
+    return rc;
+  if (small) {
+    launch_small<0>(act, x, nullptr, gamma, beta, pre_bias, N, C, L, training, eps, slope, y, chan, batch_mean,
+                    batch_var_unbiased, nullptr, nullptr, nullptr, running_mean, running_var, momentum, s);
+    return stage_status(fn, "small");
+  }
+  launch_apply<0>(act, x, nullptr, chan, nullptr, pre_bias, N, C, L, slope, y, nullptr, s);
+  return stage_status(fn, "apply");
+}
 
 extern "C" int fpsg_bn_act_rows_fwd(const float* x, int ld, const int* seg_off, const int* seg_len, int nseg,
                                     const float* pre_bias, const float* gamma, const float* beta, int C, float eps,
@@ -1210,8 +1278,7 @@ extern "C" int fpsg_bn_act_rows_fwd(const float* x, int ld, const int* seg_off, 
   int rc = rows_segments("fpsg_bn_act_rows_fwd", ld, seg_off, seg_len, nseg, C, act, false, g);
   if (rc) return rc;
   FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(y); FPSG_REQUIRE_PTR(chan);
-  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0, FPSG_E_ALIGN,
-               "fpsg_bn_act_rows_fwd: x and y must be 16-byte aligned");
+  FPSG_REQUIRE(aligned16({x, y}), FPSG_E_ALIGN, "fpsg_bn_act_rows_fwd: x and y must be 16-byte aligned");
   g.stat_stride = 2 * C;
   launch_small_segs<0>(act, x, nullptr, gamma, beta, pre_bias, 1, C, g, nseg, 1, eps, slope, y, chan, stats,
                        stats ? stats + C : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, -1.0f,
@@ -1229,8 +1296,7 @@ extern "C" int fpsg_bn_act_rows_bwd(const float* x, int ld, const int* seg_off, 
   if (rc) return rc;
   FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(dy); FPSG_REQUIRE_PTR(chan); FPSG_REQUIRE_PTR(dx);
   FPSG_REQUIRE_PTR(dgamma); FPSG_REQUIRE_PTR(dbeta);
-  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0,
-               FPSG_E_ALIGN, "fpsg_bn_act_rows_bwd: x, dy and dx must be 16-byte aligned");
+  FPSG_REQUIRE(aligned16({x, dy, dx}), FPSG_E_ALIGN, "fpsg_bn_act_rows_bwd: x, dy and dx must be 16-byte aligned");
   launch_small_segs<1>(act, x, dy, nullptr, nullptr, pre_bias, 1, C, g, nseg, 1, 0.0f, slope, dx,
                        const_cast<float*>(chan), nullptr, nullptr, dgamma, dbeta, dpre_bias, nullptr, nullptr, -1.0f,
                        static_cast<hipStream_t>(stream));
@@ -1242,62 +1308,38 @@ extern "C" int fpsg_bn_stats(const float* x, const float* pre_bias, const float*
                              int training, float eps, float* chan, float* batch_mean, float* batch_var_unbiased,
                              float* ws, const float* parts, int n_parts, fpsg_stream_t stream) {
   using namespace fpsg;
-  int rc = check_dims("fpsg_bn_stats", N, C, L, kActNone);
+  const char* fn = "fpsg_bn_stats";
+  int rc = check_dims(fn, N, C, L, kActNone);
   if (rc) return rc;
   FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(chan);
-  FPSG_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0, FPSG_E_ALIGN, "fpsg_bn_stats: x must be 16-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (training) {
-    int S = n_parts;
-    if (parts) {
-      FPSG_REQUIRE(n_parts > 0, FPSG_E_SHAPE, "fpsg_bn_stats: n_parts must be positive with parts (got %d)", n_parts);
-    } else {
-      FPSG_REQUIRE_PTR(ws);
-      S = slices_for(N, L);
-      launch_reduce<0>(kActNone, x, nullptr, nullptr, pre_bias, N, C, L, S, 0.0f, ws, s);
-      if ((rc = launch_status("fpsg_bn_stats(stats)"))) return rc;
-    }
-    hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(C), dim3(64), 0, s, parts ? parts : ws, gamma, beta, C, S,
-                       (double)N * (double)L, eps, chan, batch_mean, batch_var_unbiased, running_mean, running_var,
-                       momentum);
-    return launch_status("fpsg_bn_stats(finalize)");
-  }
-  FPSG_REQUIRE_PTR(running_mean); FPSG_REQUIRE_PTR(running_var);
-  hipLaunchKernelGGL(bn_eval_chan_kernel, dim3((C + 255) / 256), dim3(256), 0, s, running_mean, running_var,
-                     gamma, beta, C, eps, chan);
-  return launch_status("fpsg_bn_stats(eval)");
+  FPSG_REQUIRE(aligned16({x}), FPSG_E_ALIGN, "%s: x must be 16-byte aligned", fn);
+  return channel_coefficients(fn, kStatsSliced, x, pre_bias, gamma, beta, running_mean, running_var, momentum, N, C, L,
+                              training, false, eps, chan, batch_mean, batch_var_unbiased, ws, parts, n_parts,
+                              static_cast<hipStream_t>(stream));
 }
 
 extern "C" int fpsg_bn_act_bwd(const float* x, const float* pre_bias, const float* dy, const float* chan, int N,
                                int C, int L, int training, int act, float slope, float* dx, float* dgamma,
                                float* dbeta, float* dpre_bias, float* coef, float* ws, fpsg_stream_t stream) {
   using namespace fpsg;
-  int rc = check_dims("fpsg_bn_act_bwd", N, C, L, act);
+  const char* fn = "fpsg_bn_act_bwd";
+  int rc = check_dims(fn, N, C, L, act);
   if (rc) return rc;
   FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(dy); FPSG_REQUIRE_PTR(chan); FPSG_REQUIRE_PTR(dx);
   FPSG_REQUIRE_PTR(dgamma); FPSG_REQUIRE_PTR(dbeta); FPSG_REQUIRE_PTR(coef); FPSG_REQUIRE_PTR(ws);
-  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0,
-               FPSG_E_ALIGN, "fpsg_bn_act_bwd: x, dy and dx must be 16-byte aligned");
+  FPSG_REQUIRE(aligned16({x, dy, dx}), FPSG_E_ALIGN, "%s: x, dy and dx must be 16-byte aligned", fn);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((long)N * L <= kBnSmallMax) {
     launch_small<1>(act, x, dy, nullptr, nullptr, pre_bias, N, C, L, training, 0.0f, slope, dx,
                     const_cast<float*>(chan), nullptr, nullptr, dgamma, dbeta, dpre_bias, nullptr, nullptr, -1.0f, s);
-    return launch_status("fpsg_bn_act_bwd(small)");
+    return stage_status(fn, "small");
   }
   const int S = slices_for(N, L);
   launch_reduce<1>(act, x, dy, chan, pre_bias, N, C, L, S, slope, ws, s);
-  if ((rc = launch_status("fpsg_bn_act_bwd(reduce)"))) return rc;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, s, ws, chan, C, S,
-                     (double)N * (double)L, training, dgamma, dbeta, coef);
-  if ((rc = launch_status("fpsg_bn_act_bwd(finalize)"))) return rc;
-  float* dxpart = dpre_bias ? ws + (size_t)C * kBnSlices * 2 : nullptr;
-  launch_apply<1>(act, x, dy, chan, coef, pre_bias, N, C, L, slope, dx, dxpart, s);
-  if ((rc = launch_status("fpsg_bn_act_bwd(apply)"))) return rc;
-  if (dpre_bias) {
-    hipLaunchKernelGGL(bn_dxsum_kernel, dim3(C), dim3(64), 0, s, dxpart, N, C, (L + kBnSeg - 1) / kBnSeg, dpre_bias);
-    return launch_status("fpsg_bn_act_bwd(dpre_bias)");
-  }
-  return 0;
+  if ((rc = stage_status(fn, "reduce"))) return rc;
+  return backward_tail(fn, ws, S, chan, N, C, (double)N * (double)L, training, dgamma, dbeta, coef,
+                       [&](float* dxpart) { launch_apply<1>(act, x, dy, chan, coef, pre_bias, N, C, L, slope, dx, dxpart, s); },
+                       (int)row_segs(L), dpre_bias, ws, plain_workspace(N, C, L), s);
 }
 
 // The sums + coefficient half of fpsg_bn_act_bwd alone (no dx pass): dgamma, dbeta and coef [3,C] of
@@ -1307,21 +1349,19 @@ extern "C" int fpsg_bn_act_bwd_coef(const float* x, const float* pre_bias, const
                                     int C, int L, int training, int act, float slope, float* dgamma, float* dbeta,
                                     float* coef, float* ws, fpsg_stream_t stream) {
   using namespace fpsg;
-  int rc = check_dims("fpsg_bn_act_bwd_coef", N, C, L, act);
+  const char* fn = "fpsg_bn_act_bwd_coef";
+  int rc = check_dims(fn, N, C, L, act);
   if (rc) return rc;
   FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(dy); FPSG_REQUIRE_PTR(chan);
   FPSG_REQUIRE_PTR(dgamma); FPSG_REQUIRE_PTR(dbeta); FPSG_REQUIRE_PTR(coef); FPSG_REQUIRE_PTR(ws);
-  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0, FPSG_E_ALIGN,
-               "fpsg_bn_act_bwd_coef: x and dy must be 16-byte aligned");
-  FPSG_REQUIRE((long)N * L > kBnSmallMax, FPSG_E_LIMIT, "fpsg_bn_act_bwd_coef: N*L = %ld is a small tensor (<= %d): use fpsg_bn_act_bwd",
+  FPSG_REQUIRE(aligned16({x, dy}), FPSG_E_ALIGN, "%s: x and dy must be 16-byte aligned", fn);
+  FPSG_REQUIRE((long)N * L > kBnSmallMax, FPSG_E_LIMIT, "%s: N*L = %ld is a small tensor (<= %d): use fpsg_bn_act_bwd", fn,
                (long)N * L, kBnSmallMax);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int S = slices_for(N, L);
   launch_reduce<1>(act, x, dy, chan, pre_bias, N, C, L, S, slope, ws, s);
-  if ((rc = launch_status("fpsg_bn_act_bwd_coef(reduce)"))) return rc;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, s, ws, chan, C, S,
-                     (double)N * (double)L, training, dgamma, dbeta, coef);
-  return launch_status("fpsg_bn_act_bwd_coef(finalize)");
+  if ((rc = stage_status(fn, "reduce"))) return rc;
+  return backward_finalize(fn, ws, S, chan, C, (double)N * (double)L, training, dgamma, dbeta, coef, s);
 }
 
 extern "C" int fpsg_bn_act_bwd_parts(const float* x, const float* pre_bias, const float* dy, const float* chan, int N,
@@ -1329,33 +1369,23 @@ extern "C" int fpsg_bn_act_bwd_parts(const float* x, const float* pre_bias, cons
                                      float* dbeta, float* dpre_bias, float* coef, float* ws, const float* parts,
                                      int n_parts, fpsg_stream_t stream) {
   using namespace fpsg;
-  int rc = check_dims("fpsg_bn_act_bwd_parts", N, C, L, act);
+  const char* fn = "fpsg_bn_act_bwd_parts";
+  int rc = check_dims(fn, N, C, L, act);
   if (rc) return rc;
   FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(dy); FPSG_REQUIRE_PTR(chan); FPSG_REQUIRE_PTR(dx); FPSG_REQUIRE_PTR(parts);
   FPSG_REQUIRE_PTR(dgamma); FPSG_REQUIRE_PTR(dbeta); FPSG_REQUIRE_PTR(coef);
-  FPSG_REQUIRE(n_parts > 0, FPSG_E_SHAPE, "fpsg_bn_act_bwd_parts: n_parts must be positive (got %d)", n_parts);
-  FPSG_REQUIRE(dpre_bias == nullptr || ws != nullptr, FPSG_E_NULL, "fpsg_bn_act_bwd_parts: dpre_bias needs the workspace");
-  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0,
-               FPSG_E_ALIGN, "fpsg_bn_act_bwd_parts: x, dy and dx must be 16-byte aligned");
+  FPSG_REQUIRE(n_parts > 0, FPSG_E_SHAPE, "%s: n_parts must be positive (got %d)", fn, n_parts);
+  FPSG_REQUIRE(dpre_bias == nullptr || ws != nullptr, FPSG_E_NULL, "%s: dpre_bias needs the workspace", fn);
+  FPSG_REQUIRE(aligned16({x, dy, dx}), FPSG_E_ALIGN, "%s: x, dy and dx must be 16-byte aligned", fn);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, s, parts, chan, C, n_parts,
-                     (double)N * (double)L, training, dgamma, dbeta, coef);
-  if ((rc = launch_status("fpsg_bn_act_bwd_parts(finalize)"))) return rc;
-  float* dxpart = dpre_bias ? ws + (size_t)C * kBnSlices * 2 : nullptr;
-  launch_apply<1>(act, x, dy, chan, coef, pre_bias, N, C, L, slope, dx, dxpart, s);
-  if ((rc = launch_status("fpsg_bn_act_bwd_parts(apply)"))) return rc;
-  if (dpre_bias) {
-    hipLaunchKernelGGL(bn_dxsum_kernel, dim3(C), dim3(64), 0, s, dxpart, N, C, (L + kBnSeg - 1) / kBnSeg, dpre_bias);
-    return launch_status("fpsg_bn_act_bwd_parts(dpre_bias)");
-  }
-  return 0;
+  return backward_tail(fn, parts, n_parts, chan, N, C, (double)N * (double)L, training, dgamma, dbeta, coef,
+                       [&](float* dxpart) { launch_apply<1>(act, x, dy, chan, coef, pre_bias, N, C, L, slope, dx, dxpart, s); },
+                       (int)row_segs(L), dpre_bias, ws, plain_workspace(N, C, L), s);
 }
 
 extern "C" size_t fpsg_bn_pool_workspace_floats(int N, int C, int H, int W) {
   if (N <= 0 || C <= 0 || H <= 1 || W <= 1) return 0;
-  const int RP = fpsg::pool_rows_per_item(W);
-  const size_t items = (size_t)(H / 2 + RP - 1) / RP;
-  return (size_t)C * fpsg::kBnSlices * 2 + (size_t)N * C * items;
+  return fpsg::pool_workspace(N, C, H, W).floats;
 }
 
 extern "C" int fpsg_bn_act_pool_fwd(const float* x, const float* pre_bias, const float* gamma, const float* beta,
@@ -1364,37 +1394,19 @@ extern "C" int fpsg_bn_act_pool_fwd(const float* x, const float* pre_bias, const
                                     float* batch_mean, float* batch_var_unbiased, float* ws, const float* parts,
                                     int n_parts, fpsg_stream_t stream) {
   using namespace fpsg;
-  int rc = check_pool_dims("fpsg_bn_act_pool_fwd", N, C, H, W, act);
+  const char* fn = "fpsg_bn_act_pool_fwd";
+  int rc = check_pool_dims(fn, N, C, H, W, act);
   if (rc) return rc;
   FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(y_pooled); FPSG_REQUIRE_PTR(chan);
-  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y_pooled)) & 15) == 0, FPSG_E_ALIGN,
-               "fpsg_bn_act_pool_fwd: x and y_pooled must be 16-byte aligned");
+  FPSG_REQUIRE(aligned16({x, y_pooled}), FPSG_E_ALIGN, "%s: x and y_pooled must be 16-byte aligned", fn);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = H * W;
-  const bool chan_given = training == 2;        // as in fpsg_bn_act_fwd
-  if (chan_given) training = 0;
-  if (training) {
-    int S = n_parts;
-    if (parts) {
-      FPSG_REQUIRE(n_parts > 0, FPSG_E_SHAPE, "fpsg_bn_act_pool_fwd: n_parts must be positive with parts (got %d)", n_parts);
-    } else {
-      FPSG_REQUIRE_PTR(ws);
-      S = slices_for(N, L);
-      launch_reduce<0>(kActNone, x, nullptr, nullptr, pre_bias, N, C, L, S, 0.0f, ws, s);
-      if ((rc = launch_status("fpsg_bn_act_pool_fwd(stats)"))) return rc;
-    }
-    hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(C), dim3(64), 0, s, parts ? parts : ws, gamma, beta, C, S,
-                       (double)N * (double)L, eps, chan, batch_mean, batch_var_unbiased, running_mean, running_var,
-                       momentum);
-    if ((rc = launch_status("fpsg_bn_act_pool_fwd(finalize)"))) return rc;
-  } else if (!chan_given) {
-    FPSG_REQUIRE_PTR(running_mean); FPSG_REQUIRE_PTR(running_var);
-    hipLaunchKernelGGL(bn_eval_chan_kernel, dim3((C + 255) / 256), dim3(256), 0, s, running_mean, running_var,
-                       gamma, beta, C, eps, chan);
-    if ((rc = launch_status("fpsg_bn_act_pool_fwd(eval)"))) return rc;
-  }
+  const bool chan_given = take_chan_given(training);
+  if ((rc = channel_coefficients(fn, kStatsSliced, x, pre_bias, gamma, beta, running_mean, running_var, momentum, N, C,
+                                 H * W, training, chan_given, eps, chan, batch_mean, batch_var_unbiased, ws, parts,
+                                 n_parts, s)))
+    return rc;
   launch_pool_apply<0>(act, x, nullptr, chan, nullptr, pre_bias, N, C, H, W, slope, y_pooled, nullptr, s);
-  return launch_status("fpsg_bn_act_pool_fwd(apply)");
+  return stage_status(fn, "apply");
 }
 
 extern "C" int fpsg_bn_act_pool_bwd(const float* x, const float* pre_bias, const float* dy_pooled, const float* chan,
@@ -1402,43 +1414,31 @@ extern "C" int fpsg_bn_act_pool_bwd(const float* x, const float* pre_bias, const
                                     float* dgamma, float* dbeta, float* dpre_bias, float* coef, float* ws,
                                     fpsg_stream_t stream) {
   using namespace fpsg;
-  int rc = check_pool_dims("fpsg_bn_act_pool_bwd", N, C, H, W, act);
+  const char* fn = "fpsg_bn_act_pool_bwd";
+  int rc = check_pool_dims(fn, N, C, H, W, act);
   if (rc) return rc;
   FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(dy_pooled); FPSG_REQUIRE_PTR(chan); FPSG_REQUIRE_PTR(dx);
   FPSG_REQUIRE_PTR(dgamma); FPSG_REQUIRE_PTR(dbeta); FPSG_REQUIRE_PTR(coef); FPSG_REQUIRE_PTR(ws);
-  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy_pooled) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0,
-               FPSG_E_ALIGN, "fpsg_bn_act_pool_bwd: x, dy_pooled and dx must be 16-byte aligned");
+  FPSG_REQUIRE(aligned16({x, dy_pooled, dx}), FPSG_E_ALIGN, "%s: x, dy_pooled and dx must be 16-byte aligned", fn);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int RP = pool_rows_per_item(W);
-  const int per_plane = (H / 2 + RP - 1) / RP;
+  const int per_plane = pool_items_per_plane(H, W);
   const long items = (long)N * per_plane;
   const int S = items < kBnSlices ? (int)items : kBnSlices;
   launch_pool_reduce(act, x, dy_pooled, chan, pre_bias, N, C, H, W, S, slope, ws, s);
-  if ((rc = launch_status("fpsg_bn_act_pool_bwd(reduce)"))) return rc;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, s, ws, chan, C, S,
-                     (double)N * (double)H * (double)W, training, dgamma, dbeta, coef);
-  if ((rc = launch_status("fpsg_bn_act_pool_bwd(finalize)"))) return rc;
-  float* dxpart = dpre_bias ? ws + (size_t)C * kBnSlices * 2 : nullptr;
-  launch_pool_apply<2>(act, x, dy_pooled, chan, coef, pre_bias, N, C, H, W, slope, dx, dxpart, s);
-  if ((rc = launch_status("fpsg_bn_act_pool_bwd(apply)"))) return rc;
-  if (dpre_bias) {
-    hipLaunchKernelGGL(bn_dxsum_kernel, dim3(C), dim3(64), 0, s, dxpart, N, C, per_plane, dpre_bias);
-    return launch_status("fpsg_bn_act_pool_bwd(dpre_bias)");
-  }
-  return 0;
+  if ((rc = stage_status(fn, "reduce"))) return rc;
+  return backward_tail(fn, ws, S, chan, N, C, (double)N * (double)H * (double)W, training, dgamma, dbeta, coef,
+                       [&](float* dxpart) { launch_pool_apply<2>(act, x, dy_pooled, chan, coef, pre_bias, N, C, H, W, slope, dx, dxpart, s); },
+                       per_plane, dpre_bias, ws, pool_workspace(N, C, H, W), s);
 }
 
 extern "C" size_t fpsg_bn_max_workspace_floats(int N, int C, int L) {
   if (N <= 0 || C <= 0 || L <= 0) return 0;
-  const size_t segs = ((size_t)L + fpsg::kBnSeg - 1) / fpsg::kBnSeg;
-  // channel partials + per-(row, segment) extremes (4 words) / sum(dx) partials + dz [N*C]
-  return (size_t)C * fpsg::kBnSlices * 2 + (size_t)N * C * segs * 4 + (size_t)N * C;
+  return fpsg::max_workspace(N, C, L).floats;
 }
 
 extern "C" size_t fpsg_bn_max_dz_offset(int N, int C, int L) {
   if (N <= 0 || C <= 0 || L <= 0) return 0;
-  const size_t segs = ((size_t)L + fpsg::kBnSeg - 1) / fpsg::kBnSeg;
-  return (size_t)C * fpsg::kBnSlices * 2 + (size_t)N * C * segs * 4;     // dz [N*C] is the workspace's last block
+  return fpsg::max_workspace(N, C, L).dz;
 }
 
 extern "C" int fpsg_bn_act_max_fwd(const float* x, const float* pre_bias, const float* gamma, const float* beta,
@@ -1447,46 +1447,26 @@ extern "C" int fpsg_bn_act_max_fwd(const float* x, const float* pre_bias, const 
                                    float* chan, float* batch_mean, float* batch_var_unbiased, float* ws,
                                    fpsg_stream_t stream) {
   using namespace fpsg;
-  int rc = check_dims("fpsg_bn_act_max_fwd", N, C, L, act);
+  const char* fn = "fpsg_bn_act_max_fwd";
+  int rc = check_dims(fn, N, C, L, act);
   if (rc) return rc;
   FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(out); FPSG_REQUIRE_PTR(idx); FPSG_REQUIRE_PTR(chan); FPSG_REQUIRE_PTR(ws);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int segs = (L + kBnSeg - 1) / kBnSeg;
-  // one item per WAVE and pass: S workgroups of 4 waves per channel
-  const int items_max = N * segs;
-  const int S = items_max >= 4 * kBnSlices ? kBnSlices : (items_max + 3) / 4;
-  RowExt* ext = reinterpret_cast<RowExt*>(ws + (size_t)C * kBnSlices * 2);
-  dim3 grid(C, S);
-  const bool chan_given = training == 2;        // as in fpsg_bn_act_fwd
-  if (chan_given) training = 0;
-  if (training) {
-    if (beyond_cache((size_t)N * C * L * sizeof(float))) hipLaunchKernelGGL((bn_reduce_ext_kernel<1, true>), grid, dim3(kBnThreads), 0, s, x, pre_bias, N, C, L, S, ws, ext);
-    else hipLaunchKernelGGL(bn_reduce_ext_kernel<1>, grid, dim3(kBnThreads), 0, s, x, pre_bias, N, C, L, S, ws, ext);
-    if ((rc = launch_status("fpsg_bn_act_max_fwd(stats)"))) return rc;
-    hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(C), dim3(64), 0, s, ws, gamma, beta, C, S,
-                       (double)N * (double)L, eps, chan, batch_mean, batch_var_unbiased, running_mean, running_var,
-                       momentum);
-    if ((rc = launch_status("fpsg_bn_act_max_fwd(finalize)"))) return rc;
-  } else {
-    if (!chan_given) { FPSG_REQUIRE_PTR(running_mean); FPSG_REQUIRE_PTR(running_var); }
-    hipLaunchKernelGGL(bn_reduce_ext_kernel<0>, grid, dim3(kBnThreads), 0, s, x, pre_bias, N, C, L, S, ws, ext);
-    if ((rc = launch_status("fpsg_bn_act_max_fwd(extremes)"))) return rc;
-    if (!chan_given) {
-      hipLaunchKernelGGL(bn_eval_chan_kernel, dim3((C + 255) / 256), dim3(256), 0, s, running_mean, running_var,
-                         gamma, beta, C, eps, chan);
-      if ((rc = launch_status("fpsg_bn_act_max_fwd(eval)"))) return rc;
-    }
-  }
-  const int rows = N * C;
+  const bool chan_given = take_chan_given(training);
+  if ((rc = channel_coefficients(fn, kStatsRowExt, x, pre_bias, gamma, beta, running_mean, running_var, momentum, N, C, L,
+                                 training, chan_given, eps, chan, batch_mean, batch_var_unbiased, ws, nullptr, 0, s)))
+    return rc;
+  const RowExt* ext = reinterpret_cast<const RowExt*>(ws + max_workspace(N, C, L).rows);
+  const int rows = N * C, segs = (int)row_segs(L);
   dim3 og((rows + 255) / 256);
   if (act == kActRelu) hipLaunchKernelGGL(bn_max_out_kernel<kActRelu>, og, dim3(256), 0, s, ext, chan, rows, C, segs, slope, out, idx);
   else if (act == kActLeaky) hipLaunchKernelGGL(bn_max_out_kernel<kActLeaky>, og, dim3(256), 0, s, ext, chan, rows, C, segs, slope, out, idx);
   else hipLaunchKernelGGL(bn_max_out_kernel<kActNone>, og, dim3(256), 0, s, ext, chan, rows, C, segs, slope, out, idx);
-  return launch_status("fpsg_bn_act_max_fwd(out)");
+  return stage_status(fn, "out");
 }
 
-// The coefficient pass of fpsg_bn_act_max_bwd alone: dz [N,C] (left in the workspace at the offset that function uses: after
-// the channel partials and the dx partials), dgamma, dbeta and coef [3][C] = k1, k2, k3 of
+// The coefficient pass of fpsg_bn_act_max_bwd alone: dz [N,C] (left in the workspace where that function keeps it:
+// fpsg_bn_max_dz_offset), dgamma, dbeta and coef [3][C] = k1, k2, k3 of
 //   dx'[n,c,l] = k1_c dz[n,c] [l = idx[n,c]] + k2_c (x[n,c,l] + pre_bias_c) + k3_c .
 // For callers that do not form the dense dx: with x = W a the two products over it reduce to 128 x 128 Gram-matrix
 // algebra plus a gather and a scatter of N*C columns (fpsg_amd/fused_bn.py: _ConvBNActMax).
@@ -1498,13 +1478,8 @@ extern "C" int fpsg_bn_act_max_bwd_coef(const float* x, const float* pre_bias, c
   if (rc) return rc;
   FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(gout); FPSG_REQUIRE_PTR(idx); FPSG_REQUIRE_PTR(chan);
   FPSG_REQUIRE_PTR(dgamma); FPSG_REQUIRE_PTR(dbeta); FPSG_REQUIRE_PTR(coef); FPSG_REQUIRE_PTR(ws);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int segs = (L + kBnSeg - 1) / kBnSeg;
-  float* dz = ws + (size_t)C * kBnSlices * 2 + (size_t)N * C * segs * 4;
-#define FPSG_MAXB(A) hipLaunchKernelGGL(bn_max_bwd_coef_kernel<A>, dim3(C), dim3(64), 0, s, x, pre_bias, gout, idx, chan, \
-                                        N, C, L, training, slope, dz, dgamma, dbeta, coef)
-  if (act == kActRelu) FPSG_MAXB(kActRelu); else if (act == kActLeaky) FPSG_MAXB(kActLeaky); else FPSG_MAXB(kActNone);
-#undef FPSG_MAXB
+  launch_max_bwd_coef(act, x, pre_bias, gout, idx, chan, N, C, L, training, slope, ws + max_workspace(N, C, L).dz, dgamma,
+                      dbeta, coef, static_cast<hipStream_t>(stream));
   return launch_status("fpsg_bn_act_max_bwd_coef");
 }
 
@@ -1513,28 +1488,21 @@ extern "C" int fpsg_bn_act_max_bwd(const float* x, const float* pre_bias, const 
                                    float* dx, float* dgamma, float* dbeta, float* dpre_bias, float* coef, float* ws,
                                    fpsg_stream_t stream) {
   using namespace fpsg;
-  int rc = check_dims("fpsg_bn_act_max_bwd", N, C, L, act);
+  const char* fn = "fpsg_bn_act_max_bwd";
+  int rc = check_dims(fn, N, C, L, act);
   if (rc) return rc;
   FPSG_REQUIRE_PTR(x); FPSG_REQUIRE_PTR(gout); FPSG_REQUIRE_PTR(idx); FPSG_REQUIRE_PTR(chan); FPSG_REQUIRE_PTR(dx);
   FPSG_REQUIRE_PTR(dgamma); FPSG_REQUIRE_PTR(dbeta); FPSG_REQUIRE_PTR(coef); FPSG_REQUIRE_PTR(ws);
-  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0, FPSG_E_ALIGN,
-               "fpsg_bn_act_max_bwd: x and dx must be 16-byte aligned");
+  FPSG_REQUIRE(aligned16({x, dx}), FPSG_E_ALIGN, "%s: x and dx must be 16-byte aligned", fn);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int segs = (L + kBnSeg - 1) / kBnSeg;
-  float* dxpart = ws + (size_t)C * kBnSlices * 2;
-  float* dz = dxpart + (size_t)N * C * segs * 4;
-#define FPSG_MAXB(A) hipLaunchKernelGGL(bn_max_bwd_coef_kernel<A>, dim3(C), dim3(64), 0, s, x, pre_bias, gout, idx, chan, \
-                                        N, C, L, training, slope, dz, dgamma, dbeta, coef)
-  if (act == kActRelu) FPSG_MAXB(kActRelu); else if (act == kActLeaky) FPSG_MAXB(kActLeaky); else FPSG_MAXB(kActNone);
-#undef FPSG_MAXB
-  if ((rc = launch_status("fpsg_bn_act_max_bwd(coef)"))) return rc;
-  dim3 grid((unsigned)((size_t)N * C), segs);
-  hipLaunchKernelGGL(beyond_cache((size_t)N * C * L * sizeof(float)) ? bn_max_apply_kernel<true> : bn_max_apply_kernel<false>, grid, dim3(kBnThreads), 0, s, x, pre_bias, dz, idx, coef, C, L, dx,
-                     dpre_bias ? dxpart : nullptr);
-  if ((rc = launch_status("fpsg_bn_act_max_bwd(apply)"))) return rc;
-  if (dpre_bias) {
-    hipLaunchKernelGGL(bn_dxsum_kernel, dim3(C), dim3(64), 0, s, dxpart, N, C, segs, dpre_bias);
-    return launch_status("fpsg_bn_act_max_bwd(dpre_bias)");
-  }
-  return 0;
+  const BnWorkspace w = max_workspace(N, C, L);
+  float* dz = ws + w.dz;
+  launch_max_bwd_coef(act, x, pre_bias, gout, idx, chan, N, C, L, training, slope, dz, dgamma, dbeta, coef, s);
+  if ((rc = stage_status(fn, "coef"))) return rc;
+  const int segs = (int)row_segs(L);
+  return apply_and_dxsum(fn, [&](float* dxpart) {
+    dim3 grid((unsigned)((size_t)N * C), segs);
+    hipLaunchKernelGGL(beyond_cache((size_t)N * C * L * sizeof(float)) ? bn_max_apply_kernel<true> : bn_max_apply_kernel<false>,
+                       grid, dim3(kBnThreads), 0, s, x, pre_bias, dz, idx, coef, C, L, dx, dxpart);
+  }, N, C, segs, dpre_bias, ws, w, s);
 }

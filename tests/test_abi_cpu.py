@@ -74,6 +74,45 @@ def test_round4_entry_points_check_their_arguments(lib):
     assert lib.fpsg_bn_max_dz_offset(64, 1024, 2048) + 64 * 1024 == lib.fpsg_bn_max_workspace_floats(64, 1024, 2048)
 
 
+def test_batchnorm_workspace_sizes_and_offsets(lib):
+    """K5's size functions and the entry points that slice the buffer read one layout.  The numbers are those the
+    library returned before the layout had a single home (recorded from that build, not derived from this one), at
+    shapes with L below, at and not a multiple of the 4096-float segment and with H / 2 a multiple of the pooled
+    form's rows per item and not; the closed forms are that layout's (128 floats of channel sums per channel, then one
+    word, or four in the max form, per row and item; include/fpsg_hip.h states the dz offset's)."""
+    rows = {  # (N, C, L): (fpsg_bn_workspace_floats, fpsg_bn_max_workspace_floats, fpsg_bn_max_dz_offset)
+        (64, 1024, 2048): (196608, 458752, 393216),
+        (5, 9, 4096 + 4100): (1287, 1737, 1692),
+        (37, 64, 224 * 224): (38976, 133696, 131328),
+        (16, 769, 4736): (123040, 209168, 196864),
+        (2, 3, 4096): (390, 414, 408),
+        (1, 1, 1): (129, 133, 132),
+        (3, 2, 2 ** 31 - 1): (3145984, 12583174, 12583168),
+    }
+    for (N, C, L), (plain, most, dz) in rows.items():
+        segs = -(-L // 4096)
+        assert lib.fpsg_bn_workspace_floats(N, C, L) == plain == C * 128 + N * C * segs, (N, C, L)
+        assert lib.fpsg_bn_max_dz_offset(N, C, L) == dz == C * 128 + N * C * segs * 4, (N, C, L)
+        assert lib.fpsg_bn_max_workspace_floats(N, C, L) == most == dz + N * C, (N, C, L)
+    planes = {  # (N, C, H, W): fpsg_bn_pool_workspace_floats; rows per item = max(1, 4096 // (2 W))
+        (37, 64, 224, 224): 38976,       # 112 row pairs in items of 9: 13 items
+        (8, 64, 112, 112): 10240,        # 56 in items of 18: 4
+        (2, 3, 6, 4098): 402,            # a row pair longer than an item: 3 items of 1
+        (4, 16, 36, 56): 2112,           # 18 in one item of 36
+        (2, 8, 64, 64): 1040,            # 32 in one item of 32
+        (5, 7, 30, 6): 931,
+        (1, 1, 2, 2): 129,
+    }
+    for (N, C, H, W), floats in planes.items():
+        rp = max(1, 4096 // (2 * W))
+        assert lib.fpsg_bn_pool_workspace_floats(N, C, H, W) == floats == C * 128 + N * C * -(-(H // 2) // rp), (N, C, H, W)
+    for bad in ((0, 4, 4), (4, -1, 4), (4, 4, 0)):
+        assert lib.fpsg_bn_workspace_floats(*bad) == 0 and lib.fpsg_bn_max_workspace_floats(*bad) == 0, bad
+        assert lib.fpsg_bn_max_dz_offset(*bad) == 0, bad
+    for bad in ((0, 1, 2, 2), (1, 0, 2, 2), (1, 1, 1, 2), (1, 1, 2, 1), (1, 1, 0, -2)):
+        assert lib.fpsg_bn_pool_workspace_floats(*bad) == 0, bad
+
+
 def test_gemm_variant_ids_outside_the_documented_lists_are_refused_on_the_host(lib):
     """K10's entry points take the variant ids include/fpsg_hip.h lists and nothing else: the ids that once selected
     measurement-only builds (kernels without their loads, stores or split, delayed starts, no wave priorities) get
