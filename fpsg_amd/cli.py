@@ -15,7 +15,8 @@ EMD per class beside the two reference metrics), ``--set_metrics`` (evaluation: 
 distance per class, over the class's generated and reference query clouds), ``--set_metrics_emd`` (the same under the
 exact EMD), ``--set_metrics_points N`` (evaluation: the clouds of the two set metrics reduced to N points each by farthest
 point sampling, K16, and the labels marked ``@N``), ``--jsd`` (evaluation: the Jensen-Shannon divergence between the voxel-occupancy distributions of the class's
-generated and reference query clouds).
+generated and reference query clouds), ``--fscore TAU [TAU ...]`` (evaluation: the F-score of every reconstruction at
+those distances and the Hausdorff distance, per class).
 """
 from __future__ import annotations
 
@@ -99,6 +100,11 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
         g.add_argument("--jsd", action="store_true",
                        help="Also report the Jensen-Shannon divergence per class between the voxel-occupancy distributions "
                             "of its generated and reference query clouds (HIP occupancy grid, fpsg_amd.set_metrics.jsd);")
+        g.add_argument("--fscore", type=float, nargs="+", default=None, metavar="TAU",
+                       help="Also report per class the F-score of the reconstructions at these distances (1 to 16 of them; "
+                            "share of points within TAU of the other cloud, precision and recall combined) and the Hausdorff "
+                            "distance (HIP distance profile, fpsg_amd.metrics.fscore); TAU is a Euclidean distance in the "
+                            "clouds' units: the clouds are normalised into the unit ball, so 0.02 is 1 %% of its diameter;")
     return p
 
 
@@ -113,6 +119,15 @@ def validate(opt) -> None:
             raise SystemExit("--set_metrics_points needs --set_metrics and / or --set_metrics_emd")
         if points < 1:
             raise SystemExit(f"--set_metrics_points must be at least 1 (got {points})")
+    taus = getattr(opt, "fscore", None)
+    if taus is not None:
+        from .metrics import PROFILE_MAX_T, check_thresholds
+        if len(taus) > PROFILE_MAX_T:
+            raise SystemExit(f"--fscore takes at most {PROFILE_MAX_T} thresholds (got {len(taus)})")
+        try:
+            check_thresholds(taus)
+        except ValueError as e:
+            raise SystemExit(f"--fscore: {e}") from None
 
 
 def build_datasets(opt, n_query: int, device):

@@ -231,14 +231,25 @@ class EvalItem:
 
     ``return_clouds=True`` (``evaluate_Network.py --set_metrics``): every item also returns ``"syn_pc"`` and
     ``"ref_pc_q"``, the generated and reference query clouds, as clones: on the replay path they are the graph's static
-    output buffers, which the next replay overwrites."""
+    output buffers, which the next replay overwrites.
+
+    ``fscore=(tau, ...)`` (``evaluate_Network.py --fscore``; 1 to 16 distances, ``metrics.check_thresholds``): every item
+    also returns ``"fscore"``, ``"precision"`` and ``"recall"``, float64 ``[T]``, the means over the item's query pairs of
+    ``metrics.fscore(syn_pc, ref_pc_q, thresholds)`` (generated against reference: K1's forward once more, then K17), and
+    ``"hausdorff"``, 0-dim, the mean of the pairs' Hausdorff distances -- computed like ``exact_emd``, eagerly after the
+    item on the clouds it holds, never inside a capture."""
 
     _KEYS = ("xs", "xq", "xad", "pcs", "pcq", "pcad")
 
-    def __init__(self, model, graph: bool | None = None, exact_emd: bool = False, return_clouds: bool = False):
+    def __init__(self, model, graph: bool | None = None, exact_emd: bool = False, return_clouds: bool = False,
+                 fscore=None):
         self.model = model
         self.exact_emd = bool(exact_emd)
         self.return_clouds = bool(return_clouds)
+        if fscore is not None:
+            from .metrics import check_thresholds
+            fscore = check_thresholds(fscore)
+        self.fscore = fscore
         on_gpu = next(model.parameters()).is_cuda
         if graph is None:
             graph = os.environ.get("FPSG_EVAL_GRAPH", "1") != "0"
@@ -271,13 +282,19 @@ class EvalItem:
         return self.model.emd_metric is emd_wrapper and self.model.pc_metric is chamfer_distance
 
     def __call__(self, sample):
-        if not self.exact_emd and not self.return_clouds:
+        if not self.exact_emd and not self.return_clouds and self.fscore is None:
             return self._item(sample)
         out = self._item(sample, clouds=True)
         syn_pc, ref_pc_q = out.pop("syn_pc"), out.pop("ref_pc_q")
         if self.exact_emd:
             from .metrics import emd_exact
             out["exact_emd"] = emd_exact(syn_pc.contiguous(), ref_pc_q.contiguous()).sum()
+        if self.fscore is not None:
+            from .metrics import fscore
+            f = fscore(syn_pc.contiguous(), ref_pc_q.contiguous(), self.fscore)
+            for key in ("fscore", "precision", "recall"):
+                out[key] = f[key].mean(dim=0)
+            out["hausdorff"] = f["hausdorff"].mean()
         if self.return_clouds:
             out["syn_pc"], out["ref_pc_q"] = syn_pc.clone(), ref_pc_q.clone()
         return out

@@ -516,6 +516,103 @@ def occupancy_grid(clouds: torch.Tensor, resolution: int = 28, half_extent: floa
     return out
 
 
+PROFILE_MAX_T = 16              # FPSG_PROFILE_MAX_T (include/fpsg_hip.h)
+
+
+def check_thresholds(thresholds) -> tuple:
+    """The distance thresholds of ``distance_profile`` / ``fscore`` as a tuple of Python floats: a sequence of 1 to
+    ``PROFILE_MAX_T`` finite, non-negative numbers (``ValueError`` otherwise)."""
+    if isinstance(thresholds, (str, bytes, torch.Tensor)) or not hasattr(thresholds, "__len__"):
+        raise ValueError(f"thresholds must be a sequence of numbers, got {thresholds!r}")
+    if not 1 <= len(thresholds) <= PROFILE_MAX_T:
+        raise ValueError(f"thresholds: from 1 to {PROFILE_MAX_T} values, got {len(thresholds)}")
+    try:
+        taus = tuple(float(t) for t in thresholds)
+    except (TypeError, ValueError):
+        raise ValueError(f"thresholds must be numbers, got {thresholds!r}") from None
+    for t in taus:
+        if not (math.isfinite(t) and t >= 0.0):
+            raise ValueError(f"thresholds must be finite and non-negative, got {t!r}")
+    return taus
+
+
+def fscore_from_counts(counts: torch.Tensor, n1: int, n2: int) -> dict:
+    """Precision, recall and F-score from K17's counts ``[B,2,T]`` (any integer dtype, any device), float64 ``[B,T]``
+    each: ``precision = counts[:,0] / n1``, ``recall = counts[:,1] / n2``, ``fscore = 2 * P * R / (P + R)`` evaluated
+    in that order, and exactly 0.0 where ``P + R == 0``.  ``ValueError`` for another rank, a non-integer dtype,
+    ``n1`` or ``n2 < 1`` or a count outside ``[0, n]``."""
+    if not isinstance(counts, torch.Tensor) or counts.dim() != 3 or counts.size(1) != 2:
+        raise ValueError(f"expected counts [B,2,T], got {tuple(getattr(counts, 'shape', ()))}")
+    if counts.dtype.is_floating_point or counts.dtype.is_complex or counts.dtype == torch.bool:
+        raise ValueError(f"counts must have an integer dtype, got {counts.dtype}")
+    if int(n1) != n1 or int(n2) != n2 or n1 < 1 or n2 < 1:
+        raise ValueError(f"n1 and n2 must be positive integers, got {n1!r} and {n2!r}")
+    if counts.numel():
+        c = counts.long()
+        if bool((c.min() < 0) | (c[:, 0].max() > n1) | (c[:, 1].max() > n2)):      # one host read
+            raise ValueError(f"counts outside [0, n1={n1}] / [0, n2={n2}]")
+    c = counts.to(torch.float64)
+    precision, recall = c[:, 0] / int(n1), c[:, 1] / int(n2)
+    s = precision + recall
+    none = s == 0
+    f = 2 * precision * recall / torch.where(none, torch.ones_like(s), s)
+    return {"precision": precision, "recall": recall, "fscore": torch.where(none, torch.zeros_like(f), f)}
+
+
+def distance_profile(dist1: torch.Tensor, dist2: torch.Tensor, thresholds):
+    """K17 (HIP; the definition is in ``include/fpsg_hip.h``): for squared distances ``dist1 [B,N]`` and ``dist2
+    [B,M]`` (K1's rows, or any non-negative fp32 rows) and 1 to 16 ``thresholds`` -- Euclidean distances in the clouds'
+    units, finite and >= 0, in any order -- returns ``(counts, maxima)``: ``counts [B,2,T]`` int32, the number of
+    entries of ``dist1[b]`` (``[:,0]``) and of ``dist2[b]`` (``[:,1]``) that are ``<= tau2[t]`` in fp32, with ``tau2[t] =
+    float32(float(thresholds[t]) ** 2)`` (the square formed in double and rounded once); ``maxima [B,2]`` fp32,
+    ``max(0, max_i dist[b,i])`` per direction.  A NaN entry is counted nowhere and ignored by the maximum.
+
+    Exact and bitwise reproducible, independent of the batch.  Detached: the result never requires grad.  No CPU path
+    (CPU tensors raise ``FpsgHipError``); ``ValueError`` for bad thresholds (checked first) or shapes."""
+    taus = check_thresholds(thresholds)
+    for t, name in ((dist1, "dist1"), (dist2, "dist2")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{name}: expected a [B,n] tensor, got {tuple(getattr(t, 'shape', ()))}")
+    if dist1.size(0) != dist2.size(0):
+        raise ValueError(f"batch mismatch: {dist1.size(0)} vs {dist2.size(0)}")
+    if dist1.device != dist2.device:
+        raise ValueError(f"device mismatch: {dist1.device} vs {dist2.device}")
+    if dist1.numel() == 0 or dist2.numel() == 0:
+        raise ValueError(f"empty rows are not supported (got {tuple(dist1.shape)} and {tuple(dist2.shape)})")
+    dist1, dist2 = dist1.detach(), dist2.detach()
+    _hip.dev_tensor(dist1, torch.float32, "dist1")
+    _hip.dev_tensor(dist2, torch.float32, "dist2")
+    B, N = dist1.shape
+    M = dist2.size(1)
+    T = len(taus)
+    dev = dist1.device
+    tau2 = torch.tensor([t * t for t in taus], dtype=torch.float64).to(torch.float32).to(dev)
+    counts = torch.empty((B, 2, T), dtype=torch.int32, device=dev)
+    maxima = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _probe("dist_profile", B, N, M):
+        rc = _hip.load().fpsg_dist_profile(_hip.ptr(dist1), _hip.ptr(dist2), B, N, M, _hip.ptr(tau2), T,
+                                           _hip.ptr(counts), _hip.ptr(maxima), _hip.stream_of(dist1))
+    _hip.check(rc, "fpsg_dist_profile")
+    return counts, maxima
+
+
+def fscore(p1: torch.Tensor, p2: torch.Tensor, thresholds) -> dict:
+    """F-score at distance thresholds and the Hausdorff distance of the pairs ``p1 [B,N,3]`` (the reconstruction) and
+    ``p2 [B,M,3]`` (the ground truth); ``thresholds`` as in ``distance_profile``.  K1's forward (the minima of
+    ``chamfer_distance``, bit for bit), then K17, then ``fscore_from_counts``: a dict with ``"precision"`` (the share
+    of reconstructed points within tau of the ground truth), ``"recall"`` (the share of ground-truth points within tau
+    of the reconstruction) and ``"fscore"``, float64 ``[B,T]``; ``"hausdorff" [B]`` float64, ``sqrt(max(maxima[:,0],
+    maxima[:,1]))``; and K17's ``"counts"`` and ``"maxima"``.  Forward only; no CPU path."""
+    taus = check_thresholds(thresholds)
+    with torch.no_grad():
+        dist1, dist2, _, _ = _sided_forward(p1.detach(), p2.detach())
+    counts, maxima = distance_profile(dist1, dist2, taus)
+    out = fscore_from_counts(counts, p1.size(1), p2.size(1))
+    out["hausdorff"] = maxima.to(torch.float64).amax(dim=1).sqrt()
+    out["counts"], out["maxima"] = counts, maxima
+    return out
+
+
 def softmin(x: torch.Tensor, y: torch.Tensor, h: torch.Tensor, eps: float) -> torch.Tensor:
     """``out[b,i] = -eps * logsumexp_j(h[b,j] - |x_i - y_j|^2 / (2 eps))`` (K2b), no grad."""
     _check_clouds(x, y)

@@ -331,6 +331,26 @@ size_t fpsg_fps_workspace_bytes(int B, int N, int n);
 int fpsg_fps(const float* xyz, int B, int N, int n, const int32_t* start, int32_t* idx, float* min_dist, void* ws,
              size_t ws_bytes, fpsg_stream_t stream);
 
+/* ---- K17: distance profile of cloud pairs (F-score at distance thresholds, Hausdorff distance) ----
+ * The item-level columns beside Chamfer (Tatarchenko et al., CVPR 2019): which share of one cloud lies within a
+ * distance of the other.  The published scripts are not pinned; the definition below is the specification
+ * (DESIGN.md K17).
+ * dist1 [B,N], dist2 [B,M] fp32 squared distances -- K1's outputs, but any non-negative rows are valid; tau2 [T]
+ * fp32 DEVICE array of squared thresholds, in any order.
+ *   counts [B,2,T] int32, overwritten: counts[b][0][t] = #{i : dist1[b,i] <= tau2[t]}, counts[b][1][t] the same over
+ *     dist2[b,:].  The compare is fp32 `<=`: a value equal to the threshold is counted, a NaN is counted nowhere.
+ *   maxima [B,2] fp32, overwritten: max(0, max_i dist[b,i]) per direction, NaN entries ignored.  The square root is
+ *     the caller's (in double, on the host side), so the output is exact.
+ * Exact (integers, and a maximum has no order); pair b's outputs are bitwise the same on every run, whatever B is
+ * and wherever the pair sits in the batch.  No atomics, no workspace, no communication between workgroups; every
+ * loop count depends on N, M and T only.  The call only enqueues work on `stream` (it can be captured in a graph).
+ * Errors, all before any launch: FPSG_E_SHAPE for B, N, M or T < 1; FPSG_E_LIMIT for T > FPSG_PROFILE_MAX_T;
+ * FPSG_E_NULL for any null pointer; FPSG_E_ALIGN for a misaligned pointer.
+ */
+#define FPSG_PROFILE_MAX_T 16
+int fpsg_dist_profile(const float* dist1, const float* dist2, int B, int N, int M, const float* tau2, int T,
+                      int32_t* counts, float* maxima, fpsg_stream_t stream);
+
 /* ---- K4b: fused EdgeConv (gather + BatchNorm statistics + max over k) -----------------
  * Replaces the chain get_graph_feature -> Conv2d 1x1 -> BatchNorm2d -> LeakyReLU -> max_k of
  * src/dgcnn/model.py:23-42,53-56,63-76 without materialising [B,2C,N,k].  The caller first
