@@ -8,7 +8,9 @@ every test episode (HIP Chamfer K1 + the HIP Sinkhorn divergence K2b, the form `
 exact transport distance of K12 divided by n_query like the other two; ``--fscore TAU [TAU ...]``: then
 ``; F@<tau>: <mean>`` for every threshold in the order given, ``<tau>`` as ``repr(float)``, and once ``; HD: <mean>``: the
 F-score of the reconstructions at those distances and the Hausdorff distance, K17's counts and maxima over K1's minima,
-averaged over an item's queries and then over the class's items like ``Rec CD``; ``--set_metrics``: then
+averaged over an item's queries and then over the class's items like ``Rec CD``; ``--dcd [ALPHA]``: then
+``; DCD: <mean>``, the density-aware Chamfer distance of the reconstructions (K18 over K1's minima and indices, in
+[0, 1]), averaged the same way; ``--set_metrics``: then
 ``; MMD-CD: <v>; COV-CD: <v>; 1-NNA-CD: <v>``, the set-level generation metrics of ``fpsg_amd.set_metrics`` over all
 the class's generated and reference query clouds, from K13's Chamfer matrices; ``--set_metrics_emd``: then
 ``; MMD-EMD: <v>; COV-EMD: <v>; 1-NNA-EMD: <v>``, the same under the exact EMD from K14's matrices, followed by
@@ -61,6 +63,8 @@ def main(opt):
     taus = getattr(opt, "fscore", None)
     taus = None if taus is None else tuple(taus)
     per_class_f = defaultdict(list)                     # per class and item: [fscore [T], precision [T], recall [T], hd]
+    dcd_alpha = getattr(opt, "dcd", None)
+    per_class_dcd = defaultdict(list)
     sets = bool(getattr(opt, "set_metrics", False))
     sets_emd = bool(getattr(opt, "set_metrics_emd", False))
     per_class_gen, per_class_ref = defaultdict(list), defaultdict(list)
@@ -70,7 +74,8 @@ def main(opt):
     grid_gen, grid_ref = {}, {}                         # per class: the two occupancy grids, accumulated per item
     # the weights do not change while evaluating: transformed filters, stacked decoder weights and BatchNorm coefficients
     # are made once, not per item; on a GPU the item in front of the EMD is replayed as a hipGraph (engine.EvalItem)
-    with EvalItem(model, exact_emd=exact, return_clouds=sets or sets_emd or want_jsd, fscore=taus) as run_item:
+    with EvalItem(model, exact_emd=exact, return_clouds=sets or sets_emd or want_jsd, fscore=taus,
+                  dcd=dcd_alpha) as run_item:
         for item, sample in enumerate(dl_test):
             sample = to_device(sample, device)
             if getattr(opt, "npy_folder", ""):
@@ -86,6 +91,8 @@ def main(opt):
             if taus is not None:                        # the item's means over its queries, in one host read
                 per_class_f[name].append(torch.stack([out["fscore"], out["precision"], out["recall"],
                                                       out["hausdorff"].expand(len(taus))]).tolist())
+            if dcd_alpha is not None:
+                per_class_dcd[name].append(out["dcd"].item())
             if sets or sets_emd:                        # kept on the device; one set per class after the loop
                 gen, ref = out["syn_pc"], out["ref_pc_q"]
                 if set_points is not None:              # K16, two launches per item: only the reduced clouds are kept
@@ -132,6 +139,8 @@ def main(opt):
         if taus is not None:
             m = per_class_fscore[name]
             line += "".join(f"; F@{tau!r}: {v}" for tau, v in zip(taus, m["fscore"])) + f"; HD: {m['hausdorff']}"
+        if dcd_alpha is not None:
+            line += f"; DCD: {statistics.mean(per_class_dcd[name])}"
         if sets:
             m = per_class_set[name]
             line += f"; MMD-CD{at}: {m['mmd_cd']}; COV-CD{at}: {m['cov_cd']}; 1-NNA-CD{at}: {m['nna_cd']}"
@@ -145,7 +154,7 @@ def main(opt):
         print(line)
     return (per_class_cd, per_class_emd) + ((per_class_exact,) if exact else ()) + ((per_class_set,) if sets else ()) + \
         ((per_class_set_emd,) if sets_emd else ()) + ((per_class_jsd,) if want_jsd else ()) + \
-        ((per_class_fscore,) if taus is not None else ())
+        ((per_class_fscore,) if taus is not None else ()) + ((per_class_dcd,) if dcd_alpha is not None else ())
 
 
 if __name__ == "__main__":

@@ -193,6 +193,8 @@ SIGNATURES = {
     "fpsg_fps_workspace_bytes": [_c_int, _c_int, _c_int],
     "fpsg_fps": [_c_f32p, _c_int, _c_int, _c_int, _c_i32p, _c_i32p, _c_f32p, ctypes.c_void_p, ctypes.c_size_t, _c_stream],
     "fpsg_dist_profile": [_c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_f32p, _c_int, _c_i32p, _c_f32p, _c_stream],
+    "fpsg_dcd": [_c_f32p, _c_i32p, _c_f32p, _c_i32p, _c_int, _c_int, _c_int, ctypes.c_float, _c_f32p, _c_f32p, _c_i32p,
+                 _c_i32p, _c_f32p, _c_f32p, _c_stream],
 }
 _RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_chamfer_workspace_bytes": ctypes.c_size_t,
              "fpsg_sinkhorn_workspace_floats": ctypes.c_size_t,

@@ -16,7 +16,8 @@ distance per class, over the class's generated and reference query clouds), ``--
 exact EMD), ``--set_metrics_points N`` (evaluation: the clouds of the two set metrics reduced to N points each by farthest
 point sampling, K16, and the labels marked ``@N``), ``--jsd`` (evaluation: the Jensen-Shannon divergence between the voxel-occupancy distributions of the class's
 generated and reference query clouds), ``--fscore TAU [TAU ...]`` (evaluation: the F-score of every reconstruction at
-those distances and the Hausdorff distance, per class).
+those distances and the Hausdorff distance, per class), ``--pc_dist dcd`` with ``--dcd_alpha`` (training on the
+density-aware Chamfer distance, K18), ``--dcd [ALPHA]`` (evaluation: that distance per class).
 """
 from __future__ import annotations
 
@@ -69,7 +70,10 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--lr", type=float, default=1e-3)
     g.add_argument("--lr_decay", type=float, default=350)
     g.add_argument("--resume", type=int, default=-1)
-    g.add_argument("--pc_dist", type=str, default="cd", choices=["cd", "emd"])
+    g.add_argument("--pc_dist", type=str, default="cd", choices=["cd", "emd", "dcd"])
+    g.add_argument("--dcd_alpha", type=float, default=1000.0,
+                   help="With --pc_dist dcd: the factor on the squared nearest-neighbour distance inside the exponential "
+                        "of the density-aware Chamfer distance [default: 1000];")
     g.add_argument("--SGD", action="store_true")
     g.add_argument("--episodes_per_step", type=int, default=0,
                    help="Episodes per optimizer step over all ranks [default: one per rank];")
@@ -105,6 +109,9 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
                             "share of points within TAU of the other cloud, precision and recall combined) and the Hausdorff "
                             "distance (HIP distance profile, fpsg_amd.metrics.fscore); TAU is a Euclidean distance in the "
                             "clouds' units: the clouds are normalised into the unit ball, so 0.02 is 1 %% of its diameter;")
+        g.add_argument("--dcd", type=float, nargs="?", const=1000.0, default=None, metavar="ALPHA",
+                       help="Also report per class the density-aware Chamfer distance of the reconstructions (in [0, 1]; "
+                            "HIP, fpsg_amd.metrics.dcd); ALPHA is the factor on the squared distance [default: 1000];")
     return p
 
 
@@ -128,6 +135,14 @@ def validate(opt) -> None:
             check_thresholds(taus)
         except ValueError as e:
             raise SystemExit(f"--fscore: {e}") from None
+    for flag in ("dcd_alpha", "dcd"):
+        alpha = getattr(opt, flag, None)
+        if alpha is not None:
+            from .metrics import check_dcd_alpha
+            try:
+                check_dcd_alpha(alpha)
+            except ValueError as e:
+                raise SystemExit(f"--{flag}: {e}") from None
 
 
 def build_datasets(opt, n_query: int, device):

@@ -48,7 +48,7 @@ def build_model(opt) -> ImgPCProtoNet:
     return ImgPCProtoNet(img_encoder, pc_encoder, pc_decoder, mask_learner=None,
                          query_factor=opt.query_factor, support_factor=opt.support_factor,
                          metric=getattr(opt, "pc_dist", "cd"), intra_support=opt.intra_recon,
-                         aggregate=opt.aggregate)
+                         aggregate=opt.aggregate, dcd_alpha=getattr(opt, "dcd_alpha", 1000.0))
 
 
 def build_optimizer(model, opt):
@@ -237,12 +237,16 @@ class EvalItem:
     also returns ``"fscore"``, ``"precision"`` and ``"recall"``, float64 ``[T]``, the means over the item's query pairs of
     ``metrics.fscore(syn_pc, ref_pc_q, thresholds)`` (generated against reference: K1's forward once more, then K17), and
     ``"hausdorff"``, 0-dim, the mean of the pairs' Hausdorff distances -- computed like ``exact_emd``, eagerly after the
-    item on the clouds it holds, never inside a capture."""
+    item on the clouds it holds, never inside a capture.
+
+    ``dcd=alpha`` (``evaluate_Network.py --dcd``; ``metrics.check_dcd_alpha``): every item also returns ``"dcd"``, 0-dim, the
+    mean over the item's query pairs of ``metrics.dcd(syn_pc, ref_pc_q, alpha)`` (K1's forward once more, then K18),
+    computed the same way, eagerly after the item.  ``None``: ``__call__`` stays on the branches it has."""
 
     _KEYS = ("xs", "xq", "xad", "pcs", "pcq", "pcad")
 
     def __init__(self, model, graph: bool | None = None, exact_emd: bool = False, return_clouds: bool = False,
-                 fscore=None):
+                 fscore=None, dcd=None):
         self.model = model
         self.exact_emd = bool(exact_emd)
         self.return_clouds = bool(return_clouds)
@@ -250,6 +254,10 @@ class EvalItem:
             from .metrics import check_thresholds
             fscore = check_thresholds(fscore)
         self.fscore = fscore
+        if dcd is not None:
+            from .metrics import check_dcd_alpha
+            dcd = check_dcd_alpha(dcd)
+        self.dcd = dcd
         on_gpu = next(model.parameters()).is_cuda
         if graph is None:
             graph = os.environ.get("FPSG_EVAL_GRAPH", "1") != "0"
@@ -282,7 +290,7 @@ class EvalItem:
         return self.model.emd_metric is emd_wrapper and self.model.pc_metric is chamfer_distance
 
     def __call__(self, sample):
-        if not self.exact_emd and not self.return_clouds and self.fscore is None:
+        if not self.exact_emd and not self.return_clouds and self.fscore is None and self.dcd is None:
             return self._item(sample)
         out = self._item(sample, clouds=True)
         syn_pc, ref_pc_q = out.pop("syn_pc"), out.pop("ref_pc_q")
@@ -295,6 +303,9 @@ class EvalItem:
             for key in ("fscore", "precision", "recall"):
                 out[key] = f[key].mean(dim=0)
             out["hausdorff"] = f["hausdorff"].mean()
+        if self.dcd is not None:
+            from .metrics import dcd
+            out["dcd"] = dcd(syn_pc.detach().contiguous(), ref_pc_q.detach().contiguous(), self.dcd).mean()
         if self.return_clouds:
             out["syn_pc"], out["ref_pc_q"] = syn_pc.clone(), ref_pc_q.clone()
         return out

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .metrics import chamfer_distance, emd_loss, episode_chamfer_losses
+from .metrics import chamfer_distance, check_dcd_alpha, dcd, emd_loss, episode_chamfer_losses
 from .utils import emd_wrapper
 
 _AGGREGATOR = ["single", "multi", "mask_single", "mask_multi"]
@@ -60,7 +60,7 @@ def _split_rows(t, n):
 
 class ImgPCProtoNet(nn.Module):
     def __init__(self, img_encoder, pc_encoder, pc_decoder, mask_learner=None, query_factor=1.0,
-                 support_factor=1.0, metric="cd", intra_support=False, aggregate="single"):
+                 support_factor=1.0, metric="cd", intra_support=False, aggregate="single", dcd_alpha=1000.0):
         super().__init__()
         self.img_encoder = img_encoder
         self.pc_encoder = pc_encoder
@@ -78,14 +78,22 @@ class ImgPCProtoNet(nn.Module):
         elif metric == "emd":
             # training needs gradients: the differentiable approximate-assignment solver (K2)
             self.pc_metric = lambda a, b: emd_loss(a, b, reduce="sum", sinkhorn=False).reshape(1)
+        elif metric == "dcd":
+            # the density-aware Chamfer distance (K18) per pair, in [0, 1]; alpha multiplies the squared distance
+            self.dcd_alpha = check_dcd_alpha(dcd_alpha)
+            self.pc_metric = self._dcd_metric
         else:
             raise NotImplementedError(
                 f"Found unsupported point cloud reconstruction metrics: {metric}")
         # evaluation-only distance (reference few_shot.py:168); an attribute so that a test
         # can drive the module on CPU with the oracle's implementations
         self.emd_metric = emd_wrapper
+        self._dcd = metric == "dcd"
         self.overlap_encoders = False      # see _encode; switched on by bench.py / the trainer
         self._side_stream = None
+
+    def _dcd_metric(self, a, b):
+        return dcd(a, b, self.dcd_alpha)
 
     # ------------------------------------------------------------------ shared forward
     def _encode(self, img_s, img_q, img_ad, pc_s, pc_ad):
@@ -189,6 +197,13 @@ class ImgPCProtoNet(nn.Module):
                             "support_rec_loss": loss_rec_s}
                 cd = self.pc_metric(syn, ref)
                 loss_rec_q, loss_rec_s = cd[:n_q].sum(), cd[n_q:].sum()
+            elif self._dcd and syn_q.shape[1:] == syn_s.shape[1:] and ref_q.shape[1:] == ref_s.shape[1:]:
+                # as the Chamfer branch: ONE K1 + K18 call over the Q + S pairs (a pair's value does not depend on the
+                # batch, so this is only fewer launches); the fused K1l sums are Chamfer's alone
+                if syn is None:
+                    syn = torch.cat([syn_q, syn_s])
+                d = self.pc_metric(syn, torch.cat([ref_q, ref_s]))
+                loss_rec_q, loss_rec_s = d[:n_q].sum(), d[n_q:].sum()
             else:
                 loss_rec_q = self.pc_metric(syn_q, ref_q).sum()
                 loss_rec_s = self.pc_metric(syn_s, ref_s).sum()

@@ -613,6 +613,103 @@ def fscore(p1: torch.Tensor, p2: torch.Tensor, thresholds) -> dict:
     return out
 
 
+DCD_MAX_N = 16384               # FPSG_DCD_MAX_N (include/fpsg_hip.h)
+DCD_DEFAULT_ALPHA = 1000.0
+
+
+def check_dcd_alpha(alpha) -> float:
+    """``alpha`` of ``dcd`` as a Python float: a finite, non-negative number (``ValueError`` otherwise)."""
+    try:
+        a = float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"alpha must be a number, got {alpha!r}") from None
+    if not (math.isfinite(a) and a >= 0.0):
+        raise ValueError(f"alpha must be finite and non-negative, got {alpha!r}")
+    return a
+
+
+def _dcd_from_rows(dist1, idx1, dist2, idx2, alpha, need1, need2):
+    """K18 through the C ABI on K1's rows: ``(out [B], sides [B,2], deg1 [B,N], deg2 [B,M], w1 | None, w2 | None)``."""
+    B, N = dist1.shape
+    M = dist2.size(1)
+    dev = dist1.device
+    out = torch.empty((B,), dtype=torch.float32, device=dev)
+    sides = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    deg1 = torch.empty((B, N), dtype=torch.int32, device=dev)
+    deg2 = torch.empty((B, M), dtype=torch.int32, device=dev)
+    w1 = torch.empty((B, N), dtype=torch.float32, device=dev) if need1 else None
+    w2 = torch.empty((B, M), dtype=torch.float32, device=dev) if need2 else None
+    with torch.cuda.device(dev), _probe("dcd", B, N, M):
+        rc = _hip.load().fpsg_dcd(_hip.ptr(dist1), _hip.ptr(idx1), _hip.ptr(dist2), _hip.ptr(idx2), B, N, M, float(alpha),
+                                  _hip.ptr(out), _hip.ptr(sides), _hip.ptr(deg1), _hip.ptr(deg2),
+                                  None if w1 is None else _hip.ptr(w1), None if w2 is None else _hip.ptr(w2),
+                                  _hip.stream_of(dist1))
+    _hip.check(rc, "fpsg_dcd")
+    return out, sides, deg1, deg2, w1, w2
+
+
+class _Dcd(torch.autograd.Function):
+    """K1's forward, then K18 with the per-point derivatives ``w1`` / ``w2`` where an input needs a gradient; the
+    backward scales them by the upstream ``[B]`` gradient and is K1's backward (the counts held constant)."""
+
+    @staticmethod
+    def forward(ctx, p1, p2, alpha, info_out):
+        ctx.set_materialize_grads(False)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        dist1, dist2, idx1, idx2 = _sided_forward(p1, p2)
+        # both weight rows as soon as one cloud needs a gradient: either cloud's gradient takes both directions
+        out, sides, deg1, deg2, w1, w2 = _dcd_from_rows(dist1, idx1, dist2, idx2, alpha, need, need)
+        if info_out is not None:
+            info_out.update(sides=sides, deg1=deg1, deg2=deg2, dist1=dist1, dist2=dist2, idx1=idx1, idx2=idx2)
+        if need:
+            ctx.save_for_backward(p1, p2, idx1, idx2, w1, w2)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        p1, p2, idx1, idx2, w1, w2 = ctx.saved_tensors
+        gc = g.reshape(-1, 1).float()
+        gx1, gx2 = _sided_backward(p1, p2, idx1, idx2, (w1 * gc).contiguous(), (w2 * gc).contiguous())
+        return (gx1 if ctx.needs_input_grad[0] else None), (gx2 if ctx.needs_input_grad[1] else None), None, None
+
+
+def dcd(p1: torch.Tensor, p2: torch.Tensor, alpha: float = DCD_DEFAULT_ALPHA, return_info: bool = False):
+    """Density-aware Chamfer distance ``[B]`` fp32 in ``[0, 1]`` of the pairs ``p1 [B,N,3]`` and ``p2 [B,M,3]`` (Wu et
+    al., NeurIPS 2021; K18, HIP; the definition is in ``include/fpsg_hip.h``): with K1's squared nearest-neighbour
+    distances ``d`` and indices, ``0.5 * (mean_i (1 - exp(-alpha d1_i) / deg2[idx1_i]) + mean_j (1 - exp(-alpha d2_j) /
+    deg1[idx2_j]))``, where ``deg2[j]`` is the number of points of ``p1`` whose nearest neighbour is ``p2[j]`` and
+    ``deg1`` the same the other way.  ``alpha`` multiplies the *squared* distance (default 1000, count exponent 1: the
+    published code's defaults as recalled; parity UNPINNED).  ``N != M`` is the formula as it stands.
+
+    Differentiable in both clouds, the counts held constant: K18 also writes ``d dcd / d d`` per point and the
+    backward is K1's deterministic one.  Bitwise the same on every run and independent of the batch;
+    ``dcd(p1, p2) == dcd(p2, p1)`` bitwise.  The call only enqueues (no host read): it can be captured in a graph.
+
+    ``return_info=True``: returns ``(dcd, info)`` with ``info["sides"] [B,2]`` (the two means), ``"deg1" [B,N]``,
+    ``"deg2" [B,M]`` (int32) and K1's ``"dist1"``, ``"dist2"``, ``"idx1"``, ``"idx2"`` (int32).
+
+    ``ValueError`` (before anything else) for bad shapes, empty clouds, more than 16384 points per cloud, and an
+    ``alpha`` that is negative or not finite.  No CPU path: CPU tensors raise ``FpsgHipError``."""
+    alpha = check_dcd_alpha(alpha)
+    for t in (p1, p2):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.size(2) != 3:
+            raise ValueError(f"expected [B,N,3] and [B,M,3] clouds, got {tuple(getattr(p1, 'shape', ()))} and "
+                             f"{tuple(getattr(p2, 'shape', ()))}")
+    if p1.size(0) != p2.size(0):
+        raise ValueError(f"batch mismatch: {p1.size(0)} vs {p2.size(0)}")
+    if p1.size(0) == 0 or p1.size(1) == 0 or p2.size(1) == 0:
+        raise ValueError(f"empty point clouds are not supported (got {tuple(p1.shape)} and {tuple(p2.shape)})")
+    if p1.size(1) > DCD_MAX_N or p2.size(1) > DCD_MAX_N:
+        raise ValueError(f"dcd supports at most {DCD_MAX_N} points per cloud, got {p1.size(1)} and {p2.size(1)}")
+    if p1.device != p2.device:
+        raise ValueError(f"device mismatch: {p1.device} vs {p2.device}")
+    info = {} if return_info else None
+    out = _Dcd.apply(p1, p2, alpha, info)
+    return (out, info) if return_info else out
+
+
 def softmin(x: torch.Tensor, y: torch.Tensor, h: torch.Tensor, eps: float) -> torch.Tensor:
     """``out[b,i] = -eps * logsumexp_j(h[b,j] - |x_i - y_j|^2 / (2 eps))`` (K2b), no grad."""
     _check_clouds(x, y)

@@ -351,6 +351,44 @@ int fpsg_fps(const float* xyz, int B, int N, int n, const int32_t* start, int32_
 int fpsg_dist_profile(const float* dist1, const float* dist2, int B, int N, int M, const float* tau2, int T,
                       int32_t* counts, float* maxima, fpsg_stream_t stream);
 
+/* ---- K18: density-aware Chamfer distance of cloud pairs -------------------------------------------
+ * DCD (Wu et al., NeurIPS 2021, "Density-aware Chamfer Distance as a Comprehensive Metric for Point Cloud
+ * Completion"): Chamfer's nearest-neighbour terms, bounded to [0, 1] by an exponential and divided by the number of
+ * queries that chose the same nearest neighbour.  The published package is not pinned; the definition below is the
+ * specification (parity UNPINNED).
+ * Inputs are K1's outputs for B pairs of clouds p1 [N,3], p2 [M,3]: dist1, idx1 [B,N] (squared distance to, and index
+ * in p2 of, the nearest point, lowest index on ties), dist2, idx2 [B,M] the same the other way.  Per pair:
+ *   deg2[j] = #{ i : idx1[i] == j }        int32 [M]   (how many points of p1 chose p2[j])
+ *   deg1[i] = #{ j : idx2[j] == i }        int32 [N]
+ *   q1[i]   = exp(-alpha * d1[i]) / float(deg2[idx1[i]])          (deg >= 1 there by construction)
+ *   q2[j]   = exp(-alpha * d2[j]) / float(deg1[idx2[j]])
+ *   side1   = (sum_i (1 - q1[i])) * (1/N)      side2 = (sum_j (1 - q2[j])) * (1/M)
+ *   dcd     = 0.5 * (side1 + side2)
+ *   w1[i]   = d dcd / d d1[i] = (alpha * q1[i]) * (0.5 * (1/N))    w2[j] likewise with 1/M   (counts held constant)
+ * alpha multiplies the SQUARED distance.  fp32 throughout: exp(-x) is the hardware base-2 exponential of
+ * -((alpha * d) * log2(e)), each product rounded (a result below 2^-126 is +0); the division is IEEE; 1/N and 1/M are
+ * rounded to fp32 first (as K1l).  The row sums use K1l's order: a row of terms is cut into blocks of 256 consecutive
+ * values (past the end: +0), inside a block each of the four groups of 64 is summed by the balanced binary tree over
+ * the position in the group, block = ((T0 + T1) + T2) + T3, and the blocks are added in ascending order from +0.
+ * Outputs, all overwritten: out [B]; sides [B,2] = (side1, side2); deg1 [B,N], deg2 [B,M] int32; w1 [B,N], w2 [B,M]
+ * fp32, each may be NULL (not wanted).
+ * Special values: an index outside [0, M) (idx1) or [0, N) (idx2) is counted nowhere, reads and writes no memory
+ * and gives q = 0 (term 1, weight 0) whatever its distance; a NaN distance with a valid index gives a NaN term and so
+ * a NaN side and dcd for its pair only.  The entry point is memory-safe on any int32 index input.
+ * Integer counts are exact; the float results are bitwise the same on every run, whatever B is and wherever the pair
+ * sits in the batch; the two sides go through one routine, so swapping (dist1, idx1, N) with (dist2, idx2, M) swaps
+ * sides, deg and w and leaves out bitwise unchanged.  One launch, one workgroup per pair, integer LDS atomics only,
+ * no workspace, no communication between workgroups.  The call only enqueues work on `stream` (no host read; it
+ * can be captured in a graph).
+ * Errors, all before any launch: FPSG_E_NULL for a null pointer other than w1 / w2; FPSG_E_SHAPE for B, N or M < 1;
+ * FPSG_E_LIMIT for N or M > FPSG_DCD_MAX_N (the in-degree histogram of one cloud lives in 64 KB of LDS); FPSG_E_ALIGN
+ * for a misaligned pointer.
+ */
+#define FPSG_DCD_MAX_N 16384
+int fpsg_dcd(const float* dist1, const int32_t* idx1, const float* dist2, const int32_t* idx2, int B, int N, int M,
+             float alpha, float* out, float* sides, int32_t* deg1, int32_t* deg2, float* w1, float* w2,
+             fpsg_stream_t stream);
+
 /* ---- K4b: fused EdgeConv (gather + BatchNorm statistics + max over k) -----------------
  * Replaces the chain get_graph_feature -> Conv2d 1x1 -> BatchNorm2d -> LeakyReLU -> max_k of
  * src/dgcnn/model.py:23-42,53-56,63-76 without materialising [B,2C,N,k].  The caller first
