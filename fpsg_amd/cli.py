@@ -28,6 +28,7 @@ import os
 import torch
 from torch.utils.data import DataLoader
 
+from . import eval_report
 from .episodes import EpisodicBatchSampler, SequentialBatchSampler, SyntheticFewShot
 
 
@@ -89,29 +90,7 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--sequential_eval", action="store_true")
     if evaluation:
         g.add_argument("--npy_folder", type=str, default="", help="Where draw_reconstruction dumps go;")
-        g.add_argument("--exact_emd", action="store_true",
-                       help="Also report the exact EMD per class (HIP auction, fpsg_amd.metrics.emd_exact);")
-        g.add_argument("--set_metrics", action="store_true",
-                       help="Also report MMD-CD, COV-CD and 1-NNA-CD per class over all its generated and reference "
-                            "query clouds (HIP Chamfer matrix, fpsg_amd.set_metrics);")
-        g.add_argument("--set_metrics_emd", action="store_true",
-                       help="Also report MMD-EMD, COV-EMD and 1-NNA-EMD per class over all its generated and reference "
-                            "query clouds (HIP exact EMD matrix, fpsg_amd.set_metrics);")
-        g.add_argument("--set_metrics_points", type=int, default=None, metavar="N",
-                       help="With --set_metrics / --set_metrics_emd: reduce every generated and reference query cloud to N "
-                            "points by farthest point sampling from index 0 (HIP, fpsg_amd.sampling) before the set metrics; "
-                            "the labels become MMD-CD@N, ...; every other column stays on the full clouds;")
-        g.add_argument("--jsd", action="store_true",
-                       help="Also report the Jensen-Shannon divergence per class between the voxel-occupancy distributions "
-                            "of its generated and reference query clouds (HIP occupancy grid, fpsg_amd.set_metrics.jsd);")
-        g.add_argument("--fscore", type=float, nargs="+", default=None, metavar="TAU",
-                       help="Also report per class the F-score of the reconstructions at these distances (1 to 16 of them; "
-                            "share of points within TAU of the other cloud, precision and recall combined) and the Hausdorff "
-                            "distance (HIP distance profile, fpsg_amd.metrics.fscore); TAU is a Euclidean distance in the "
-                            "clouds' units: the clouds are normalised into the unit ball, so 0.02 is 1 %% of its diameter;")
-        g.add_argument("--dcd", type=float, nargs="?", const=1000.0, default=None, metavar="ALPHA",
-                       help="Also report per class the density-aware Chamfer distance of the reconstructions (in [0, 1]; "
-                            "HIP, fpsg_amd.metrics.dcd); ALPHA is the factor on the squared distance [default: 1000];")
+        eval_report.add_arguments(g)
     return p
 
 
@@ -120,29 +99,8 @@ def validate(opt) -> None:
         raise SystemExit("--config_path and --test_path are required unless --synthetic is given")
     if opt.n_way != 1:
         raise SystemExit("only 1-way episodes are defined by the model (as in the reference)")
-    points = getattr(opt, "set_metrics_points", None)
-    if points is not None:
-        if not (getattr(opt, "set_metrics", False) or getattr(opt, "set_metrics_emd", False)):
-            raise SystemExit("--set_metrics_points needs --set_metrics and / or --set_metrics_emd")
-        if points < 1:
-            raise SystemExit(f"--set_metrics_points must be at least 1 (got {points})")
-    taus = getattr(opt, "fscore", None)
-    if taus is not None:
-        from .metrics import PROFILE_MAX_T, check_thresholds
-        if len(taus) > PROFILE_MAX_T:
-            raise SystemExit(f"--fscore takes at most {PROFILE_MAX_T} thresholds (got {len(taus)})")
-        try:
-            check_thresholds(taus)
-        except ValueError as e:
-            raise SystemExit(f"--fscore: {e}") from None
-    for flag in ("dcd_alpha", "dcd"):
-        alpha = getattr(opt, flag, None)
-        if alpha is not None:
-            from .metrics import check_dcd_alpha
-            try:
-                check_dcd_alpha(alpha)
-            except ValueError as e:
-                raise SystemExit(f"--{flag}: {e}") from None
+    eval_report.check_alpha_option(opt, "dcd_alpha")
+    eval_report.check(opt)          # the evaluation report's options; a training namespace has none of them
 
 
 def build_datasets(opt, n_query: int, device):

@@ -15,9 +15,10 @@ import torch
 import torch.optim as optim
 
 from . import dist as fdist
-from . import bn_counters, winograd
+from . import bn_counters, eval_report, winograd
 from .few_shot import ImgPCProtoNet
 from .image_net import ImageEncoderWarpper
+from .metrics import check_dcd_alpha, check_thresholds, nearest_rows
 from .optim import FlatAdam
 from .point_cloud_net import PCDecoder, PCEncoder
 
@@ -225,23 +226,14 @@ class EvalItem:
     their kernels, the filter bank registers the layers); capture happens on the third.  A model whose ``emd_metric`` /
     ``pc_metric`` were replaced (tests drive the module with the oracle's functions) takes the plain method.
 
-    ``exact_emd=True`` (``evaluate_Network.py --exact_emd``): every item also returns ``"exact_emd"``, the summed exact EMD
-    of its query clouds (``metrics.emd_exact``, K12), computed eagerly after the item -- after the replay on the same
-    ``syn_pc`` / ``ref_pc_q`` the graph produced, never inside a capture.
+    ``exact_emd=True``, ``fscore=(tau, ...)``, ``dcd=alpha``: the per-item parts of the report's column groups
+    (``eval_report.COLUMNS`` says what each adds to an item's result; bad values raise ``ValueError`` here).  They run
+    eagerly after the item -- after the replay, on the same ``syn_pc`` / ``ref_pc_q`` the graph produced, never inside a
+    capture -- and the groups that read K1's rows of those clouds share one ``metrics.nearest_rows`` call.
 
-    ``return_clouds=True`` (``evaluate_Network.py --set_metrics``): every item also returns ``"syn_pc"`` and
-    ``"ref_pc_q"``, the generated and reference query clouds, as clones: on the replay path they are the graph's static
-    output buffers, which the next replay overwrites.
-
-    ``fscore=(tau, ...)`` (``evaluate_Network.py --fscore``; 1 to 16 distances, ``metrics.check_thresholds``): every item
-    also returns ``"fscore"``, ``"precision"`` and ``"recall"``, float64 ``[T]``, the means over the item's query pairs of
-    ``metrics.fscore(syn_pc, ref_pc_q, thresholds)`` (generated against reference: K1's forward once more, then K17), and
-    ``"hausdorff"``, 0-dim, the mean of the pairs' Hausdorff distances -- computed like ``exact_emd``, eagerly after the
-    item on the clouds it holds, never inside a capture.
-
-    ``dcd=alpha`` (``evaluate_Network.py --dcd``; ``metrics.check_dcd_alpha``): every item also returns ``"dcd"``, 0-dim, the
-    mean over the item's query pairs of ``metrics.dcd(syn_pc, ref_pc_q, alpha)`` (K1's forward once more, then K18),
-    computed the same way, eagerly after the item.  ``None``: ``__call__`` stays on the branches it has."""
+    ``return_clouds=True``: every item also returns ``"syn_pc"`` and ``"ref_pc_q"``, the generated and reference query
+    clouds, as clones: on the replay path they are the graph's static output buffers, which the next replay overwrites.
+    Without any of these ``__call__`` returns what ``_item`` returns."""
 
     _KEYS = ("xs", "xq", "xad", "pcs", "pcq", "pcad")
 
@@ -250,14 +242,10 @@ class EvalItem:
         self.model = model
         self.exact_emd = bool(exact_emd)
         self.return_clouds = bool(return_clouds)
-        if fscore is not None:
-            from .metrics import check_thresholds
-            fscore = check_thresholds(fscore)
-        self.fscore = fscore
-        if dcd is not None:
-            from .metrics import check_dcd_alpha
-            dcd = check_dcd_alpha(dcd)
-        self.dcd = dcd
+        self.fscore = None if fscore is None else check_thresholds(fscore)
+        self.dcd = None if dcd is None else check_dcd_alpha(dcd)
+        self._columns = eval_report.item_columns(self.exact_emd, self.fscore, self.dcd)
+        self._needs_rows = any(c.needs_rows for c in self._columns)
         on_gpu = next(model.parameters()).is_cuda
         if graph is None:
             graph = os.environ.get("FPSG_EVAL_GRAPH", "1") != "0"
@@ -290,22 +278,14 @@ class EvalItem:
         return self.model.emd_metric is emd_wrapper and self.model.pc_metric is chamfer_distance
 
     def __call__(self, sample):
-        if not self.exact_emd and not self.return_clouds and self.fscore is None and self.dcd is None:
+        if not self._columns and not self.return_clouds:
             return self._item(sample)
         out = self._item(sample, clouds=True)
         syn_pc, ref_pc_q = out.pop("syn_pc"), out.pop("ref_pc_q")
-        if self.exact_emd:
-            from .metrics import emd_exact
-            out["exact_emd"] = emd_exact(syn_pc.contiguous(), ref_pc_q.contiguous()).sum()
-        if self.fscore is not None:
-            from .metrics import fscore
-            f = fscore(syn_pc.contiguous(), ref_pc_q.contiguous(), self.fscore)
-            for key in ("fscore", "precision", "recall"):
-                out[key] = f[key].mean(dim=0)
-            out["hausdorff"] = f["hausdorff"].mean()
-        if self.dcd is not None:
-            from .metrics import dcd
-            out["dcd"] = dcd(syn_pc.detach().contiguous(), ref_pc_q.detach().contiguous(), self.dcd).mean()
+        gen, ref = syn_pc.contiguous(), ref_pc_q.contiguous()
+        rows = nearest_rows(gen, ref) if self._needs_rows else None
+        for column in self._columns:
+            out.update(column.per_item(gen, ref, rows))
         if self.return_clouds:
             out["syn_pc"], out["ref_pc_q"] = syn_pc.clone(), ref_pc_q.clone()
         return out

@@ -216,10 +216,9 @@ class ImgPCProtoNet(nn.Module):
                 "support_rec_loss": loss_rec_s}
 
     # ---------------------------------------------------------------------- evaluation
-    def _reconstruct_for_eval(self, sample):
-        """The part of ``_return_reconstruction`` in front of the EMD: ``(syn_pc, ref_pc_q, cd_loss, diameter)`` with no host
-        read in it (``engine.EvalItem`` replays it as a hipGraph).  ``diameter`` (0-dim device tensor) is what the Sinkhorn
-        form's annealing schedule starts from -- ``metrics.sinkhorn_divergence`` would compute the same value itself."""
+    def _reconstruct_queries(self, sample):
+        """What both evaluation forms start with: ``(syn_pc, ref_pc_q, loss_rec_q)``, the generated and reference query
+        clouds of one test item (pruned or full encode, query decode) and their summed ``pc_metric``."""
         if self._eval_prune():
             img_zq, pc_z_proto = self._encode_for_eval(sample["xq"], sample["pcs"])
         else:
@@ -227,6 +226,13 @@ class ImgPCProtoNet(nn.Module):
         syn_pc = self._decode_queries(img_zq, pc_z_proto)
         ref_pc_q = sample["pcq"].squeeze(0).contiguous()
         loss_rec_q = self.pc_metric(syn_pc, ref_pc_q).sum()
+        return syn_pc, ref_pc_q, loss_rec_q
+
+    def _reconstruct_for_eval(self, sample):
+        """The part of ``_return_reconstruction`` in front of the EMD: ``(syn_pc, ref_pc_q, cd_loss, diameter)`` with no host
+        read in it (``engine.EvalItem`` replays it as a hipGraph).  ``diameter`` (0-dim device tensor) is what the Sinkhorn
+        form's annealing schedule starts from -- ``metrics.sinkhorn_divergence`` would compute the same value itself."""
+        syn_pc, ref_pc_q, loss_rec_q = self._reconstruct_queries(sample)
         pts = torch.cat([syn_pc.detach().reshape(-1, 3), ref_pc_q.reshape(-1, 3)])
         diameter = (pts.amax(0) - pts.amin(0)).norm()
         return syn_pc, ref_pc_q, self.query_factor * loss_rec_q, diameter
@@ -234,13 +240,7 @@ class ImgPCProtoNet(nn.Module):
     def _return_reconstruction(self, sample, return_clouds: bool = False):
         """``{"cd_loss", "emd_loss"}`` of one test item; ``return_clouds=True`` also returns the generated and reference
         query clouds (``"syn_pc"``, ``"ref_pc_q"``) the two were computed on."""
-        if self._eval_prune():
-            img_zq, pc_z_proto = self._encode_for_eval(sample["xq"], sample["pcs"])
-        else:
-            _, img_zq, pc_z_proto, _ = self._encode(sample["xs"], sample["xq"], sample["xad"], sample["pcs"], sample["pcad"])
-        syn_pc = self._decode_queries(img_zq, pc_z_proto)
-        ref_pc_q = sample["pcq"].squeeze(0).contiguous()
-        loss_rec_q = self.pc_metric(syn_pc, ref_pc_q).sum()
+        syn_pc, ref_pc_q, loss_rec_q = self._reconstruct_queries(sample)
         emd_loss = self.emd_metric(syn_pc, ref_pc_q).sum()
         if return_clouds:
             return {"cd_loss": self.query_factor * loss_rec_q, "emd_loss": emd_loss, "syn_pc": syn_pc,

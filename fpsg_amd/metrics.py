@@ -604,10 +604,24 @@ def fscore(p1: torch.Tensor, p2: torch.Tensor, thresholds) -> dict:
     of the reconstruction) and ``"fscore"``, float64 ``[B,T]``; ``"hausdorff" [B]`` float64, ``sqrt(max(maxima[:,0],
     maxima[:,1]))``; and K17's ``"counts"`` and ``"maxima"``.  Forward only; no CPU path."""
     taus = check_thresholds(thresholds)
+    return fscore_from_rows(nearest_rows(p1, p2), taus)
+
+
+def nearest_rows(p1: torch.Tensor, p2: torch.Tensor):
+    """K1's forward, detached and without autograd: ``(dist1 [B,N], dist2 [B,M], idx1, idx2)``, the squared
+    nearest-neighbour distances of ``chamfer_distance`` (bit for bit) and the int32 indices of the neighbours -- the rows
+    ``fscore_from_rows`` and ``dcd_from_rows`` read, so that a caller that wants both computes them once."""
     with torch.no_grad():
-        dist1, dist2, _, _ = _sided_forward(p1.detach(), p2.detach())
+        return _sided_forward(p1.detach(), p2.detach())
+
+
+def fscore_from_rows(rows, thresholds) -> dict:
+    """``fscore(p1, p2, thresholds)`` from ``rows = nearest_rows(p1, p2)``: K17 over the two distance rows, then
+    ``fscore_from_counts``.  ``ValueError`` as ``distance_profile`` (thresholds first, then the rows' shapes)."""
+    taus = check_thresholds(thresholds)
+    dist1, dist2 = rows[0], rows[1]
     counts, maxima = distance_profile(dist1, dist2, taus)
-    out = fscore_from_counts(counts, p1.size(1), p2.size(1))
+    out = fscore_from_counts(counts, dist1.size(1), dist2.size(1))
     out["hausdorff"] = maxima.to(torch.float64).amax(dim=1).sqrt()
     out["counts"], out["maxima"] = counts, maxima
     return out
@@ -646,6 +660,31 @@ def _dcd_from_rows(dist1, idx1, dist2, idx2, alpha, need1, need2):
                                   _hip.stream_of(dist1))
     _hip.check(rc, "fpsg_dcd")
     return out, sides, deg1, deg2, w1, w2
+
+
+def dcd_from_rows(rows, alpha: float = DCD_DEFAULT_ALPHA) -> torch.Tensor:
+    """``dcd(p1, p2, alpha)`` ``[B]`` from ``rows = nearest_rows(p1, p2)``: K18 without the weight rows, the value ``dcd``
+    returns when no input needs a gradient, bit for bit.  ``ValueError`` (before anything else) for a bad ``alpha``, rows
+    that are not ``[B,N]`` / ``[B,M]`` of one batch and one device, empty rows and more than 16384 entries per row."""
+    alpha = check_dcd_alpha(alpha)
+    dist1, dist2, idx1, idx2 = rows
+    for t, like in ((dist1, dist1), (dist2, dist2), (idx1, dist1), (idx2, dist2)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape != like.shape:
+            raise ValueError("expected K1's rows dist1 [B,N], dist2 [B,M], idx1 [B,N], idx2 [B,M], got "
+                             f"{[tuple(getattr(r, 'shape', ())) for r in rows]}")
+    if dist1.size(0) != dist2.size(0):
+        raise ValueError(f"batch mismatch: {dist1.size(0)} vs {dist2.size(0)}")
+    if dist1.numel() == 0 or dist2.numel() == 0:
+        raise ValueError(f"empty rows are not supported (got {tuple(dist1.shape)} and {tuple(dist2.shape)})")
+    if dist1.size(1) > DCD_MAX_N or dist2.size(1) > DCD_MAX_N:
+        raise ValueError(f"dcd supports at most {DCD_MAX_N} points per cloud, got {dist1.size(1)} and {dist2.size(1)}")
+    if len({t.device for t in rows}) != 1:
+        raise ValueError(f"device mismatch: {[str(t.device) for t in rows]}")
+    _hip.dev_tensor(dist1, torch.float32, "dist1")
+    _hip.dev_tensor(dist2, torch.float32, "dist2")
+    _hip.dev_tensor(idx1, torch.int32, "idx1")
+    _hip.dev_tensor(idx2, torch.int32, "idx2")
+    return _dcd_from_rows(dist1, idx1, dist2, idx2, alpha, False, False)[0]
 
 
 class _Dcd(torch.autograd.Function):
