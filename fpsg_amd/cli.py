@@ -17,7 +17,8 @@ exact EMD), ``--set_metrics_points N`` (evaluation: the clouds of the two set me
 point sampling, K16, and the labels marked ``@N``), ``--jsd`` (evaluation: the Jensen-Shannon divergence between the voxel-occupancy distributions of the class's
 generated and reference query clouds), ``--fscore TAU [TAU ...]`` (evaluation: the F-score of every reconstruction at
 those distances and the Hausdorff distance, per class), ``--pc_dist dcd`` with ``--dcd_alpha`` (training on the
-density-aware Chamfer distance, K18), ``--dcd [ALPHA]`` (evaluation: that distance per class).
+density-aware Chamfer distance, K18), ``--dcd [ALPHA]`` (evaluation: that distance per class), ``--pc_dist sinkhorn``
+with ``--sinkhorn_blur`` / ``--sinkhorn_diameter`` (training on the Sinkhorn divergence the evaluation prints as EMD, K19).
 """
 from __future__ import annotations
 
@@ -29,6 +30,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import eval_report
+from .metrics import SINKHORN_TRAIN_DIAMETER, check_sinkhorn_option
 from .episodes import EpisodicBatchSampler, SequentialBatchSampler, SyntheticFewShot
 
 
@@ -71,10 +73,18 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--lr", type=float, default=1e-3)
     g.add_argument("--lr_decay", type=float, default=350)
     g.add_argument("--resume", type=int, default=-1)
-    g.add_argument("--pc_dist", type=str, default="cd", choices=["cd", "emd", "dcd"])
+    g.add_argument("--pc_dist", type=str, default="cd", choices=["cd", "emd", "dcd", "sinkhorn"])
     g.add_argument("--dcd_alpha", type=float, default=1000.0,
                    help="With --pc_dist dcd: the factor on the squared nearest-neighbour distance inside the exponential "
                         "of the density-aware Chamfer distance [default: 1000];")
+    g.add_argument("--sinkhorn_blur", type=float, default=0.05,
+                   help="With --pc_dist sinkhorn: the blur of the Sinkhorn divergence, the annealing ends at blur^2 "
+                        "[default: 0.05, as the evaluation's EMD];")
+    g.add_argument("--sinkhorn_diameter", type=float, default=SINKHORN_TRAIN_DIAMETER,
+                   help="With --pc_dist sinkhorn: the FIXED diameter the annealing schedule starts from [default: 2*sqrt(3), "
+                        "the diagonal of [-1,1]^3].  The evaluation's EMD takes each item's own bounding-box diagonal "
+                        "instead, so its value differs slightly (under 1 %% on unit-ball clouds); a fixed one keeps the "
+                        "training step free of host reads;")
     g.add_argument("--SGD", action="store_true")
     g.add_argument("--episodes_per_step", type=int, default=0,
                    help="Episodes per optimizer step over all ranks [default: one per rank];")
@@ -100,6 +110,12 @@ def validate(opt) -> None:
     if opt.n_way != 1:
         raise SystemExit("only 1-way episodes are defined by the model (as in the reference)")
     eval_report.check_alpha_option(opt, "dcd_alpha")
+    for flag in ("sinkhorn_blur", "sinkhorn_diameter"):
+        if getattr(opt, flag, None) is not None:
+            try:
+                check_sinkhorn_option(getattr(opt, flag), flag)
+            except ValueError as e:
+                raise SystemExit(f"--{e}") from None
     eval_report.check(opt)          # the evaluation report's options; a training namespace has none of them
 
 

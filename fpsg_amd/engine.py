@@ -18,7 +18,7 @@ from . import dist as fdist
 from . import bn_counters, eval_report, winograd
 from .few_shot import ImgPCProtoNet
 from .image_net import ImageEncoderWarpper
-from .metrics import check_dcd_alpha, check_thresholds, nearest_rows
+from .metrics import SINKHORN_TRAIN_DIAMETER, check_dcd_alpha, check_thresholds, nearest_rows
 from .optim import FlatAdam
 from .point_cloud_net import PCDecoder, PCEncoder
 
@@ -49,7 +49,9 @@ def build_model(opt) -> ImgPCProtoNet:
     return ImgPCProtoNet(img_encoder, pc_encoder, pc_decoder, mask_learner=None,
                          query_factor=opt.query_factor, support_factor=opt.support_factor,
                          metric=getattr(opt, "pc_dist", "cd"), intra_support=opt.intra_recon,
-                         aggregate=opt.aggregate, dcd_alpha=getattr(opt, "dcd_alpha", 1000.0))
+                         aggregate=opt.aggregate, dcd_alpha=getattr(opt, "dcd_alpha", 1000.0),
+                         sinkhorn_blur=getattr(opt, "sinkhorn_blur", 0.05),
+                         sinkhorn_diameter=getattr(opt, "sinkhorn_diameter", SINKHORN_TRAIN_DIAMETER))
 
 
 def build_optimizer(model, opt):

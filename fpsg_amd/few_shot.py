@@ -19,7 +19,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .metrics import chamfer_distance, check_dcd_alpha, dcd, emd_loss, episode_chamfer_losses
+from .metrics import (SINKHORN_TRAIN_DIAMETER, chamfer_distance, check_dcd_alpha, check_sinkhorn_option, dcd, emd_loss,
+                      episode_chamfer_losses, sinkhorn_loss)
 from .utils import emd_wrapper
 
 _AGGREGATOR = ["single", "multi", "mask_single", "mask_multi"]
@@ -60,7 +61,8 @@ def _split_rows(t, n):
 
 class ImgPCProtoNet(nn.Module):
     def __init__(self, img_encoder, pc_encoder, pc_decoder, mask_learner=None, query_factor=1.0,
-                 support_factor=1.0, metric="cd", intra_support=False, aggregate="single", dcd_alpha=1000.0):
+                 support_factor=1.0, metric="cd", intra_support=False, aggregate="single", dcd_alpha=1000.0,
+                 sinkhorn_blur=0.05, sinkhorn_diameter=SINKHORN_TRAIN_DIAMETER):
         super().__init__()
         self.img_encoder = img_encoder
         self.pc_encoder = pc_encoder
@@ -82,18 +84,27 @@ class ImgPCProtoNet(nn.Module):
             # the density-aware Chamfer distance (K18) per pair, in [0, 1]; alpha multiplies the squared distance
             self.dcd_alpha = check_dcd_alpha(dcd_alpha)
             self.pc_metric = self._dcd_metric
+        elif metric == "sinkhorn":
+            # the Sinkhorn divergence the evaluation prints as EMD, with geomloss's gradient (K19).  The schedule starts
+            # from a FIXED diameter (the evaluation's is per item): no host read, so the step can be captured
+            self.sinkhorn_blur = check_sinkhorn_option(sinkhorn_blur, "sinkhorn_blur")
+            self.sinkhorn_diameter = check_sinkhorn_option(sinkhorn_diameter, "sinkhorn_diameter")
+            self.pc_metric = self._sinkhorn_metric
         else:
             raise NotImplementedError(
                 f"Found unsupported point cloud reconstruction metrics: {metric}")
         # evaluation-only distance (reference few_shot.py:168); an attribute so that a test
         # can drive the module on CPU with the oracle's implementations
         self.emd_metric = emd_wrapper
-        self._dcd = metric == "dcd"
+        self._batched_pairs = metric in ("dcd", "sinkhorn")      # one call over the Q + S pairs (below)
         self.overlap_encoders = False      # see _encode; switched on by bench.py / the trainer
         self._side_stream = None
 
     def _dcd_metric(self, a, b):
         return dcd(a, b, self.dcd_alpha)
+
+    def _sinkhorn_metric(self, a, b):
+        return sinkhorn_loss(a, b, blur=self.sinkhorn_blur, diameter=self.sinkhorn_diameter)
 
     # ------------------------------------------------------------------ shared forward
     def _encode(self, img_s, img_q, img_ad, pc_s, pc_ad):
@@ -197,9 +208,9 @@ class ImgPCProtoNet(nn.Module):
                             "support_rec_loss": loss_rec_s}
                 cd = self.pc_metric(syn, ref)
                 loss_rec_q, loss_rec_s = cd[:n_q].sum(), cd[n_q:].sum()
-            elif self._dcd and syn_q.shape[1:] == syn_s.shape[1:] and ref_q.shape[1:] == ref_s.shape[1:]:
-                # as the Chamfer branch: ONE K1 + K18 call over the Q + S pairs (a pair's value does not depend on the
-                # batch, so this is only fewer launches); the fused K1l sums are Chamfer's alone
+            elif self._batched_pairs and syn_q.shape[1:] == syn_s.shape[1:] and ref_q.shape[1:] == ref_s.shape[1:]:
+                # as the Chamfer branch: ONE K1 + K18 (or K2b + K19, fixed diameter) call over the Q + S pairs (a pair's
+                # value does not depend on the batch, so this is only fewer launches); the fused K1l sums are Chamfer's alone
                 if syn is None:
                     syn = torch.cat([syn_q, syn_s])
                 d = self.pc_metric(syn, torch.cat([ref_q, ref_s]))

@@ -773,7 +773,8 @@ def sinkhorn_divergence(p1: torch.Tensor, p2: torch.Tensor, blur: float = 0.05, 
     defaults (p=2, blur=.05, scaling=.5, debias): the symmetric Sinkhorn loop annealed over
     ``eps = diameter^2, ..., blur^2``, four soft-mins (K2b) per step, no [B,N,M] tensor.
 
-    Forward value only (the reference uses it in evaluation, ``few_shot.py:168``); the geomloss
+    Forward value only (the reference uses it in evaluation, ``few_shot.py:168``; ``sinkhorn_loss`` is the differentiable
+    form, same bits); the geomloss
     package is absent from the reference tree and unpinned, so parity is UNPINNED."""
     _check_clouds(p1, p2)
     B, N, _ = p1.shape
@@ -795,6 +796,74 @@ def sinkhorn_divergence(p1: torch.Tensor, p2: torch.Tensor, blur: float = 0.05, 
                                           _hip.ptr(ws), _hip.stream_of(x))
     _hip.check(rc, "fpsg_sinkhorn_divergence")
     return out
+
+
+SINKHORN_TRAIN_DIAMETER = 2.0 * math.sqrt(3.0)      # the diagonal of [-1, 1]^3: tanh outputs and unit-ball references
+
+
+def check_sinkhorn_option(value, name: str) -> float:
+    """``blur`` / ``diameter`` of ``sinkhorn_loss`` as a Python float: a finite number > 0 (``ValueError`` naming the
+    option otherwise)."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number, got {value!r}") from None
+    if not (math.isfinite(v) and v > 0.0):
+        raise ValueError(f"{name} must be finite and positive, got {value!r}")
+    return v
+
+
+class _SinkhornLoss(torch.autograd.Function):
+    """K2b's loop with K19 as its last launch: the divergence ``[B]`` and, for the inputs that need them, its
+    gradients (duals, summed clouds and schedule held constant), cached for the backward."""
+
+    @staticmethod
+    def forward(ctx, p1, p2, eps_s):
+        import ctypes
+        B, N, _ = p1.shape
+        M = p2.size(1)
+        lib = _hip.load()
+        dev = p1.device
+        need1, need2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        eps_arr = (ctypes.c_float * len(eps_s))(*eps_s)
+        out = torch.empty((B,), dtype=torch.float32, device=dev)
+        g1 = torch.empty_like(p1) if need1 else None
+        g2 = torch.empty_like(p2) if need2 else None
+        ws = torch.empty((lib.fpsg_sinkhorn_grad_workspace_floats(B, N, M),), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev), _probe("sinkhorn_grad", B, N, M):
+            rc = lib.fpsg_sinkhorn_divergence_grad(_hip.ptr(p1), _hip.ptr(p2), B, N, M, eps_arr, len(eps_s),
+                                                   _hip.ptr(out), _hip.ptr(g1) if need1 else None,
+                                                   _hip.ptr(g2) if need2 else None, _hip.ptr(ws), _hip.stream_of(p1))
+        _hip.check(rc, "fpsg_sinkhorn_divergence_grad")
+        ctx.grads = (g1, g2)
+        return out
+
+    @staticmethod
+    def backward(ctx, gcost):
+        g1, g2 = ctx.grads
+        gc = gcost.reshape(-1, 1, 1)
+        return (None if g1 is None else g1 * gc), (None if g2 is None else g2 * gc), None
+
+
+def sinkhorn_loss(p1: torch.Tensor, p2: torch.Tensor, blur: float = 0.05, scaling: float = 0.5,
+                  diameter: float | None = None) -> torch.Tensor:
+    """``sinkhorn_divergence(p1, p2, blur, scaling, diameter)`` ``[B]``, bit for bit, as a differentiable loss: what
+    ``geomloss.SamplesLoss()`` gives a training loop.  The gradient is geomloss's (K19, ``include/fpsg_hip.h``): the
+    derivative of the final extrapolation with the duals, the summed clouds and the schedule held constant -- not a
+    backward pass through the annealing loop -- formed in the call's last launch for the inputs that require grad.
+    Bitwise reproducible; ``sinkhorn_loss(x, x.clone())`` has an exactly zero gradient.
+
+    ``diameter=None``: geomloss's rule, the bounding-box diagonal of all points (one host read: not capturable).
+    A float fixes the schedule: the call only enqueues and can be captured in a graph.  No gradient flows through
+    the diameter either way.  Parity with the geomloss package is UNPINNED."""
+    _check_clouds(p1, p2)
+    blur = check_sinkhorn_option(blur, "blur")
+    if diameter is None:     # one host sync; pass `diameter` to stay asynchronous
+        pts = torch.cat([p1.detach().reshape(-1, 3), p2.detach().reshape(-1, 3)])
+        diameter = float((pts.amax(0) - pts.amin(0)).norm())
+    else:
+        diameter = check_sinkhorn_option(diameter, "diameter")
+    return _SinkhornLoss.apply(p1, p2, sinkhorn_epsilons(diameter, blur, scaling))
 
 
 def sinkhorn_epsilons(diameter: float, blur: float = 0.05, scaling: float = 0.5):

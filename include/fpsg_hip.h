@@ -475,6 +475,33 @@ int fpsg_sinkhorn_divergence(const float* x, const float* y, int B, int N, int M
                              const float* eps_host, int n_eps, float* out, float* ws,
                              fpsg_stream_t stream);
 
+/* ---- K19: the gradient of that divergence --------------------------------------------
+ * What geomloss.SamplesLoss("sinkhorn") returns from backward(): NOT a backward pass through the loop.  geomloss runs
+ * the annealing loop without autograd and then evaluates the final extrapolation with autograd on and three things
+ * held as constants: the duals, the summed cloud of every soft-min, and the diameter with its schedule.  With
+ * C(u,v) = |u-v|^2 / 2, e = eps[n_eps-1], (a_x, b_x, a_y, b_y) the duals in front of the final extrapolation and
+ * w_ij = softmax_j( h_j - C(x_i, y_j) / e ):
+ *   d out[b] / d x_i = ( D_xx(i) - D_xy(i) ) / N
+ *       D_xy(i) = sum_j w_ij (y_j - x_i),  h_j = -log M + a_y[j] / e    (the weights of  b_x <- softmin over y)
+ *       D_xx(i) = sum_k w_ik (x_k - x_i),  h_k = -log N + a_x[k] / e    (the weights of  a_x <- softmin over x)
+ *   d out[b] / d y_j = ( D_yy(j) - D_yx(j) ) / M
+ *       D_yx(j): owners y, summed cloud x, h_i = -log N + b_x[i] / e
+ *       D_yy(j): owners y, summed cloud y, h_l = -log M + b_y[l] / e
+ * -- each from the same soft-min, over the same summed cloud and the same h, as the final extrapolation evaluates.
+ * The last launch of the call is that extrapolation with three more running sums per owner (the displacements
+ * y_j - x_i, not barycentres: at e = blur^2 the xx weights sit on the point itself); one small launch forms the two
+ * differences.  No [B,N,M] tensor, no atomics: bitwise reproducible, and the gradient of out(x, x) is exactly 0.
+ *
+ * out [B]: bit-identical to fpsg_sinkhorn_divergence for the same inputs and schedule.  gx [B,N,3], gy [B,M,3]: either
+ * may be NULL, and its two soft-mins then skip the displacement sums.  ws: fpsg_sinkhorn_grad_workspace_floats(B,N,M)
+ * device floats.  Argument checks, error codes and limits as fpsg_sinkhorn_divergence (FPSG_E_ALIGN for a misaligned
+ * gx / gy).  n_eps + 4 launches; only enqueues (eps_host is read at call time: capturable in a graph). */
+size_t fpsg_sinkhorn_grad_workspace_floats(int B, int N, int M);
+int fpsg_sinkhorn_divergence_grad(const float* x, const float* y, int B, int N, int M,
+                                  const float* eps_host, int n_eps, float* out,
+                                  float* gx /*[B,N,3] or NULL*/, float* gy /*[B,M,3] or NULL*/,
+                                  float* ws, fpsg_stream_t stream);
+
 /* ---- K9: first layer of the decoder's patch MLPs ------------------------------------------
  * Replaces, per decode, the 16 x [conv1 (1539 -> 1539, 1x1) + BatchNorm1d + ReLU] of
  * PrimitiveNode.forward (src/models/point_cloud_net.py:76-80) applied to cat(x.repeat, patch points)
