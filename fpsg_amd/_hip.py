@@ -167,6 +167,17 @@ SIGNATURES = {
     "fpsg_adam_step_segments": [_c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_f32p, _c_f32p, ctypes.c_size_t,
                                 ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int, ctypes.c_float,
                                 _c_stream],
+    "fpsg_grad_norm_workspace_bytes": [ctypes.c_size_t],
+    "fpsg_grad_clip_scale": [_c_f32p, ctypes.c_size_t, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t,
+                             _c_f32p, ctypes.c_void_p, _c_stream],
+    "fpsg_grad_clip_scale_segments": [ctypes.c_void_p, ctypes.c_void_p, _c_int, ctypes.c_size_t, ctypes.c_float,
+                                      ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, _c_f32p, ctypes.c_void_p,
+                                      _c_stream],
+    "fpsg_adam_step_dscale": [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_size_t, ctypes.c_float, ctypes.c_float,
+                              ctypes.c_float, ctypes.c_float, _c_int, _c_f32p, _c_stream],
+    "fpsg_adam_step_segments_dscale": [_c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_f32p, _c_f32p,
+                                       ctypes.c_size_t, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                       _c_int, _c_f32p, _c_stream],
     "fpsg_gemm_split_workspace_floats": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int],
     "fpsg_gemm_split": [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_long,
                         ctypes.c_long, ctypes.c_long, _c_int, _c_int, _c_f32p, ctypes.c_size_t, _c_stream],
@@ -199,7 +210,8 @@ SIGNATURES = {
     "fpsg_dcd": [_c_f32p, _c_i32p, _c_f32p, _c_i32p, _c_int, _c_int, _c_int, ctypes.c_float, _c_f32p, _c_f32p, _c_i32p,
                  _c_i32p, _c_f32p, _c_f32p, _c_stream],
 }
-_RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_chamfer_workspace_bytes": ctypes.c_size_t,
+_RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_grad_norm_workspace_bytes": ctypes.c_size_t,
+"fpsg_chamfer_workspace_bytes": ctypes.c_size_t,
              "fpsg_sinkhorn_workspace_floats": ctypes.c_size_t,
              "fpsg_sinkhorn_grad_workspace_floats": ctypes.c_size_t,
              "fpsg_knn_workspace_floats": ctypes.c_size_t,

@@ -18,7 +18,8 @@ point sampling, K16, and the labels marked ``@N``), ``--jsd`` (evaluation: the J
 generated and reference query clouds), ``--fscore TAU [TAU ...]`` (evaluation: the F-score of every reconstruction at
 those distances and the Hausdorff distance, per class), ``--pc_dist dcd`` with ``--dcd_alpha`` (training on the
 density-aware Chamfer distance, K18), ``--dcd [ALPHA]`` (evaluation: that distance per class), ``--pc_dist sinkhorn``
-with ``--sinkhorn_blur`` / ``--sinkhorn_diameter`` (training on the Sinkhorn divergence the evaluation prints as EMD, K19).
+with ``--sinkhorn_blur`` / ``--sinkhorn_diameter`` (training on the Sinkhorn divergence the evaluation prints as EMD, K19),
+``--clip_grad_norm X`` (training: the 2-norm of every step's mean gradient clipped to X, K20, and one extra line per epoch).
 """
 from __future__ import annotations
 
@@ -32,6 +33,16 @@ from torch.utils.data import DataLoader
 from . import eval_report
 from .metrics import SINKHORN_TRAIN_DIAMETER, check_sinkhorn_option
 from .episodes import EpisodicBatchSampler, SequentialBatchSampler, SyntheticFewShot
+
+
+def _clip_norm(text: str) -> float:
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"a non-negative number, got {text!r}") from None
+    if value != value or value < 0:
+        raise argparse.ArgumentTypeError(f"a non-negative number, got {text!r}")
+    return value
 
 
 def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
@@ -85,6 +96,9 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
                         "the diagonal of [-1,1]^3].  The evaluation's EMD takes each item's own bounding-box diagonal "
                         "instead, so its value differs slightly (under 1 %% on unit-ball clouds); a fixed one keeps the "
                         "training step free of host reads;")
+    g.add_argument("--clip_grad_norm", type=_clip_norm, default=0.0, metavar="X",
+                   help="Clip the 2-norm of every optimizer step's mean gradient to X [default: 0 = off]; prints the "
+                        "largest norm and the number of clipped steps after every epoch;")
     g.add_argument("--SGD", action="store_true")
     g.add_argument("--episodes_per_step", type=int, default=0,
                    help="Episodes per optimizer step over all ranks [default: one per rank];")

@@ -38,10 +38,18 @@ __device__ __forceinline__ void st4(float* p, size_t i, v4f v) {
 #endif
 }
 
+// Where the factor on the gradient comes from: the kernel argument (K7's entry points), or one float in device memory
+// that an earlier launch on the stream wrote (K20: grad_scale times the clip coefficient; a uniform address, so one
+// scalar load per wave).  The arithmetic behind it is the same instruction for instruction.
+__device__ __forceinline__ float scale_of(float s) { return s; }
+__device__ __forceinline__ float scale_of(const float* s) { return *s; }
+
+template <typename Scale>
 __global__ __launch_bounds__(kAdamThreads) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                             float* __restrict__ m, float* __restrict__ v, size_t n4,
                                                             size_t n, float step_size, float b1, float b2, float eps,
-                                                            float inv_sqrt_bc2, float gscale) {
+                                                            float inv_sqrt_bc2, Scale gscale_src) {
+  const float gscale = scale_of(gscale_src);
   const size_t stride = (size_t)gridDim.x * kAdamThreads;
   const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
   auto update = [&](v4f& pv, const v4f& gv, v4f& mv, v4f& vv) {
@@ -326,11 +334,13 @@ __global__ __launch_bounds__(kAdamThreads) void flat_accumulate_tables_kernel(fl
   }
 }
 
+template <typename Scale>
 __global__ __launch_bounds__(kAdamThreads) void adam_ptr_kernel(float* __restrict__ p, const float* const* __restrict__ gtab,
                                                                 const long long* __restrict__ seg_off, int nseg,
                                                                 float* __restrict__ m, float* __restrict__ v, size_t n4,
                                                                 size_t n, float step_size, float b1, float b2,
-                                                                float eps, float inv_sqrt_bc2, float gscale) {
+                                                                float eps, float inv_sqrt_bc2, Scale gscale_src) {
+  const float gscale = scale_of(gscale_src);
   const size_t stride = (size_t)gridDim.x * kAdamThreads;
   const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
   size_t j = (size_t)blockIdx.x * kAdamThreads + threadIdx.x;
@@ -402,50 +412,131 @@ __global__ __launch_bounds__(kAdamThreads) void adam_ptr_kernel(float* __restric
   }
 }
 
-}  // namespace
-}  // namespace fpsg
+// ---- K20: the norm of the step's gradient and the clip coefficient, folded into K7's factor ------------------------
+// One read of the gradient (4 B per parameter) for the sum of squares in fp64, one small finalize launch; the Adam
+// step then takes grad_scale * coef from device memory (scale_of above): no host read, no pass that rewrites the
+// gradient.  The order of every add depends on n alone -- not on the device, the stream or the run -- and is the same
+// for the flat and the pointer-table form: the same bits from the same values (include/fpsg_hip.h pins it).
+constexpr int kNormBlocksMax = 256 * 16;     // the grid cap of flat_accumulate_kernel; also the most partial sums
+constexpr int kNormU = 4;                    // vectors per trip: 16-byte loads in flight per thread
 
-extern "C" int fpsg_adam_step_segments(float* param, const float* const* grad_ptrs, const long long* seg_off, int nseg,
-                                       float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
-                                       float eps, int step, float grad_scale, fpsg_stream_t stream) {
-  using namespace fpsg;
-  FPSG_REQUIRE(n > 0 && step >= 1 && nseg > 0, FPSG_E_SHAPE,
-               "fpsg_adam_step_segments: n, nseg must be positive and step >= 1 (got %zu, %d, %d)", n, nseg, step);
-  FPSG_REQUIRE(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f && eps >= 0.0f, FPSG_E_SHAPE,
-               "fpsg_adam_step_segments: betas must lie in [0,1) and eps be non-negative");
-  FPSG_REQUIRE_PTR(param); FPSG_REQUIRE_PTR(exp_avg); FPSG_REQUIRE_PTR(exp_avg_sq);
-  FPSG_REQUIRE(grad_ptrs != nullptr && seg_off != nullptr, FPSG_E_NULL, "fpsg_adam_step_segments: null table");
-  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(exp_avg) |
-                 reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0,
-               FPSG_E_ALIGN, "fpsg_adam_step_segments: param, exp_avg and exp_avg_sq must be 16-byte aligned");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  const size_t n4 = n / 4;
-  size_t blocks = (n4 + 1 + kAdamThreads - 1) / kAdamThreads;
-  // no grid-stride cap, as adam_kernel (c3 same box, three alternating pairs: 43.99-44.01 -> 44.01-44.14 episodes/s)
-  hipLaunchKernelGGL(adam_ptr_kernel, dim3((unsigned)blocks), dim3(kAdamThreads), 0, static_cast<hipStream_t>(stream),
-                     param, grad_ptrs, seg_off, nseg, exp_avg, exp_avg_sq, n4, n, step_size, beta1, beta2, eps,
-                     inv_sqrt_bc2, grad_scale);
-  return launch_status("fpsg_adam_step_segments");
+inline size_t grad_norm_blocks(size_t n) {
+  if (n == 0) return 0;
+  const size_t blocks = (n / 4 + 1 + kAdamThreads - 1) / kAdamThreads;
+  return blocks > (size_t)kNormBlocksMax ? (size_t)kNormBlocksMax : blocks;
 }
 
-extern "C" int fpsg_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
-                              float beta1, float beta2, float eps, int step, float grad_scale, fpsg_stream_t stream) {
-  using namespace fpsg;
-  FPSG_REQUIRE(n > 0 && step >= 1, FPSG_E_SHAPE, "fpsg_adam_step: n must be positive and step >= 1 (got %zu, %d)", n, step);
-  FPSG_REQUIRE(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f && eps >= 0.0f, FPSG_E_SHAPE,
-               "fpsg_adam_step: betas must lie in [0,1) and eps be non-negative");
-  FPSG_REQUIRE_PTR(param); FPSG_REQUIRE_PTR(grad); FPSG_REQUIRE_PTR(exp_avg); FPSG_REQUIRE_PTR(exp_avg_sq);
-  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
-                 reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0,
-               FPSG_E_ALIGN, "fpsg_adam_step: the four buffers must be 16-byte aligned");
-  // bias corrections in double, as torch does for python-scalar steps
+template <int M>
+__device__ __forceinline__ double lane_xor_f64(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  const unsigned lo = lane_xor<M>((unsigned)b), hi = lane_xor<M>((unsigned)(b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// wave_sum of fpsg_common.h on a double: the same fixed butterfly, the two halves exchanged separately
+__device__ __forceinline__ double wave_sum_f64(double v) {
+  v += lane_xor_f64<1>(v);
+  v += lane_xor_f64<2>(v);
+  v += lane_xor_f64<4>(v);
+  v += lane_xor_f64<8>(v);
+  v += lane_xor_f64<16>(v);
+  v += lane_xor_f64<32>(v);
+  return v;
+}
+
+// Vector slot j holds the flat positions 4j .. 4j+3 (slot n/4: the n % 4 tail, the rest of it zeros).  Thread t of the
+// grid takes the slots t, t + T, t + 2T, ... (T threads in the grid) in that order; element e of every slot goes into
+// the thread's accumulator e, a_e = fma(g, g, a_e) in fp64 (the square of an fp32 value is exact there).  Then
+// (a_0 + a_1) + (a_2 + a_3), the butterfly over the wave, ((w_0 + w_1) + (w_2 + w_3)) over the workgroup's four waves,
+// and one plain store per workgroup.  SEG: the gradient through the pointer table of adam_ptr_kernel (null = zeros,
+// which add +0.0: the same bits as the flat form on the gathered values).
+template <bool SEG>
+__global__ __launch_bounds__(kAdamThreads) void grad_sqnorm_kernel(const float* __restrict__ g,
+                                                                   const float* const* __restrict__ gtab,
+                                                                   const long long* __restrict__ seg_off, int nseg,
+                                                                   size_t n4, size_t n, double* __restrict__ partial) {
+  const size_t stride = (size_t)gridDim.x * kAdamThreads;
+  size_t j = (size_t)blockIdx.x * kAdamThreads + threadIdx.x;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  auto add = [&](const float (&q)[4]) {
+    a0 = __builtin_fma((double)q[0], (double)q[0], a0);
+    a1 = __builtin_fma((double)q[1], (double)q[1], a1);
+    a2 = __builtin_fma((double)q[2], (double)q[2], a2);
+    a3 = __builtin_fma((double)q[3], (double)q[3], a3);
+  };
+  for (; j + (kNormU - 1) * stride < n4; j += kNormU * stride) {
+    float q[kNormU][4];
+#pragma unroll
+    for (int u = 0; u < kNormU; ++u) {
+      if constexpr (SEG) {
+        gather_grad4_wave(gtab, seg_off, nseg, (long long)(4 * (j + u * stride)), q[u]);
+      } else {
+        const v4f t = reinterpret_cast<const v4f*>(g)[j + u * stride];
+        q[u][0] = t[0]; q[u][1] = t[1]; q[u][2] = t[2]; q[u][3] = t[3];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kNormU; ++u) add(q[u]);
+  }
+  for (; j < n4 + 1; j += stride) {
+    const int cnt = j < n4 ? 4 : (int)(n - 4 * n4);          // the last slot is the tail
+    if (cnt == 0) break;
+    float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (SEG) {
+      gather_grad4(gtab, seg_off, nseg, (long long)(4 * j), cnt, q);
+    } else if (cnt == 4) {
+      const v4f t = reinterpret_cast<const v4f*>(g)[j];
+      q[0] = t[0]; q[1] = t[1]; q[2] = t[2]; q[3] = t[3];
+    } else {
+      for (int u = 0; u < cnt; ++u) q[u] = g[4 * j + u];
+    }
+    add(q);
+  }
+  const double w = wave_sum_f64((a0 + a1) + (a2 + a3));
+  __shared__ double waves[kAdamThreads / kWave];
+  if ((threadIdx.x & (kWave - 1)) == 0) waves[threadIdx.x / kWave] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (waves[0] + waves[1]) + (waves[2] + waves[3]);
+}
+
+// One workgroup: the partial sums into LDS, then ONE thread adds them in ascending index order from +0.0 (a ticket in
+// the kernel above would save this launch and cost more, DESIGN K1l) and writes the norm, the factor and the counters.
+__global__ __launch_bounds__(kAdamThreads) void grad_clip_finalize_kernel(const double* __restrict__ partial, int nparts,
+                                                                          float grad_scale, float max_norm,
+                                                                          float* __restrict__ out2,
+                                                                          double* __restrict__ stats) {
+  __shared__ double part[kNormBlocksMax];
+  for (int e = threadIdx.x; e < nparts; e += kAdamThreads) part[e] = partial[e];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double S = 0.0;
+  for (int e = 0; e < nparts; ++e) S += part[e];
+  const float norm = (float)(__builtin_fabs((double)grad_scale) * __builtin_sqrt(S));
+  // torch.nn.utils.clip_grad_norm_(error_if_nonfinite=False): clamp(max_norm / (norm + 1e-6), max=1.0) keeps a NaN
+  const float x = max_norm / (norm + 1e-6f);
+  const float coef = (x < 1.0f || x != x) ? x : 1.0f;
+  out2[0] = norm;
+  out2[1] = grad_scale * coef;
+  if (stats) {
+    stats[0] += 1.0;
+    if (coef < 1.0f) stats[1] += 1.0;
+    if (!__builtin_isfinite(norm)) stats[2] += 1.0;
+    else if ((double)norm > stats[3]) stats[3] = (double)norm;
+  }
+}
+
+// hyper-parameters of a step as the kernels take them (bias corrections in double, as torch does for python-scalar steps)
+struct AdamConsts { float step_size, inv_sqrt_bc2; };
+inline AdamConsts adam_consts(float lr, float beta1, float beta2, int step) {
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  return {(float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
+}
+
+template <typename Scale>
+int launch_adam(const char* what, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
+                float beta1, float beta2, float eps, int step, Scale scale, fpsg_stream_t stream) {
+  const AdamConsts c = adam_consts(lr, beta1, beta2, step);
   const size_t n4 = n / 4;
   size_t blocks = (n4 + kAdamThreads - 1) / kAdamThreads;
   // One vector per thread, no grid-stride cap (round 4): rounds 2-3 launched 16 workgroups per CU walking the buffers with a
@@ -453,9 +544,137 @@ extern "C" int fpsg_adam_step(float* param, const float* grad, float* exp_avg, f
   // this one 356-389 us for the model's 77.4 M parameters (0.59 -> 0.64-0.75 of the HBM peak) -- a workgroup's 4 KB pieces of
   // the seven streams stay next to its neighbours' in time, whatever the residency.  (2 / 4 vectors per thread: 361-408 us.)
   if (blocks == 0) blocks = 1;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(kAdamThreads), 0, static_cast<hipStream_t>(stream), param,
-                     grad, exp_avg, exp_avg_sq, n4, n, step_size, beta1, beta2, eps, inv_sqrt_bc2, grad_scale);
-  return launch_status("fpsg_adam_step");
+  hipLaunchKernelGGL((adam_kernel<Scale>), dim3((unsigned)blocks), dim3(kAdamThreads), 0, static_cast<hipStream_t>(stream),
+                     param, grad, exp_avg, exp_avg_sq, n4, n, c.step_size, beta1, beta2, eps, c.inv_sqrt_bc2, scale);
+  return launch_status(what);
+}
+
+template <typename Scale>
+int launch_adam_segments(const char* what, float* param, const float* const* grad_ptrs, const long long* seg_off, int nseg,
+                         float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2, float eps,
+                         int step, Scale scale, fpsg_stream_t stream) {
+  const AdamConsts c = adam_consts(lr, beta1, beta2, step);
+  const size_t n4 = n / 4;
+  size_t blocks = (n4 + 1 + kAdamThreads - 1) / kAdamThreads;
+  // no grid-stride cap, as adam_kernel (c3 same box, three alternating pairs: 43.99-44.01 -> 44.01-44.14 episodes/s)
+  hipLaunchKernelGGL((adam_ptr_kernel<Scale>), dim3((unsigned)blocks), dim3(kAdamThreads), 0,
+                     static_cast<hipStream_t>(stream), param, grad_ptrs, seg_off, nseg, exp_avg, exp_avg_sq, n4, n,
+                     c.step_size, beta1, beta2, eps, c.inv_sqrt_bc2, scale);
+  return launch_status(what);
+}
+
+}  // namespace
+}  // namespace fpsg
+
+// the argument checks of the two forms of the step: the plain and the _dscale entry share them, each under its own name
+#define FPSG_ADAM_CHECK_SEGMENTS(NAME)                                                                                  \
+  FPSG_REQUIRE(n > 0 && step >= 1 && nseg > 0, FPSG_E_SHAPE,                                                            \
+               NAME ": n, nseg must be positive and step >= 1 (got %zu, %d, %d)", n, nseg, step);                       \
+  FPSG_REQUIRE(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f && eps >= 0.0f, FPSG_E_SHAPE,             \
+               NAME ": betas must lie in [0,1) and eps be non-negative");                                               \
+  FPSG_REQUIRE_PTR(param); FPSG_REQUIRE_PTR(exp_avg); FPSG_REQUIRE_PTR(exp_avg_sq);                                     \
+  FPSG_REQUIRE(grad_ptrs != nullptr && seg_off != nullptr, FPSG_E_NULL, NAME ": null table");                           \
+  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(exp_avg) |                            \
+                 reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0,                                                   \
+               FPSG_E_ALIGN, NAME ": param, exp_avg and exp_avg_sq must be 16-byte aligned")
+
+#define FPSG_ADAM_CHECK_FLAT(NAME)                                                                                      \
+  FPSG_REQUIRE(n > 0 && step >= 1, FPSG_E_SHAPE, NAME ": n must be positive and step >= 1 (got %zu, %d)", n, step);     \
+  FPSG_REQUIRE(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f && eps >= 0.0f, FPSG_E_SHAPE,             \
+               NAME ": betas must lie in [0,1) and eps be non-negative");                                               \
+  FPSG_REQUIRE_PTR(param); FPSG_REQUIRE_PTR(grad); FPSG_REQUIRE_PTR(exp_avg); FPSG_REQUIRE_PTR(exp_avg_sq);             \
+  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |                               \
+                 reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0,            \
+               FPSG_E_ALIGN, NAME ": the four buffers must be 16-byte aligned")
+
+extern "C" int fpsg_adam_step_segments(float* param, const float* const* grad_ptrs, const long long* seg_off, int nseg,
+                                       float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
+                                       float eps, int step, float grad_scale, fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_ADAM_CHECK_SEGMENTS("fpsg_adam_step_segments");
+  return launch_adam_segments<float>("fpsg_adam_step_segments", param, grad_ptrs, seg_off, nseg, exp_avg, exp_avg_sq, n, lr,
+                                     beta1, beta2, eps, step, grad_scale, stream);
+}
+
+extern "C" int fpsg_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
+                              float beta1, float beta2, float eps, int step, float grad_scale, fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_ADAM_CHECK_FLAT("fpsg_adam_step");
+  return launch_adam<float>("fpsg_adam_step", param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, grad_scale,
+                            stream);
+}
+
+extern "C" int fpsg_adam_step_segments_dscale(float* param, const float* const* grad_ptrs, const long long* seg_off,
+                                              int nseg, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1,
+                                              float beta2, float eps, int step, const float* grad_scale_dev,
+                                              fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_ADAM_CHECK_SEGMENTS("fpsg_adam_step_segments_dscale");
+  FPSG_REQUIRE_PTR(grad_scale_dev);
+  return launch_adam_segments<const float*>("fpsg_adam_step_segments_dscale", param, grad_ptrs, seg_off, nseg, exp_avg,
+                                            exp_avg_sq, n, lr, beta1, beta2, eps, step, grad_scale_dev, stream);
+}
+
+extern "C" int fpsg_adam_step_dscale(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
+                                     float beta1, float beta2, float eps, int step, const float* grad_scale_dev,
+                                     fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_ADAM_CHECK_FLAT("fpsg_adam_step_dscale");
+  FPSG_REQUIRE_PTR(grad_scale_dev);
+  return launch_adam<const float*>("fpsg_adam_step_dscale", param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step,
+                                   grad_scale_dev, stream);
+}
+
+extern "C" size_t fpsg_grad_norm_workspace_bytes(size_t n) { return fpsg::grad_norm_blocks(n) * sizeof(double); }
+
+// the checks the two forms of fpsg_grad_clip_scale share, behind their own (n, pointers of the gradient)
+#define FPSG_CLIP_CHECK_TAIL(NAME)                                                                                      \
+  FPSG_REQUIRE(workspace != nullptr, FPSG_E_NULL, NAME ": null pointer 'workspace'");                                   \
+  FPSG_REQUIRE_PTR(out2);                                                                                               \
+  FPSG_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0,      \
+               FPSG_E_ALIGN, NAME ": workspace and stats must be 8-byte aligned");                                      \
+  FPSG_REQUIRE(workspace_bytes >= fpsg_grad_norm_workspace_bytes(n), FPSG_E_SHAPE,                                      \
+               NAME ": workspace of %zu bytes, fpsg_grad_norm_workspace_bytes(%zu) = %zu", workspace_bytes, n,          \
+               fpsg_grad_norm_workspace_bytes(n));                                                                      \
+  FPSG_REQUIRE(max_norm >= 0.0f, FPSG_E_SHAPE, NAME ": max_norm must be non-negative and not NaN (got %g)",             \
+               (double)max_norm);                                                                                       \
+  FPSG_REQUIRE(__builtin_isfinite(grad_scale), FPSG_E_SHAPE, NAME ": grad_scale must be finite (got %g)",               \
+               (double)grad_scale)
+
+extern "C" int fpsg_grad_clip_scale(const float* grad, size_t n, float grad_scale, float max_norm, void* workspace,
+                                    size_t workspace_bytes, float* out2, double* stats, fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_REQUIRE(n > 0, FPSG_E_SHAPE, "fpsg_grad_clip_scale: n must be positive (got %zu)", n);
+  FPSG_REQUIRE_PTR(grad);
+  FPSG_REQUIRE((reinterpret_cast<uintptr_t>(grad) & 15) == 0, FPSG_E_ALIGN, "fpsg_grad_clip_scale: grad must be 16-byte aligned");
+  FPSG_CLIP_CHECK_TAIL("fpsg_grad_clip_scale");
+  const int blocks = (int)grad_norm_blocks(n);
+  double* partial = static_cast<double*>(workspace);
+  hipLaunchKernelGGL((grad_sqnorm_kernel<false>), dim3((unsigned)blocks), dim3(kAdamThreads), 0,
+                     static_cast<hipStream_t>(stream), grad, nullptr, nullptr, 0, n / 4, n, partial);
+  if (const int rc = launch_status("fpsg_grad_clip_scale")) return rc;
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(kAdamThreads), 0, static_cast<hipStream_t>(stream),
+                     partial, blocks, grad_scale, max_norm, out2, stats);
+  return launch_status("fpsg_grad_clip_scale");
+}
+
+extern "C" int fpsg_grad_clip_scale_segments(const float* const* grad_ptrs, const long long* seg_off, int nseg, size_t n,
+                                             float grad_scale, float max_norm, void* workspace, size_t workspace_bytes,
+                                             float* out2, double* stats, fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_REQUIRE(n > 0 && nseg > 0, FPSG_E_SHAPE, "fpsg_grad_clip_scale_segments: n, nseg must be positive (got %zu, %d)", n, nseg);
+  FPSG_REQUIRE(grad_ptrs != nullptr && seg_off != nullptr, FPSG_E_NULL, "fpsg_grad_clip_scale_segments: null table");
+  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(grad_ptrs) | reinterpret_cast<uintptr_t>(seg_off)) & 7) == 0, FPSG_E_ALIGN,
+               "fpsg_grad_clip_scale_segments: the tables must be 8-byte aligned");
+  FPSG_CLIP_CHECK_TAIL("fpsg_grad_clip_scale_segments");
+  const int blocks = (int)grad_norm_blocks(n);
+  double* partial = static_cast<double*>(workspace);
+  hipLaunchKernelGGL((grad_sqnorm_kernel<true>), dim3((unsigned)blocks), dim3(kAdamThreads), 0,
+                     static_cast<hipStream_t>(stream), nullptr, grad_ptrs, seg_off, nseg, n / 4, n, partial);
+  if (const int rc = launch_status("fpsg_grad_clip_scale_segments")) return rc;
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(kAdamThreads), 0, static_cast<hipStream_t>(stream),
+                     partial, blocks, grad_scale, max_norm, out2, stats);
+  return launch_status("fpsg_grad_clip_scale_segments");
 }
 
 extern "C" int fpsg_flat_accumulate_segments(float* flat, const float* const* grad_ptrs, const long long* seg_off, int nseg,

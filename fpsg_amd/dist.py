@@ -355,7 +355,10 @@ class FlatGradBuckets:
         unless ``scale`` is False: the caller's optimizer then applies 1/E itself while it
         reads the buffer (``fpsg_adam_step``'s ``grad_scale``: the same fp32 product per
         element, without a separate read-modify-write pass over the 310 MB buffer on the
-        critical path behind the last all-reduce), and the buffer keeps the SUM."""
+        critical path behind the last all-reduce), and the buffer keeps the SUM.  The attached
+        ``p.grad`` views then hold that sum too: ``torch.nn.utils.clip_grad_norm_`` called on
+        them clips at E times the wrong threshold; ``--clip_grad_norm`` / ``FlatAdam``'s
+        ``max_grad_norm`` and ``last_grad_norm`` (K20) work on the mean."""
         self.flush()
         if self._armed:
             cur = torch.cuda.current_stream(self.flat.device) if self.flat.is_cuda else None

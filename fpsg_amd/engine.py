@@ -19,7 +19,7 @@ from . import bn_counters, eval_report, winograd
 from .few_shot import ImgPCProtoNet
 from .image_net import ImageEncoderWarpper
 from .metrics import SINKHORN_TRAIN_DIAMETER, check_dcd_alpha, check_thresholds, nearest_rows
-from .optim import FlatAdam
+from .optim import FlatAdam, check_max_grad_norm
 from .point_cloud_net import PCDecoder, PCEncoder
 
 
@@ -31,7 +31,7 @@ def default_options(**overrides) -> argparse.Namespace:
         support_factor=1.0, query_factor=1.0, intra_recon=False, num_clusters=4, ori_dim=2,
         raw_dim=3, num_nodes=4, device="cuda", bottleneck_size=1536, template_type="SQUARE",
         activation="relu", aggregate="single", pc_dist="cd", lr=1e-3, lr_decay=350, SGD=False,
-        n_way=1, n_shot=20, n_query=0)
+        n_way=1, n_shot=20, n_query=0, clip_grad_norm=0.0)
     for k, v in overrides.items():
         setattr(opt, k, v)
     return opt
@@ -56,17 +56,21 @@ def build_model(opt) -> ImgPCProtoNet:
 
 def build_optimizer(model, opt):
     """Adam(lr, betas=(.9,.999)) or SGD(weight_decay=1e-2) + StepLR(gamma=.5)
-    (``trainNetwork.py:118-130``)."""
+    (``trainNetwork.py:118-130``).  ``opt.clip_grad_norm`` (0: off) becomes the optimizer's ``max_grad_norm``: K20 inside
+    ``FlatAdam.step``; on any other optimizer an attribute that ``TrainStep`` reads."""
     on_gpu = next(model.parameters()).is_cuda
+    max_norm = check_max_grad_norm(getattr(opt, "clip_grad_norm", None), "clip_grad_norm")
     if not opt.SGD:
         if on_gpu and os.environ.get("FPSG_FLAT_ADAM", "1") != "0":
             # K7: parameters, gradients and moments in flat buffers, the step is one HBM stream
-            optimizer = FlatAdam(model.parameters(), lr=opt.lr, betas=(0.9, 0.999))
+            optimizer = FlatAdam(model.parameters(), lr=opt.lr, betas=(0.9, 0.999), max_grad_norm=max_norm)
         else:
             optimizer = optim.Adam(model.parameters(), lr=opt.lr, betas=(0.9, 0.999),
                                    **({"fused": True} if on_gpu else {}))
     else:
         optimizer = optim.SGD(model.parameters(), lr=opt.lr, weight_decay=1e-2)
+    if max_norm is not None and not isinstance(optimizer, FlatAdam):
+        optimizer.max_grad_norm = max_norm
     scheduler = optim.lr_scheduler.StepLR(optimizer, step_size=int(opt.lr_decay), gamma=0.5)
     return optimizer, scheduler
 
@@ -93,10 +97,22 @@ class TrainStep:
     into the graph's static buffers; the captured sequence ends with the multi-tensor adds of
     the episode's gradients into the flat buffer (``FlatGradBuckets.absorb``).  With more than
     one rank the LAST local episode of a step always runs eagerly, so that its backward can
-    launch the bucketed all-reduce from the autograd hooks."""
+    launch the bucketed all-reduce from the autograd hooks.
 
-    def __init__(self, model, optimizer, world: int = 1, bucket_mb: float = 80.0, graph: bool = False):
+    ``max_grad_norm`` (default: the optimizer's ``max_grad_norm`` attribute, as ``build_optimizer`` sets it from
+    ``--clip_grad_norm``; None, 0 and inf mean off): the 2-norm of the step's MEAN gradient is clipped to it.  With
+    ``FlatAdam`` that happens inside ``optimizer.step()`` (K20: no pass over the gradient, no host read); with any other
+    optimizer -- CPU runs, ``--SGD``, ``FPSG_FLAT_ADAM=0`` -- the attached gradients hold the mean and
+    ``torch.nn.utils.clip_grad_norm_`` runs on them in front of the step.  ``last_grad_norm`` / ``clip_stats()`` report
+    either form.  Note that after a step with ``FlatAdam`` ``p.grad`` holds the SUM over the step's episodes (the ``1/E``
+    is folded into the step): ``clip_grad_norm_`` called on it from outside clips at ``E`` times the wrong threshold."""
+
+    def __init__(self, model, optimizer, world: int = 1, bucket_mb: float = 80.0, graph: bool = False,
+                 max_grad_norm=None):
         self.model, self.optimizer, self.world = model, optimizer, world
+        if max_grad_norm is not None:
+            optimizer.max_grad_norm = check_max_grad_norm(max_grad_norm, "TrainStep: max_grad_norm")
+        self._torch_clip = None     # (last norm, counters) of the clip_grad_norm_ form
         self.buckets = fdist.FlatGradBuckets(model, bucket_mb=bucket_mb)
         if isinstance(optimizer, FlatAdam):
             optimizer.bind_gradients(self.buckets.flat)      # same layout: the step reads it in place
@@ -167,6 +183,37 @@ class TrainStep:
         g.replay()
         return {n: v.clone() for n, v in static_out.items()}
 
+    # ------------------------------------------------------------------- clipping
+    def _clip_attached(self, max_norm: float) -> None:
+        """``clip_grad_norm_`` on the attached (mean) gradients, with K20's counters kept on the device."""
+        params = [p for p in self.model.parameters() if p.grad is not None]
+        norm = torch.nn.utils.clip_grad_norm_(params, max_norm).detach().float()
+        stats = self._torch_clip[1] if self._torch_clip else torch.zeros(4, dtype=torch.float64, device=norm.device)
+        finite = torch.isfinite(norm)
+        stats[0] += 1
+        stats[1] += (max_norm / (norm + 1e-6) < 1).double()
+        stats[2] += (~finite).double()
+        stats[3] = torch.maximum(stats[3], torch.where(finite, norm, torch.zeros_like(norm)).double())
+        self._torch_clip = (norm, stats)
+
+    @property
+    def last_grad_norm(self):
+        """The norm of the last clipped step's mean gradient, a 0-dim tensor on the model's device (no sync), or None."""
+        if isinstance(self.optimizer, FlatAdam):
+            return self.optimizer.last_grad_norm
+        return self._torch_clip[0] if self._torch_clip else None
+
+    def clip_stats(self, reset: bool = True) -> dict:
+        """``FlatAdam.clip_stats`` for whichever form clips: one host read."""
+        if isinstance(self.optimizer, FlatAdam):
+            return self.optimizer.clip_stats(reset)
+        if self._torch_clip is None:
+            return {"steps": 0, "clipped": 0, "nonfinite": 0, "max_norm_seen": 0.0}
+        s = self._torch_clip[1].tolist()
+        if reset:
+            self._torch_clip[1].zero_()
+        return {"steps": int(s[0]), "clipped": int(s[1]), "nonfinite": int(s[2]), "max_norm_seen": float(s[3])}
+
     # ----------------------------------------------------------------------- the step
     def __call__(self, local_episodes: list[dict], n_episodes_global: int | None = None):
         """Returns the list of loss dicts (device tensors; call ``.item()`` outside the
@@ -202,6 +249,10 @@ class TrainStep:
             self.buckets.attach()       # the optimizer reads the step's gradient from the flat buffer
             if fold:
                 self.optimizer.grad_scale = 1.0 / n_episodes_global if n_episodes_global > 1 else 1.0
+        if not isinstance(self.optimizer, FlatAdam):
+            max_norm = check_max_grad_norm(getattr(self.optimizer, "max_grad_norm", None), "max_grad_norm")
+            if max_norm is not None:
+                self._clip_attached(max_norm)
         try:
             self.optimizer.step()
         finally:

@@ -16,8 +16,19 @@ It is a ``torch.optim.Optimizer``: ``param_groups[0]['lr']`` (StepLR), ``state_d
 ``load_state_dict()`` (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` entries, i.e. the
 format of ``torch.optim.Adam``) keep working.  A parameter without a gradient counts as a zero
 gradient (torch skips it): with the flat gradient buffer of the train step every parameter has one.
+
+``max_grad_norm`` (K20): ``torch.nn.utils.clip_grad_norm_`` in front of the step, without its read-modify-write pass
+over the gradient and without a host read -- one read of the gradient for the norm (``fpsg_grad_clip_scale``), the clip
+coefficient folded into the factor the step multiplies the gradient by anyway, taken from device memory
+(``fpsg_adam_step_dscale``).  The norm is that of ``grad_scale * grad``, the gradient the update uses: under
+``TrainStep``'s folded ``1/E`` the MEAN over the step's episodes, so a threshold means the same for any number of
+episodes per step.  (``p.grad`` itself holds their SUM after such a step: ``clip_grad_norm_`` called on it would clip
+at ``E`` times the wrong threshold.)  ``last_grad_norm`` and ``clip_stats()`` report what happened.
 """
 from __future__ import annotations
+
+import math
+import numbers
 
 import torch
 from torch.optim import Optimizer
@@ -63,8 +74,23 @@ def flat_layout(params):
     return out, off
 
 
+def check_max_grad_norm(value, name: str = "max_grad_norm"):
+    """The clipping threshold as a float, or None where it means no clipping (``None``, ``0``, ``inf``); ``ValueError``
+    for a negative number, NaN or something that is no number."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, numbers.Real):
+        raise ValueError(f"{name}: a non-negative number or None, got {value!r}")
+    value = float(value)
+    if math.isnan(value) or value < 0:
+        raise ValueError(f"{name}: a non-negative number or None, got {value!r}")
+    return None if value == 0 or math.isinf(value) else value
+
+
 class FlatAdam(Optimizer):
-    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm=None):
+        # (not a hyper-parameter of the group: param_groups and state_dict keep torch.optim.Adam's entries)
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm, "FlatAdam: max_grad_norm")
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1):
             raise ValueError("FlatAdam: invalid lr / eps / betas")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps))
@@ -89,6 +115,7 @@ class FlatAdam(Optimizer):
         self._t = 0
         self.grad_scale = 1.0                  # multiplies the gradient as the step reads it (TrainStep: 1/E, then reset)
         self._step_tensor = torch.zeros((), dtype=torch.float32)       # shared by every state entry
+        self._clip = None                      # K20's buffers: (workspace, out2, stats), made by the first clipped step
         with torch.no_grad():
             for p, off, n in self._layout:
                 view = self.flat_param[off:off + n].view(p.shape)
@@ -170,6 +197,9 @@ class FlatAdam(Optimizer):
         self._t += 1
         self._step_tensor.fill_(float(self._t))
         lib = _hip.load()
+        if check_max_grad_norm(self.max_grad_norm, "FlatAdam: max_grad_norm") is not None:
+            _hip.check(self._clipped_step(lib, group, g, table), "fpsg_adam_step (clipped)")
+            return loss
         hyper = (float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]), self._t,
                  float(self.grad_scale), _hip.stream_of(self.flat_param))
         with torch.cuda.device(self.flat_param.device):
@@ -182,6 +212,52 @@ class FlatAdam(Optimizer):
                                                  _hip.ptr(self.flat_exp_avg_sq), self.flat_param.numel(), *hyper)
         _hip.check(rc, "fpsg_adam_step")
         return loss
+
+    # ------------------------------------------------------------------ clipping (K20)
+    def _clip_buffers(self):
+        if self._clip is None:
+            dev = self.flat_param.device
+            nbytes = int(_hip.load().fpsg_grad_norm_workspace_bytes(self.flat_param.numel()))
+            self._clip = (torch.empty(nbytes // 8, dtype=torch.float64, device=dev),
+                          torch.zeros(2, dtype=torch.float32, device=dev),
+                          torch.zeros(4, dtype=torch.float64, device=dev))
+        return self._clip
+
+    def _clipped_step(self, lib, group, g, table) -> int:
+        """The norm of ``grad_scale * grad`` and the factor ``grad_scale * coef`` into ``out2``, then the step that reads
+        the factor from there: three launches, nothing read by the host."""
+        ws, out2, stats = self._clip_buffers()
+        n, stream = self.flat_param.numel(), _hip.stream_of(self.flat_param)
+        tail = (float(self.grad_scale), float(self.max_grad_norm), _hip.ptr(ws), ws.numel() * 8, _hip.ptr(out2),
+                _hip.ptr(stats), stream)
+        hyper = (float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]), self._t,
+                 _hip.ptr(out2) + 4, stream)
+        with torch.cuda.device(self.flat_param.device):
+            if g is not None:
+                rc = lib.fpsg_grad_clip_scale(_hip.ptr(g), n, *tail)
+                return rc or lib.fpsg_adam_step_dscale(_hip.ptr(self.flat_param), _hip.ptr(g), _hip.ptr(self.flat_exp_avg),
+                                                       _hip.ptr(self.flat_exp_avg_sq), n, *hyper)
+            rc = lib.fpsg_grad_clip_scale_segments(_hip.ptr(table), _hip.ptr(self._seg_off), len(self._layout), n, *tail)
+            return rc or lib.fpsg_adam_step_segments_dscale(_hip.ptr(self.flat_param), _hip.ptr(table),
+                                                            _hip.ptr(self._seg_off), len(self._layout),
+                                                            _hip.ptr(self.flat_exp_avg), _hip.ptr(self.flat_exp_avg_sq),
+                                                            n, *hyper)
+
+    @property
+    def last_grad_norm(self):
+        """The norm of the last clipped step's gradient (``grad_scale`` included) as a 0-dim device tensor: a view of the
+        kernel's output, read without a synchronisation and overwritten by the next step.  None before the first one."""
+        return None if self._clip is None else self._clip[1][0]
+
+    def clip_stats(self, reset: bool = True) -> dict:
+        """Counters of the clipped steps since the last reset -- the one host read of K20: ``steps``, ``clipped`` (the
+        coefficient was below 1), ``nonfinite`` (the norm was inf or NaN) and ``max_norm_seen`` (over the finite norms)."""
+        if self._clip is None:
+            return {"steps": 0, "clipped": 0, "nonfinite": 0, "max_norm_seen": 0.0}
+        s = self._clip[2].tolist()
+        if reset:
+            self._clip[2].zero_()
+        return {"steps": int(s[0]), "clipped": int(s[1]), "nonfinite": int(s[2]), "max_norm_seen": float(s[3])}
 
     # ------------------------------------------------------------------ state dict
     def load_state_dict(self, state_dict) -> None:

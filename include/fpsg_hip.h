@@ -901,6 +901,52 @@ int fpsg_flat_accumulate_segments(float* flat, const float* const* grad_ptrs, co
 int fpsg_flat_accumulate_tables(float* flat, const float* const* grad_ptrs, const long long* seg_off, int nseg, int ntab,
                                 size_t n, int accumulate, fpsg_stream_t stream);
 
+/* ---- K20: gradient-norm clipping folded into K7's factor ------------------------------------------
+ * torch.nn.utils.clip_grad_norm_(params, max_norm) (2-norm, error_if_nonfinite=False) in front of the Adam step,
+ * without a pass that rewrites the gradient and without a host read: one read of the gradient for the sum of its
+ * squares, one finalize launch that leaves grad_scale * coef in device memory, and the _dscale forms of K7's entry
+ * points, which take their factor from there.  The norm is that of grad_scale * grad, the gradient the update uses.
+ *
+ * Sum of squares (pinned: the order of every add depends on n alone, not on the device, the stream or the run):
+ *   P = min(ceil((n/4 + 1) / 256), 4096) workgroups of 256 threads, T = 256 P threads; vector slot j holds the flat
+ *   positions 4j .. 4j+3, slot n/4 the n % 4 tail padded with zeros.  Thread t takes the slots t, t + T, t + 2T, ..
+ *   in that order; element e of a slot goes into the thread's accumulator e, a_e = fma(g, g, a_e) in fp64 from +0.0
+ *   (the square of an fp32 value is exact in fp64).  The thread's value is (a_0 + a_1) + (a_2 + a_3); a wave's is the
+ *   butterfly v += v[lane ^ 1], ^ 2, ^ 4, ^ 8, ^ 16, ^ 32; a workgroup's is (w_0 + w_1) + (w_2 + w_3) over its four
+ *   waves, written as one double to workspace[blockIdx] by a plain store.  No atomics, no arrival counter.
+ *   The _segments form reads the same positions through the table of fpsg_adam_step_segments (NULL = zeros; the
+ *   gradient tensors may start at any 4-byte address): the same thread, the same order, so the same bits as the flat
+ *   form on the gathered values.
+ * Finalize (one workgroup; one thread does the arithmetic):
+ *   S    = workspace[0] + workspace[1] + .. in ascending order from +0.0, fp64
+ *   norm = (float)(fabs((double)grad_scale) * sqrt(S))
+ *   x    = max_norm / (norm + 1e-6f)            fp32
+ *   coef = x if x < 1 or x is NaN, else 1.0f    (torch.clamp(max=1.0) keeps a NaN)
+ *   out2[0] = norm;  out2[1] = grad_scale * coef   (one fp32 product: grad_scale itself whenever nothing is clipped)
+ *   stats (optional, double[4], updated in place by plain loads and stores -- the stream orders the steps):
+ *   [0] += 1; [1] += 1 if coef < 1; [2] += 1 if norm is not finite; [3] = max([3], norm) over the finite norms.
+ * fpsg_grad_norm_workspace_bytes(n) = 8 P (0 for n = 0).  Both calls only enqueue (two launches).
+ * Errors, all before any launch: FPSG_E_SHAPE for n = 0, nseg < 1, a workspace smaller than
+ * fpsg_grad_norm_workspace_bytes(n), max_norm negative or NaN (+inf is accepted and never clips) or a grad_scale that
+ * is not finite; FPSG_E_NULL for a null grad, table, workspace or out2; FPSG_E_ALIGN for a grad that is not 16-byte
+ * aligned, a workspace, stats or table that is not 8-byte aligned, or a misaligned out2.
+ */
+size_t fpsg_grad_norm_workspace_bytes(size_t n);
+int fpsg_grad_clip_scale(const float* grad, size_t n, float grad_scale, float max_norm, void* workspace,
+                         size_t workspace_bytes, float* out2, double* stats, fpsg_stream_t stream);
+int fpsg_grad_clip_scale_segments(const float* const* grad_ptrs, const long long* seg_off, int nseg, size_t n,
+                                  float grad_scale, float max_norm, void* workspace, size_t workspace_bytes, float* out2,
+                                  double* stats, fpsg_stream_t stream);
+/* fpsg_adam_step / fpsg_adam_step_segments with the factor on the gradient read from device memory (one float, e.g.
+ * out2 + 1 of the calls above; each thread reads it once) instead of passed by value: the same arithmetic, so with
+ * *grad_scale_dev == grad_scale the same bits.  The same checks; grad_scale_dev must not be null. */
+int fpsg_adam_step_dscale(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
+                          float beta1, float beta2, float eps, int step, const float* grad_scale_dev,
+                          fpsg_stream_t stream);
+int fpsg_adam_step_segments_dscale(float* param, const float* const* grad_ptrs, const long long* seg_off, int nseg,
+                                   float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
+                                   float eps, int step, const float* grad_scale_dev, fpsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

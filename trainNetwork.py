@@ -29,6 +29,7 @@ from fpsg_amd import cli, winograd
 from fpsg_amd import dist as fdist
 from fpsg_amd.engine import TrainStep, build_model, build_optimizer, to_device
 from fpsg_amd.episodes import EpisodePrefetcher
+from fpsg_amd.optim import check_max_grad_norm
 
 
 def evaluate(model, dl_test, n_query, n_shot, device, log, rank: int = 0, world: int = 1):
@@ -173,6 +174,10 @@ def main(opt):
             f"Support_rec: {s_sum / done}")
         if is_main:
             print(f"  [{done / dt:.2f} episodes/s over {world} GPU(s)]")
+        if is_main and check_max_grad_norm(opt.clip_grad_norm) is not None:
+            cs = step.clip_stats()      # one host read per epoch; printed only, not part of the reference-format log
+            print(f"  [grad norm: max {cs['max_norm_seen']:.6g}; clipped {cs['clipped']} of {cs['steps']} steps; "
+                  f"{cs['nonfinite']} non-finite]")
         scheduler.step()
 
         evaluating = epoch % opt.eval_interval == 0 or epoch == opt.epoch
