@@ -19,7 +19,9 @@ generated and reference query clouds), ``--fscore TAU [TAU ...]`` (evaluation: t
 those distances and the Hausdorff distance, per class), ``--pc_dist dcd`` with ``--dcd_alpha`` (training on the
 density-aware Chamfer distance, K18), ``--dcd [ALPHA]`` (evaluation: that distance per class), ``--pc_dist sinkhorn``
 with ``--sinkhorn_blur`` / ``--sinkhorn_diameter`` (training on the Sinkhorn divergence the evaluation prints as EMD, K19),
-``--clip_grad_norm X`` (training: the 2-norm of every step's mean gradient clipped to X, K20, and one extra line per epoch).
+``--clip_grad_norm X`` (training: the 2-norm of every step's mean gradient clipped to X, K20, and one extra line per epoch),
+``--repulsion_weight W`` with ``--repulsion_k`` / ``--repulsion_h`` (training: W times the repulsion term of the decoded
+clouds, K21, added to whichever ``--pc_dist`` is trained, and one extra line per epoch).
 """
 from __future__ import annotations
 
@@ -31,7 +33,8 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import eval_report
-from .metrics import SINKHORN_TRAIN_DIAMETER, check_sinkhorn_option
+from .few_shot import check_repulsion_weight
+from .metrics import SINKHORN_TRAIN_DIAMETER, check_repulsion_options, check_sinkhorn_option
 from .episodes import EpisodicBatchSampler, SequentialBatchSampler, SyntheticFewShot
 
 
@@ -99,6 +102,15 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--clip_grad_norm", type=_clip_norm, default=0.0, metavar="X",
                    help="Clip the 2-norm of every optimizer step's mean gradient to X [default: 0 = off]; prints the "
                         "largest norm and the number of clipped steps after every epoch;")
+    g.add_argument("--repulsion_weight", type=float, default=0.0, metavar="W",
+                   help="Add W times the repulsion term of the generated clouds (each point against its nearest "
+                        "neighbours in its own cloud) to the training loss, under any --pc_dist [default: 0 = off]; prints "
+                        "the mean term per cloud after every epoch;")
+    g.add_argument("--repulsion_k", type=int, default=4, metavar="K",
+                   help="With --repulsion_weight: neighbours per point, 1..8 [default: 4];")
+    g.add_argument("--repulsion_h", type=float, default=0.03, metavar="H",
+                   help="With --repulsion_weight: the bandwidth of the term, a length -- clouds live in the unit ball "
+                        "[default: 0.03];")
     g.add_argument("--SGD", action="store_true")
     g.add_argument("--episodes_per_step", type=int, default=0,
                    help="Episodes per optimizer step over all ranks [default: one per rank];")
@@ -130,6 +142,15 @@ def validate(opt) -> None:
                 check_sinkhorn_option(getattr(opt, flag), flag)
             except ValueError as e:
                 raise SystemExit(f"--{e}") from None
+    if getattr(opt, "repulsion_weight", None) is not None:
+        try:
+            check_repulsion_weight(opt.repulsion_weight)
+        except ValueError as e:
+            raise SystemExit(f"--{e}") from None
+        try:
+            check_repulsion_options(opt.repulsion_k, opt.repulsion_h)
+        except ValueError as e:
+            raise SystemExit(f"--repulsion_{e}") from None
     eval_report.check(opt)          # the evaluation report's options; a training namespace has none of them
 
 

@@ -13,14 +13,15 @@ and ``metric='emd'`` works instead of raising AttributeError.
 """
 from __future__ import annotations
 
+import math
 import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from .metrics import (SINKHORN_TRAIN_DIAMETER, chamfer_distance, check_dcd_alpha, check_sinkhorn_option, dcd, emd_loss,
-                      episode_chamfer_losses, sinkhorn_loss)
+from .metrics import (SINKHORN_TRAIN_DIAMETER, chamfer_distance, check_dcd_alpha, check_repulsion_options,
+                      check_sinkhorn_option, dcd, emd_loss, episode_chamfer_losses, repulsion_loss, sinkhorn_loss)
 from .utils import emd_wrapper
 
 _AGGREGATOR = ["single", "multi", "mask_single", "mask_multi"]
@@ -29,6 +30,17 @@ _AGGREGATOR = ["single", "multi", "mask_single", "mask_multi"]
 def _fused_losses_enabled() -> bool:
     """``FPSG_FUSED_LOSSES=0``: the loss sums as separate PyTorch operations (A/B measurements)."""
     return os.environ.get("FPSG_FUSED_LOSSES", "1") != "0"
+
+
+def check_repulsion_weight(weight) -> float:
+    """``repulsion_weight`` as a Python float: a finite, non-negative number (``ValueError`` otherwise)."""
+    try:
+        w = float(weight)
+    except (TypeError, ValueError):
+        raise ValueError(f"repulsion_weight must be a number, got {weight!r}") from None
+    if isinstance(weight, bool) or not (math.isfinite(w) and w >= 0.0):
+        raise ValueError(f"repulsion_weight must be finite and non-negative, got {weight!r}")
+    return w
 
 
 class _SplitRows(torch.autograd.Function):
@@ -62,7 +74,8 @@ def _split_rows(t, n):
 class ImgPCProtoNet(nn.Module):
     def __init__(self, img_encoder, pc_encoder, pc_decoder, mask_learner=None, query_factor=1.0,
                  support_factor=1.0, metric="cd", intra_support=False, aggregate="single", dcd_alpha=1000.0,
-                 sinkhorn_blur=0.05, sinkhorn_diameter=SINKHORN_TRAIN_DIAMETER):
+                 sinkhorn_blur=0.05, sinkhorn_diameter=SINKHORN_TRAIN_DIAMETER, repulsion_weight=0.0, repulsion_k=4,
+                 repulsion_h=0.03):
         super().__init__()
         self.img_encoder = img_encoder
         self.pc_encoder = pc_encoder
@@ -97,6 +110,10 @@ class ImgPCProtoNet(nn.Module):
         # can drive the module on CPU with the oracle's implementations
         self.emd_metric = emd_wrapper
         self._batched_pairs = metric in ("dcd", "sinkhorn")      # one call over the Q + S pairs (below)
+        # the repulsion regulariser (K21) on the decoded clouds, added to whichever distance is trained; 0: off, and
+        # the loss is what it is without these arguments, launch for launch
+        self.repulsion_weight = check_repulsion_weight(repulsion_weight)
+        self.repulsion_k, self.repulsion_h = check_repulsion_options(repulsion_k, repulsion_h)
         self.overlap_encoders = False      # see _encode; switched on by bench.py / the trainer
         self._side_stream = None
 
@@ -175,7 +192,32 @@ class ImgPCProtoNet(nn.Module):
         return self._loss_single_class(sample["xs"], sample["xq"], sample["xad"], sample["pcs"],
                                        sample["pcq"], sample["pcad"])
 
+    def _with_repulsion(self, out, syn, n_q):
+        """Adds the repulsion term of the episode's decoded clouds ``syn`` (the first ``n_q`` are the queries', the rest
+        the supports') to the loss dict: ONE K21 call; ``ttl_loss`` gains ``repulsion_weight * (query_factor * sum_q R
+        + support_factor * sum_s R)``, ``repulsion_loss`` is the unweighted sum, every other entry stays as it is."""
+        rep = repulsion_loss(syn.contiguous(), self.repulsion_k, self.repulsion_h)
+        rep_q = rep[:n_q].sum()
+        weighted = self.query_factor * rep_q
+        total = rep_q
+        if n_q < rep.size(0):
+            rep_s = rep[n_q:].sum()
+            weighted = weighted + self.support_factor * rep_s
+            total = total + rep_s
+        out = dict(out)
+        out["ttl_loss"] = out["recon_loss"] + self.repulsion_weight * weighted
+        out["repulsion_loss"] = total
+        return out
+
     def _loss_single_class(self, img_s, img_q, img_ad, pc_s, pc_q, pc_ad):
+        out, syn, n_q = self._recon_losses(img_s, img_q, img_ad, pc_s, pc_q, pc_ad, self.repulsion_weight > 0)
+        if self.repulsion_weight > 0:
+            return self._with_repulsion(out, syn, n_q)
+        return out
+
+    def _recon_losses(self, img_s, img_q, img_ad, pc_s, pc_q, pc_ad, want_clouds=False):
+        """``(loss dict, decoded clouds, number of query clouds)``; the clouds (queries first, then the supports under
+        ``intra_support``) only where ``want_clouds``: their concatenation is a launch the plain loss does not make."""
         img_zad, img_zq, pc_z_proto, pc_z_ad = self._encode(img_s, img_q, img_ad, pc_s, pc_ad)
         pack = self._decoder_pack() if self.intra_flag else None
         ref_q = pc_q.squeeze(0).contiguous()
@@ -205,7 +247,7 @@ class ImgPCProtoNet(nn.Module):
                     loss_rec_q, loss_rec_s, loss_recon = episode_chamfer_losses(syn, ref, n_q, self.query_factor,
                                                                                 self.support_factor)
                     return {"ttl_loss": loss_recon, "recon_loss": loss_recon, "query_rec_loss": loss_rec_q,
-                            "support_rec_loss": loss_rec_s}
+                            "support_rec_loss": loss_rec_s}, syn, n_q
                 cd = self.pc_metric(syn, ref)
                 loss_rec_q, loss_rec_s = cd[:n_q].sum(), cd[n_q:].sum()
             elif self._batched_pairs and syn_q.shape[1:] == syn_s.shape[1:] and ref_q.shape[1:] == ref_s.shape[1:]:
@@ -218,13 +260,16 @@ class ImgPCProtoNet(nn.Module):
             else:
                 loss_rec_q = self.pc_metric(syn_q, ref_q).sum()
                 loss_rec_s = self.pc_metric(syn_s, ref_s).sum()
+            if want_clouds and syn is None:
+                syn = torch.cat([syn_q, syn_s])
         else:
             syn_q = self._decode_queries(img_zq, pc_z_proto, pack)
             loss_rec_q = self.pc_metric(syn_q, ref_q).sum()
             loss_rec_s = torch.zeros(1, dtype=loss_rec_q.dtype, device=loss_rec_q.device)
+            syn, n_q = syn_q, syn_q.size(0)
         loss_recon = self.query_factor * loss_rec_q + self.support_factor * loss_rec_s
         return {"ttl_loss": loss_recon, "recon_loss": loss_recon, "query_rec_loss": loss_rec_q,
-                "support_rec_loss": loss_rec_s}
+                "support_rec_loss": loss_rec_s}, syn, n_q
 
     # ---------------------------------------------------------------------- evaluation
     def _reconstruct_queries(self, sample):

@@ -8,6 +8,7 @@ contiguity / dtype / device assertions.  There is no CPU path.
 from __future__ import annotations
 
 import math
+import numbers
 
 import torch
 
@@ -746,6 +747,97 @@ def dcd(p1: torch.Tensor, p2: torch.Tensor, alpha: float = DCD_DEFAULT_ALPHA, re
         raise ValueError(f"device mismatch: {p1.device} vs {p2.device}")
     info = {} if return_info else None
     out = _Dcd.apply(p1, p2, alpha, info)
+    return (out, info) if return_info else out
+
+
+REPULSION_MAX_N = 16384          # FPSG_REPULSION_MAX_N (include/fpsg_hip.h)
+REPULSION_MAX_K = 8             # FPSG_REPULSION_MAX_K
+
+
+def check_repulsion_options(k, h):
+    """``(k, h)`` of ``repulsion_loss`` as a Python int and float: ``k`` an integer in 1..8, ``h`` a positive, finite
+    number (``ValueError`` naming the argument otherwise)."""
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+        raise ValueError(f"k must be an integer in 1..{REPULSION_MAX_K}, got {k!r}")
+    if not 1 <= int(k) <= REPULSION_MAX_K:
+        raise ValueError(f"k must be in 1..{REPULSION_MAX_K}, got {k!r}")
+    try:
+        hf = float(h)
+    except (TypeError, ValueError):
+        raise ValueError(f"h must be a number, got {h!r}") from None
+    if isinstance(h, bool) or not (math.isfinite(hf) and hf > 0.0):
+        raise ValueError(f"h must be positive and finite, got {h!r}")
+    return int(k), hf
+
+
+class _Repulsion(torch.autograd.Function):
+    """K21's forward (neighbour lists and the value per cloud) and its gather backward on the saved lists."""
+
+    @staticmethod
+    def forward(ctx, p, k, h, info_out):
+        ctx.set_materialize_grads(False)
+        B, N, _ = p.shape
+        lib = _hip.load()
+        idx = torch.empty((B, N, k), dtype=torch.int32, device=p.device)
+        d2 = torch.empty((B, N, k), dtype=torch.float32, device=p.device)
+        value = torch.empty((B,), dtype=torch.float32, device=p.device)
+        ws_bytes = lib.fpsg_repulsion_workspace_bytes(B, N, k)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=p.device)
+        with torch.cuda.device(p.device), _probe("repulsion_fwd", B, N, N):
+            rc = lib.fpsg_repulsion_fwd(_hip.ptr(p), B, N, k, h, _hip.ptr(idx), _hip.ptr(d2), _hip.ptr(value),
+                                        _hip.ptr(ws), ws_bytes, _hip.stream_of(p))
+        _hip.check(rc, "fpsg_repulsion_fwd")
+        if info_out is not None:
+            info_out.update(idx=idx, d2=d2)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(p, idx, d2)
+            ctx.cfg = (k, h)
+        return value
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        p, idx, d2 = ctx.saved_tensors
+        k, h = ctx.cfg
+        B, N, _ = p.shape
+        g = g.reshape(B).contiguous().float()
+        gx = torch.empty_like(p)
+        with torch.cuda.device(p.device), _probe("repulsion_bwd", B, N, N):
+            rc = _hip.load().fpsg_repulsion_bwd(_hip.ptr(p), _hip.ptr(idx), _hip.ptr(d2), _hip.ptr(g), B, N, k, h,
+                                                _hip.ptr(gx), _hip.stream_of(p))
+        _hip.check(rc, "fpsg_repulsion_bwd")
+        return gx, None, None, None
+
+
+def repulsion_loss(p: torch.Tensor, k: int = 4, h: float = 0.03, return_info: bool = False):
+    """PU-Net's repulsion term ``[B]`` fp32 of the clouds ``p [B,N,3]`` (K21, HIP; the definition is in
+    ``include/fpsg_hip.h``): ``(1 / (N k)) sum_i sum_{j in K(i)} -r_ij exp(-r_ij^2 / h^2)`` with ``K(i)`` the ``k`` nearest
+    neighbours of point ``i`` in its own cloud (ties to the lower index; ``i`` itself never, a duplicate of ``i`` yes) and
+    ``r = sqrt(max(d2, 1e-12))``.  In ``[-h / sqrt(2 e), 0]``: the more negative, the more neighbours sit about ``h /
+    sqrt(2)`` away; points closer than that are pushed apart by the gradient.  ``h`` is a length in the clouds' units
+    (default 0.03: clouds live in the unit ball).  It needs no ground truth and is added to whichever distance is trained.
+
+    Differentiable in ``p`` with the lists held constant; a pair at distance 0 pushes nobody.  Bitwise the same on every
+    run and independent of the batch, forward and backward (no atomics).  The call only enqueues: it can be captured.
+
+    ``return_info=True``: returns ``(value, info)`` with ``info["idx"] [B,N,k]`` int32 and ``info["d2"] [B,N,k]`` fp32,
+    nearest first.
+
+    ``ValueError`` (before anything else) for a bad ``k`` or ``h``, a shape that is not ``[B,N,3]``, ``B = 0``, ``N < k + 1``
+    and more than 16384 points.  No CPU path: a CPU tensor raises ``FpsgHipError``."""
+    k, h = check_repulsion_options(k, h)
+    if not isinstance(p, torch.Tensor) or p.dim() != 3 or p.size(2) != 3:
+        raise ValueError(f"expected a [B,N,3] cloud tensor, got {tuple(getattr(p, 'shape', ()))}")
+    if p.size(0) == 0:
+        raise ValueError(f"empty batches are not supported (got {tuple(p.shape)})")
+    if p.size(1) < k + 1:
+        raise ValueError(f"repulsion_loss needs at least k + 1 = {k + 1} points per cloud, got {p.size(1)}")
+    if p.size(1) > REPULSION_MAX_N:
+        raise ValueError(f"repulsion_loss supports at most {REPULSION_MAX_N} points per cloud, got {p.size(1)}")
+    _hip.dev_tensor(p, torch.float32, "p")
+    info = {} if return_info else None
+    out = _Repulsion.apply(p, k, h, info)
     return (out, info) if return_info else out
 
 

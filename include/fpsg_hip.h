@@ -389,6 +389,48 @@ int fpsg_dcd(const float* dist1, const int32_t* idx1, const float* dist2, const 
              float alpha, float* out, float* sides, int32_t* deg1, int32_t* deg2, float* w1, float* w2,
              fpsg_stream_t stream);
 
+/* ---- K21: repulsion regulariser of a cloud against itself --------------------------------------------
+ * PU-Net's repulsion term (Yu et al., CVPR 2018): every point is charged for its k nearest neighbours in its OWN
+ * cloud, eta(r) w(r) = -r exp(-r^2 / h^2).  The published code is not pinned; the definition below is the specification
+ * (parity UNPINNED).  Inputs: B clouds xyz [N,3] fp32, 1 <= k <= FPSG_REPULSION_MAX_K, k <= N - 1, h > 0.
+ *   d2(i,j)  = fma(dz,dz, fma(dy,dy, dx*dx)), dx = x_j - x_i (K1's sq_dist: bitwise symmetric in i and j)
+ *   K(i)     = the k indices j != i with the smallest (d2(i,j), j) in lexicographic order (ties: the lower index),
+ *              stored nearest first: nbr_idx [B,N,k] int32, nbr_d2 [B,N,k] fp32.  j == i is skipped by index, so a
+ *              duplicate of point i is a neighbour of i at distance 0
+ *   r        = sqrt(d2) where d2 > 1e-12, else 1e-6          (= sqrt(max(d2, 1e-12)))
+ *   rho(d2)  = -(r * exp(-d2 / h^2))
+ *   rho'(d2) = -(e / (2 r) - (e r) / h^2), e = exp(-d2 / h^2), where d2 > 1e-12; 0 elsewhere (duplicates push nobody)
+ *   value[b] = (1 / (N k)) sum_i sum_{j in K(i)} rho(d2(i,j))                  in [-h / sqrt(2 e), 0]
+ *   gxyz[j]  = gvalue[b] (2 / (N k)) [ sum_{m in K(j)} rho'(d2(j,m)) (x_j - x_m)
+ *                                      + sum_{i : j in K(i)} rho'(d2(i,j)) (x_j - x_i) ]
+ * (the lists are piecewise constant: no gradient flows through the selection).  fp32 throughout: 1 / h^2 is formed
+ * in double on the host, rounded to fp32 and kept finite; exp(-x) is the hardware base-2 exponential of
+ * -((d2 * (1/h^2)) * log2(e)) (a result below 2^-126 is +0); sqrt and 1 / r are the hardware instructions.
+ * Orders: a point's k terms of the value are added as a balanced tree over eight slots (absent: +0); 64 consecutive
+ * points by the balanced tree over the position; 256 consecutive points as (w0 + w1) + (w2 + w3); these partials in
+ * ascending order from +0; the product with 1 / (N k) (rounded to fp32) last.  A point's gradient starts from +0,
+ * takes its own k terms in list order, then the reverse terms in ascending i, each as fma(rho', x_j - x_other, acc);
+ * the product with gvalue[b] * (2 / (N k)) last.  gxyz is written, not accumulated.
+ * The backward takes the lists as written by the forward: j is in K(i) exactly where (d2(i,j), j) <=
+ * (nbr_d2[i,k-1], nbr_idx[i,k-1]) lexicographically and i != j, with d2 recomputed; a row whose k-th index is outside
+ * [0, N) holds nobody, and an own index outside [0, N) is skipped: no index is dereferenced unchecked.  Coordinates
+ * that are not finite give unspecified values for their cloud, never an access out of bounds.
+ * Bitwise the same on every run, whatever B is and wherever the cloud sits in the batch; no atomics.  The forward is
+ * two launches (the sweep; one thread per cloud adds the partials), the backward one; the workspace holds the
+ * forward's partials.  The calls only enqueue work on `stream` (no host read; they can be captured in a graph).
+ * Errors, all before any launch, shape and limit checks in front of the pointer checks: FPSG_E_SHAPE for B < 1, k
+ * outside 1..8, N < k + 1, h not positive and finite, or a workspace smaller than fpsg_repulsion_workspace_bytes;
+ * FPSG_E_LIMIT for N > FPSG_REPULSION_MAX_N; FPSG_E_NULL for a null pointer; FPSG_E_ALIGN for a misaligned one.
+ * fpsg_repulsion_workspace_bytes returns 0 for a shape the entries refuse.
+ */
+#define FPSG_REPULSION_MAX_N 16384
+#define FPSG_REPULSION_MAX_K 8
+size_t fpsg_repulsion_workspace_bytes(int B, int N, int k);
+int fpsg_repulsion_fwd(const float* xyz, int B, int N, int k, float h, int32_t* nbr_idx, float* nbr_d2, float* value,
+                       void* workspace, size_t workspace_bytes, fpsg_stream_t stream);
+int fpsg_repulsion_bwd(const float* xyz, const int32_t* nbr_idx, const float* nbr_d2, const float* gvalue, int B, int N,
+                       int k, float h, float* gxyz, fpsg_stream_t stream);
+
 /* ---- K4b: fused EdgeConv (gather + BatchNorm statistics + max over k) -----------------
  * Replaces the chain get_graph_feature -> Conv2d 1x1 -> BatchNorm2d -> LeakyReLU -> max_k of
  * src/dgcnn/model.py:23-42,53-56,63-76 without materialising [B,2C,N,k].  The caller first
