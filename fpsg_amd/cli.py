@@ -20,6 +20,7 @@ those distances and the Hausdorff distance, per class), ``--pc_dist dcd`` with `
 density-aware Chamfer distance, K18), ``--dcd [ALPHA]`` (evaluation: that distance per class), ``--pc_dist sinkhorn``
 with ``--sinkhorn_blur`` / ``--sinkhorn_diameter`` (training on the Sinkhorn divergence the evaluation prints as EMD, K19),
 ``--clip_grad_norm X`` (training: the 2-norm of every step's mean gradient clipped to X, K20, and one extra line per epoch),
+``--pc_dist swd`` with ``--swd_n_proj`` / ``--swd_directions`` (training on the sliced Wasserstein distance, K22),
 ``--repulsion_weight W`` with ``--repulsion_k`` / ``--repulsion_h`` (training: W times the repulsion term of the decoded
 clouds, K21, added to whichever ``--pc_dist`` is trained, and one extra line per epoch).
 """
@@ -34,7 +35,7 @@ from torch.utils.data import DataLoader
 
 from . import eval_report
 from .few_shot import check_repulsion_weight
-from .metrics import SINKHORN_TRAIN_DIAMETER, check_repulsion_options, check_sinkhorn_option
+from .metrics import SINKHORN_TRAIN_DIAMETER, check_repulsion_options, check_sinkhorn_option, check_swd_options
 from .episodes import EpisodicBatchSampler, SequentialBatchSampler, SyntheticFewShot
 
 
@@ -87,7 +88,7 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--lr", type=float, default=1e-3)
     g.add_argument("--lr_decay", type=float, default=350)
     g.add_argument("--resume", type=int, default=-1)
-    g.add_argument("--pc_dist", type=str, default="cd", choices=["cd", "emd", "dcd", "sinkhorn"])
+    g.add_argument("--pc_dist", type=str, default="cd", choices=["cd", "emd", "dcd", "sinkhorn", "swd"])
     g.add_argument("--dcd_alpha", type=float, default=1000.0,
                    help="With --pc_dist dcd: the factor on the squared nearest-neighbour distance inside the exponential "
                         "of the density-aware Chamfer distance [default: 1000];")
@@ -99,6 +100,12 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
                         "the diagonal of [-1,1]^3].  The evaluation's EMD takes each item's own bounding-box diagonal "
                         "instead, so its value differs slightly (under 1 %% on unit-ball clouds); a fixed one keeps the "
                         "training step free of host reads;")
+    g.add_argument("--swd_n_proj", type=int, default=64, metavar="L",
+                   help="With --pc_dist swd: the number of directions the sliced Wasserstein distance projects on, "
+                        "1..1024 [default: 64];")
+    g.add_argument("--swd_directions", type=str, default="random", metavar="{random,fixed}",
+                   help="With --pc_dist swd: 'random' draws fresh unit vectors for every loss, 'fixed' uses one Fibonacci "
+                        "lattice on the sphere throughout [default: random];")
     g.add_argument("--clip_grad_norm", type=_clip_norm, default=0.0, metavar="X",
                    help="Clip the 2-norm of every optimizer step's mean gradient to X [default: 0 = off]; prints the "
                         "largest norm and the number of clipped steps after every epoch;")
@@ -142,6 +149,11 @@ def validate(opt) -> None:
                 check_sinkhorn_option(getattr(opt, flag), flag)
             except ValueError as e:
                 raise SystemExit(f"--{e}") from None
+    if getattr(opt, "swd_n_proj", None) is not None:
+        try:
+            check_swd_options(opt.swd_n_proj, getattr(opt, "swd_directions", "random"))
+        except ValueError as e:
+            raise SystemExit(f"--swd_{e}") from None
     if getattr(opt, "repulsion_weight", None) is not None:
         try:
             check_repulsion_weight(opt.repulsion_weight)

@@ -31,7 +31,8 @@ def default_options(**overrides) -> argparse.Namespace:
         support_factor=1.0, query_factor=1.0, intra_recon=False, num_clusters=4, ori_dim=2,
         raw_dim=3, num_nodes=4, device="cuda", bottleneck_size=1536, template_type="SQUARE",
         activation="relu", aggregate="single", pc_dist="cd", lr=1e-3, lr_decay=350, SGD=False,
-        n_way=1, n_shot=20, n_query=0, clip_grad_norm=0.0, repulsion_weight=0.0, repulsion_k=4, repulsion_h=0.03)
+        n_way=1, n_shot=20, n_query=0, clip_grad_norm=0.0, repulsion_weight=0.0, repulsion_k=4, repulsion_h=0.03,
+        swd_n_proj=64, swd_directions="random")
     for k, v in overrides.items():
         setattr(opt, k, v)
     return opt
@@ -53,7 +54,9 @@ def build_model(opt) -> ImgPCProtoNet:
                          sinkhorn_blur=getattr(opt, "sinkhorn_blur", 0.05),
                          sinkhorn_diameter=getattr(opt, "sinkhorn_diameter", SINKHORN_TRAIN_DIAMETER),
                          repulsion_weight=getattr(opt, "repulsion_weight", 0.0),
-                         repulsion_k=getattr(opt, "repulsion_k", 4), repulsion_h=getattr(opt, "repulsion_h", 0.03))
+                         repulsion_k=getattr(opt, "repulsion_k", 4), repulsion_h=getattr(opt, "repulsion_h", 0.03),
+                         swd_n_proj=getattr(opt, "swd_n_proj", 64),
+                         swd_directions=getattr(opt, "swd_directions", "random"))
 
 
 def build_optimizer(model, opt):

@@ -21,7 +21,8 @@ import torch
 import torch.nn as nn
 
 from .metrics import (SINKHORN_TRAIN_DIAMETER, chamfer_distance, check_dcd_alpha, check_repulsion_options,
-                      check_sinkhorn_option, dcd, emd_loss, episode_chamfer_losses, repulsion_loss, sinkhorn_loss)
+                      check_sinkhorn_option, check_swd_options, dcd, emd_loss, episode_chamfer_losses, repulsion_loss,
+                      sinkhorn_loss, swd_directions, swd_loss)
 from .utils import emd_wrapper
 
 _AGGREGATOR = ["single", "multi", "mask_single", "mask_multi"]
@@ -75,7 +76,7 @@ class ImgPCProtoNet(nn.Module):
     def __init__(self, img_encoder, pc_encoder, pc_decoder, mask_learner=None, query_factor=1.0,
                  support_factor=1.0, metric="cd", intra_support=False, aggregate="single", dcd_alpha=1000.0,
                  sinkhorn_blur=0.05, sinkhorn_diameter=SINKHORN_TRAIN_DIAMETER, repulsion_weight=0.0, repulsion_k=4,
-                 repulsion_h=0.03):
+                 repulsion_h=0.03, swd_n_proj=64, swd_directions="random"):
         super().__init__()
         self.img_encoder = img_encoder
         self.pc_encoder = pc_encoder
@@ -103,13 +104,19 @@ class ImgPCProtoNet(nn.Module):
             self.sinkhorn_blur = check_sinkhorn_option(sinkhorn_blur, "sinkhorn_blur")
             self.sinkhorn_diameter = check_sinkhorn_option(sinkhorn_diameter, "sinkhorn_diameter")
             self.pc_metric = self._sinkhorn_metric
+        elif metric == "swd":
+            # the sliced Wasserstein distance (K22): sort-and-match on swd_n_proj directions, exact gradient.  "fixed": the
+            # Fibonacci lattice, built once per device; "random": fresh unit vectors per loss call, drawn on the device
+            self.swd_n_proj, self.swd_directions = check_swd_options(swd_n_proj, swd_directions)
+            self._swd_lattice = {}
+            self.pc_metric = self._swd_metric
         else:
             raise NotImplementedError(
                 f"Found unsupported point cloud reconstruction metrics: {metric}")
         # evaluation-only distance (reference few_shot.py:168); an attribute so that a test
         # can drive the module on CPU with the oracle's implementations
         self.emd_metric = emd_wrapper
-        self._batched_pairs = metric in ("dcd", "sinkhorn")      # one call over the Q + S pairs (below)
+        self._batched_pairs = metric in ("dcd", "sinkhorn", "swd")      # one call over the Q + S pairs (below)
         # the repulsion regulariser (K21) on the decoded clouds, added to whichever distance is trained; 0: off, and
         # the loss is what it is without these arguments, launch for launch
         self.repulsion_weight = check_repulsion_weight(repulsion_weight)
@@ -122,6 +129,16 @@ class ImgPCProtoNet(nn.Module):
 
     def _sinkhorn_metric(self, a, b):
         return sinkhorn_loss(a, b, blur=self.sinkhorn_blur, diameter=self.sinkhorn_diameter)
+
+    def _swd_metric(self, a, b):
+        if self.swd_directions == "fixed":
+            dirs = self._swd_lattice.get(a.device)
+            if dirs is None:
+                dirs = self._swd_lattice[a.device] = swd_directions(self.swd_n_proj, a.device)
+        else:       # no host read: the draw and its normalisation are device work (and replay with fresh numbers in a graph)
+            dirs = torch.randn((self.swd_n_proj, 3), dtype=torch.float32, device=a.device)
+            dirs = dirs / dirs.norm(dim=1, keepdim=True)
+        return swd_loss(a, b, dirs)
 
     # ------------------------------------------------------------------ shared forward
     def _encode(self, img_s, img_q, img_ad, pc_s, pc_ad):
@@ -251,7 +268,7 @@ class ImgPCProtoNet(nn.Module):
                 cd = self.pc_metric(syn, ref)
                 loss_rec_q, loss_rec_s = cd[:n_q].sum(), cd[n_q:].sum()
             elif self._batched_pairs and syn_q.shape[1:] == syn_s.shape[1:] and ref_q.shape[1:] == ref_s.shape[1:]:
-                # as the Chamfer branch: ONE K1 + K18 (or K2b + K19, fixed diameter) call over the Q + S pairs (a pair's
+                # as the Chamfer branch: ONE K1 + K18 (or K2b + K19, fixed diameter; or K22) call over the Q + S pairs (a pair's
                 # value does not depend on the batch, so this is only fewer launches); the fused K1l sums are Chamfer's alone
                 if syn is None:
                     syn = torch.cat([syn_q, syn_s])

@@ -841,6 +841,140 @@ def repulsion_loss(p: torch.Tensor, k: int = 4, h: float = 0.03, return_info: bo
     return (out, info) if return_info else out
 
 
+SWD_MAX_N = 2048                # FPSG_SWD_MAX_N (include/fpsg_hip.h)
+SWD_MAX_L = 1024                # FPSG_SWD_MAX_L
+SWD_DIRECTION_MODES = ("random", "fixed")
+
+
+def swd_directions(L: int, device=None) -> torch.Tensor:
+    """The deterministic Fibonacci lattice of ``L`` unit vectors ``[L,3]`` fp32 on the sphere: ``z_i = 1 - 2 (i + 1/2) / L``,
+    ``phi_i = i pi (3 - sqrt 5)``, ``(sqrt(1 - z^2) cos phi, sqrt(1 - z^2) sin phi, z)``, formed in float64 on the host and
+    rounded once.  Its second moment is near isotropic (``3 / L sum theta theta^T`` within 3e-3 of the identity at
+    ``L = 64``), so the sliced distance over it weighs every axis alike."""
+    if isinstance(L, bool) or not isinstance(L, numbers.Integral) or not 1 <= int(L) <= SWD_MAX_L:
+        raise ValueError(f"L must be an integer in 1..{SWD_MAX_L}, got {L!r}")
+    i = torch.arange(int(L), dtype=torch.float64)
+    z = 1.0 - 2.0 * (i + 0.5) / int(L)
+    phi = i * (math.pi * (3.0 - math.sqrt(5.0)))
+    rho = torch.sqrt(1.0 - z * z)
+    dirs = torch.stack([rho * torch.cos(phi), rho * torch.sin(phi), z], dim=1).to(torch.float32)
+    return dirs if device is None else dirs.to(device)
+
+
+def check_swd_options(n_proj, directions):
+    """``(n_proj, directions)`` of the sliced Wasserstein loss as a Python int and str: ``n_proj`` an integer in
+    1..1024, ``directions`` ``"random"`` or ``"fixed"`` (``ValueError`` naming the argument otherwise)."""
+    if isinstance(n_proj, bool) or not isinstance(n_proj, numbers.Integral):
+        raise ValueError(f"n_proj must be an integer in 1..{SWD_MAX_L}, got {n_proj!r}")
+    if not 1 <= int(n_proj) <= SWD_MAX_L:
+        raise ValueError(f"n_proj must be in 1..{SWD_MAX_L}, got {n_proj!r}")
+    if not isinstance(directions, str) or directions not in SWD_DIRECTION_MODES:
+        raise ValueError(f"directions must be one of {SWD_DIRECTION_MODES}, got {directions!r}")
+    return int(n_proj), directions
+
+
+def _check_swd_inputs(p1, p2, directions):
+    for name, t in (("p1", p1), ("p2", p2), ("directions", directions)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: expected a torch.Tensor, got {type(t)}")
+    if p1.dim() != 3 or p2.dim() != 3 or p1.size(2) != 3 or p2.size(2) != 3:
+        raise ValueError(f"expected two [B,N,3] clouds, got {tuple(p1.shape)} and {tuple(p2.shape)}")
+    if directions.dim() != 2 or directions.size(1) != 3 or not 1 <= directions.size(0) <= SWD_MAX_L:
+        raise ValueError(f"directions must be [L,3] with L in 1..{SWD_MAX_L}, got {tuple(directions.shape)}")
+    if p1.size(0) != p2.size(0):
+        raise ValueError(f"batch mismatch: {p1.size(0)} vs {p2.size(0)}")
+    if p1.size(1) != p2.size(1):
+        raise ValueError(f"the sliced Wasserstein distance matches rank by rank: both clouds need the same number of "
+                         f"points, got {p1.size(1)} and {p2.size(1)}")
+    if p1.size(0) == 0 or p1.size(1) == 0:
+        raise ValueError(f"empty point clouds are not supported (got {tuple(p1.shape)} and {tuple(p2.shape)})")
+    if p1.size(1) > SWD_MAX_N:
+        raise ValueError(f"swd supports at most {SWD_MAX_N} points per cloud, got {p1.size(1)}")
+    for name, t in (("p1", p1), ("p2", p2), ("directions", directions)):
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: expected dtype torch.float32, got {t.dtype}")
+        if t.device.type != "cuda":
+            raise ValueError(f"{name}: tensor is on '{t.device}'; swd runs on a ROCm GPU only (no CPU fallback)")
+        if t.device != p1.device:
+            raise ValueError(f"device mismatch: {name} is on {t.device}, p1 on {p1.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: tensor must be contiguous")
+
+
+def _swd_call(p1, p2, directions, need1, need2, matching):
+    """One ``fpsg_swd`` call: ``(value [B], g1 | None, g2 | None, perm1 | None, perm2 | None)``."""
+    B, N, _ = p1.shape
+    L = directions.size(0)
+    lib = _hip.load()
+    dev = p1.device
+    value = torch.empty((B,), dtype=torch.float32, device=dev)
+    g1 = torch.empty_like(p1) if need1 else None
+    g2 = torch.empty_like(p2) if need2 else None
+    m1 = torch.empty((B, L, N), dtype=torch.int32, device=dev) if matching else None
+    m2 = torch.empty((B, L, N), dtype=torch.int32, device=dev) if matching else None
+    ws_bytes = lib.fpsg_swd_workspace_bytes(B, N, L)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _probe("swd", B, N, N):
+        rc = lib.fpsg_swd(_hip.ptr(p1), _hip.ptr(p2), _hip.ptr(directions), B, N, L, _hip.ptr(value),
+                          _hip.ptr(g1) if need1 else None, _hip.ptr(g2) if need2 else None,
+                          _hip.ptr(m1) if matching else None, _hip.ptr(m2) if matching else None, _hip.ptr(ws), ws_bytes,
+                          _hip.stream_of(p1))
+    _hip.check(rc, "fpsg_swd")
+    return value, g1, g2, m1, m2
+
+
+class _SwdLoss(torch.autograd.Function):
+    """K22 in one call: the distance ``[B]`` and, for the inputs that need them, its gradients, cached for the backward."""
+
+    @staticmethod
+    def forward(ctx, p1, p2, directions):
+        need1, need2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        value, g1, g2, _, _ = _swd_call(p1, p2, directions, need1, need2, False)
+        ctx.grads = (g1, g2)
+        return value
+
+    @staticmethod
+    def backward(ctx, g):
+        g1, g2 = ctx.grads
+        gc = g.reshape(-1, 1, 1)
+        return (None if g1 is None else g1 * gc), (None if g2 is None else g2 * gc), None
+
+
+def swd_loss(p1: torch.Tensor, p2: torch.Tensor, directions: torch.Tensor) -> torch.Tensor:
+    """The sliced Wasserstein distance ``[B]`` fp32 of the clouds ``p1, p2 [B,N,3]`` (the SAME ``N``) under the directions
+    ``[L,3]`` (K22, HIP; the definition is in ``include/fpsg_hip.h``): both clouds are projected on every direction, each
+    projection is sorted and the points are matched rank by rank; the value is the mean squared difference over the
+    ``L N`` matched keys.  Directions are used as given (``swd_directions`` gives unit vectors).
+
+    Differentiable in ``p1`` and ``p2`` with the matchings held constant -- the exact gradient wherever the keys of a
+    projection are distinct.  ONE kernel call in the forward forms the gradients of the inputs that require grad; the
+    backward multiplies them by the upstream gradient.  No gradient flows to ``directions``.  Bitwise the same on every
+    run and independent of the batch (no atomics); the value does not change when a cloud's points are permuted.  The call
+    only enqueues: it can be captured in a graph.
+
+    ``ValueError`` for shapes that are not ``[B,N,3]`` / ``[L,3]``, unequal ``N``, ``N`` above 2048, ``L`` above 1024, and
+    tensors that are not contiguous fp32 on one ROCm device.  There is no CPU path."""
+    _check_swd_inputs(p1, p2, directions)
+    return _SwdLoss.apply(p1, p2, directions.detach())
+
+
+@torch.no_grad()
+def swd(p1: torch.Tensor, p2: torch.Tensor, n_proj: int = 128, directions: torch.Tensor | None = None,
+        return_matching: bool = False):
+    """``swd_loss`` as a metric, no grad: ``[B]``.  ``directions=None``: the Fibonacci lattice of ``n_proj`` directions
+    (``swd_directions``); a ``[L,3]`` tensor is used as given and ``n_proj`` is ignored.  ``return_matching=True``: returns
+    ``(value, perm1, perm2)`` with the orders ``[B,L,N]`` int32 of the two clouds per direction, ascending by (key, index):
+    point ``perm1[b,l,r]`` of ``p1[b]`` is matched with point ``perm2[b,l,r]`` of ``p2[b]``."""
+    if directions is None:
+        if isinstance(n_proj, bool) or not isinstance(n_proj, numbers.Integral) or not 1 <= int(n_proj) <= SWD_MAX_L:
+            raise ValueError(f"n_proj must be an integer in 1..{SWD_MAX_L}, got {n_proj!r}")
+        directions = swd_directions(int(n_proj), p1.device if isinstance(p1, torch.Tensor) else None)
+    p1, p2 = (t.detach() if isinstance(t, torch.Tensor) else t for t in (p1, p2))
+    _check_swd_inputs(p1, p2, directions)
+    value, _, _, m1, m2 = _swd_call(p1, p2, directions.detach(), False, False, bool(return_matching))
+    return (value, m1, m2) if return_matching else value
+
+
 def softmin(x: torch.Tensor, y: torch.Tensor, h: torch.Tensor, eps: float) -> torch.Tensor:
     """``out[b,i] = -eps * logsumexp_j(h[b,j] - |x_i - y_j|^2 / (2 eps))`` (K2b), no grad."""
     _check_clouds(x, y)

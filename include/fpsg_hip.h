@@ -431,6 +431,44 @@ int fpsg_repulsion_fwd(const float* xyz, int B, int N, int k, float h, int32_t* 
 int fpsg_repulsion_bwd(const float* xyz, const int32_t* nbr_idx, const float* nbr_d2, const float* gvalue, int B, int N,
                        int k, float h, float* gxyz, fpsg_stream_t stream);
 
+/* ---- K22: sliced Wasserstein distance with its gradient and matchings ----------------------------------
+ * The squared 2-Wasserstein distance of the clouds' projections on L given directions, averaged (Bonneel et al. 2015;
+ * the cheap transport loss of the point-cloud literature).  Inputs: B pairs xyz1, xyz2 [N,3] fp32 with the SAME N,
+ * directions dirs [L,3] fp32 shared by every pair, used as given (not normalised).  DESIGN.md K22.
+ *   key      k = fl(fl(fl(x tx) + fl(y ty)) + fl(z tz)) + 0.0f      (fp32, this order; the last addition turns -0 into +0)
+ *   pi1, pi2 per pair and direction: the N points of cloud 1 (2) ascending by (key, index), ties to the lower index;
+ *            perm1 / perm2 [B,L,N] int32 hold pi1[r] / pi2[r] at rank r
+ *   d_r      = k1[pi1[r]] - k2[pi2[r]]
+ *   value[b] = 1 / (L N) sum_l sum_r d_r^2
+ *   gxyz1[b, pi1[r]] += 2 / (L N) d_r theta_l          gxyz2[b, pi2[r]] -= 2 / (L N) d_r theta_l
+ * gxyz1 / gxyz2 [B,N,3] are the gradient of value[b] with the matchings held constant (they are piecewise constant);
+ * they are written, not accumulated, and either may be NULL, as may perm1 / perm2: the other outputs keep their bits.
+ * The orders are total, so every output is determined: bitwise the same on every run, whatever B is and wherever the
+ * pair sits in the batch, and value[b] is bitwise unchanged when the points of either cloud are permuted.  Orders of
+ * the sums: the L directions are split over G = min(ceil(L / 8), 16) workgroups per pair, group g taking directions
+ * [g L / G, (g + 1) L / G).  Inside a group the thread of rank r (and r + T, T = max(64, P / 2) threads, P the power
+ * of two >= max(N, 64)) adds its d_r^2 in ascending direction, the 64 threads of a wave are added by the balanced tree
+ * over the lane, the waves in ascending order; a gradient row takes its terms d_r theta (one product, one addition
+ * each, from +0) in ascending direction.  The G partials are added in ascending g from +0 and multiplied by
+ * 1 / (L N) resp. 2 / (L N), formed in double and rounded to fp32.  No atomics.
+ * The sort is a bitonic network over P slots in LDS on 64-bit words (monotone image of the key << 32 | index); slots
+ * N .. P - 1 hold sentinels above every real word, a NaN's included, which never reach d_r, the matchings or the
+ * gradients.  Its control flow does not depend on the data: a coordinate or direction that is not finite gives
+ * non-finite or unspecified values for the pairs it touches (a NaN key sorts behind +inf, or in front of -inf with the
+ * sign bit set), never an access out of bounds, and leaves every other pair's bits alone.
+ * Two launches (the groups; the sum of their partials).  The call only enqueues work on `stream` (no host read; it can
+ * be captured in a graph).  ws: fpsg_swd_workspace_bytes(B, N, L) bytes, 4-byte aligned, contents unspecified.
+ * Errors, all before any launch: FPSG_E_SHAPE for B, N or L < 1 or a workspace that is too small; FPSG_E_LIMIT for
+ * N > FPSG_SWD_MAX_N, L > FPSG_SWD_MAX_L or B > FPSG_SWD_MAX_B; FPSG_E_NULL for a null xyz1, xyz2, dirs, value or ws;
+ * FPSG_E_ALIGN for a misaligned pointer.  fpsg_swd_workspace_bytes returns 0 for a shape the entry refuses.
+ */
+#define FPSG_SWD_MAX_N 2048
+#define FPSG_SWD_MAX_L 1024
+#define FPSG_SWD_MAX_B 65535
+size_t fpsg_swd_workspace_bytes(int B, int N, int L);
+int fpsg_swd(const float* xyz1, const float* xyz2, const float* dirs, int B, int N, int L, float* value, float* gxyz1,
+             float* gxyz2, int32_t* perm1, int32_t* perm2, void* ws, size_t ws_bytes, fpsg_stream_t stream);
+
 /* ---- K4b: fused EdgeConv (gather + BatchNorm statistics + max over k) -----------------
  * Replaces the chain get_graph_feature -> Conv2d 1x1 -> BatchNorm2d -> LeakyReLU -> max_k of
  * src/dgcnn/model.py:23-42,53-56,63-76 without materialising [B,2C,N,k].  The caller first
