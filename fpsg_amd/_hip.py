@@ -178,6 +178,12 @@ SIGNATURES = {
     "fpsg_adam_step_segments_dscale": [_c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_f32p, _c_f32p,
                                        ctypes.c_size_t, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                        _c_int, _c_f32p, _c_stream],
+    "fpsg_adam_step_ema": [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_size_t, ctypes.c_float, ctypes.c_float,
+                           ctypes.c_float, ctypes.c_float, _c_int, ctypes.c_float, _c_f32p, ctypes.c_float, _c_stream],
+    "fpsg_adam_step_segments_ema": [_c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_f32p, _c_f32p, _c_f32p,
+                                    ctypes.c_size_t, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                    _c_int, ctypes.c_float, _c_f32p, ctypes.c_float, _c_stream],
+    "fpsg_flat_swap": [_c_f32p, _c_f32p, ctypes.c_size_t, _c_stream],
     "fpsg_gemm_split_workspace_floats": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int],
     "fpsg_gemm_split": [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_long,
                         ctypes.c_long, ctypes.c_long, _c_int, _c_int, _c_f32p, ctypes.c_size_t, _c_stream],

@@ -22,7 +22,8 @@ with ``--sinkhorn_blur`` / ``--sinkhorn_diameter`` (training on the Sinkhorn div
 ``--clip_grad_norm X`` (training: the 2-norm of every step's mean gradient clipped to X, K20, and one extra line per epoch),
 ``--pc_dist swd`` with ``--swd_n_proj`` / ``--swd_directions`` (training on the sliced Wasserstein distance, K22),
 ``--repulsion_weight W`` with ``--repulsion_k`` / ``--repulsion_h`` (training: W times the repulsion term of the decoded
-clouds, K21, added to whichever ``--pc_dist`` is trained, and one extra line per epoch).
+clouds, K21, added to whichever ``--pc_dist`` is trained, and one extra line per epoch), ``--ema_decay D`` (training: an
+exponential moving average of the weights, K23, evaluated beside the raw weights and saved as ``model_epoch_N_ema.pt``).
 """
 from __future__ import annotations
 
@@ -34,6 +35,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import eval_report
+from .ema import check_ema_decay
 from .few_shot import check_repulsion_weight
 from .metrics import SINKHORN_TRAIN_DIAMETER, check_repulsion_options, check_sinkhorn_option, check_swd_options
 from .episodes import EpisodicBatchSampler, SequentialBatchSampler, SyntheticFewShot
@@ -118,6 +120,10 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--repulsion_h", type=float, default=0.03, metavar="H",
                    help="With --repulsion_weight: the bandwidth of the term, a length -- clouds live in the unit ball "
                         "[default: 0.03];")
+    g.add_argument("--ema_decay", type=float, default=0.0, metavar="D",
+                   help="Keep an exponential moving average of the weights with decay D in (0, 1), warmed up as "
+                        "min(D, (1 + t) / (10 + t)) [default: 0 = off]; every evaluation is followed by one on the "
+                        "averaged weights ([EMA] lines) and model_epoch_N_ema.pt is saved beside model_epoch_N.pt;")
     g.add_argument("--SGD", action="store_true")
     g.add_argument("--episodes_per_step", type=int, default=0,
                    help="Episodes per optimizer step over all ranks [default: one per rank];")
@@ -163,6 +169,11 @@ def validate(opt) -> None:
             check_repulsion_options(opt.repulsion_k, opt.repulsion_h)
         except ValueError as e:
             raise SystemExit(f"--repulsion_{e}") from None
+    if getattr(opt, "ema_decay", None) is not None:
+        try:
+            check_ema_decay(opt.ema_decay)
+        except ValueError as e:
+            raise SystemExit(f"--{e}") from None
     eval_report.check(opt)          # the evaluation report's options; a training namespace has none of them
 
 

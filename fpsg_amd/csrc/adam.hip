@@ -11,6 +11,9 @@
 //   v  = b2 * v + (1-b2) * g * g
 //   p -= (lr / (1-b1^t)) * m / (sqrt(v) / sqrt(1-b2^t) + eps)
 // 4 reads + 3 writes of the buffer = 28 B per parameter (2.17 GB for the 77.4 M of the full model).
+// K23 (EMA = true): a shadow copy of the parameters rides along as a fifth stream,
+//   e  = e + w * (p - e)              (the p just computed, still in registers; w = 1 - decay_t)
+// one more read and one more write, 36 B per parameter, in the same launch.
 #include "fpsg_common.h"
 
 namespace fpsg {
@@ -44,11 +47,27 @@ __device__ __forceinline__ void st4(float* p, size_t i, v4f v) {
 __device__ __forceinline__ float scale_of(float s) { return s; }
 __device__ __forceinline__ float scale_of(const float* s) { return *s; }
 
-template <typename Scale>
+// K23: the shadow's update from the parameter vector just computed
+__device__ __forceinline__ void ema4(v4f& ev, const v4f& pv, float w) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u) ev[u] = fma_rn(w, pv[u] - ev[u], ev[u]);
+}
+
+// The shadow and its weight are the kernels' LAST arguments and exist only in the EMA = true instantiations (EmaArgs =
+// float*, float): the EMA = false ones keep the argument list, the kernarg layout and the instructions they had.
+__device__ __forceinline__ float* ema_buffer() { return nullptr; }
+__device__ __forceinline__ float* ema_buffer(float* ema, float) { return ema; }
+__device__ __forceinline__ float ema_weight_of() { return 0.0f; }
+__device__ __forceinline__ float ema_weight_of(float*, float w) { return w; }
+
+template <typename Scale, bool EMA, typename... EmaArgs>
 __global__ __launch_bounds__(kAdamThreads) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                             float* __restrict__ m, float* __restrict__ v, size_t n4,
                                                             size_t n, float step_size, float b1, float b2, float eps,
-                                                            float inv_sqrt_bc2, Scale gscale_src) {
+                                                            float inv_sqrt_bc2, Scale gscale_src, EmaArgs... ema_args) {
+  static_assert(sizeof...(EmaArgs) == (EMA ? 2 : 0), "the shadow and its weight, with EMA only");
+  [[maybe_unused]] float* __restrict__ const ema = ema_buffer(ema_args...);
+  [[maybe_unused]] const float ema_w = ema_weight_of(ema_args...);
   const float gscale = scale_of(gscale_src);
   const size_t stride = (size_t)gridDim.x * kAdamThreads;
   const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
@@ -70,20 +89,32 @@ __global__ __launch_bounds__(kAdamThreads) void adam_kernel(float* __restrict__ 
     const v4f ga = ld4(g, i), gb = ld4(g, j);
     v4f ma = ld4(m, i), mb = ld4(m, j);
     v4f va = ld4(v, i), vb = ld4(v, j);
+    [[maybe_unused]] v4f ea, eb;
+    if constexpr (EMA) { ea = ld4(ema, i); eb = ld4(ema, j); }
     update(pa, ga, ma, va);
     update(pb, gb, mb, vb);
     st4(p, i, pa); st4(m, i, ma); st4(v, i, va);
     st4(p, j, pb); st4(m, j, mb); st4(v, j, vb);
+    if constexpr (EMA) {
+      ema4(ea, pa, ema_w); ema4(eb, pb, ema_w);
+      st4(ema, i, ea); st4(ema, j, eb);
+    }
   }
   if (i < n4) {
     v4f pv = ld4(p, i);
     const v4f gv = ld4(g, i);
     v4f mv = ld4(m, i);
     v4f vv = ld4(v, i);
+    [[maybe_unused]] v4f ev;
+    if constexpr (EMA) ev = ld4(ema, i);
     update(pv, gv, mv, vv);
     st4(p, i, pv);
     st4(m, i, mv);
     st4(v, i, vv);
+    if constexpr (EMA) {
+      ema4(ev, pv, ema_w);
+      st4(ema, i, ev);
+    }
   }
   // tail (n not a multiple of 4)
   if (blockIdx.x == 0) {
@@ -92,7 +123,13 @@ __global__ __launch_bounds__(kAdamThreads) void adam_kernel(float* __restrict__ 
       const float mm = fma_rn(omb1, gg - m[i], m[i]);
       const float vq = fma_rn(omb2 * gg, gg, b2 * v[i]);
       const float denom = fma_rn(__fsqrt_rn(vq), inv_sqrt_bc2, eps);
-      p[i] = fma_rn(-step_size, mm / denom, p[i]);
+      if constexpr (EMA) {
+        const float pn = fma_rn(-step_size, mm / denom, p[i]);
+        p[i] = pn;
+        ema[i] = fma_rn(ema_w, pn - ema[i], ema[i]);
+      } else {
+        p[i] = fma_rn(-step_size, mm / denom, p[i]);
+      }
       m[i] = mm;
       v[i] = vq;
     }
@@ -334,12 +371,16 @@ __global__ __launch_bounds__(kAdamThreads) void flat_accumulate_tables_kernel(fl
   }
 }
 
-template <typename Scale>
+template <typename Scale, bool EMA, typename... EmaArgs>
 __global__ __launch_bounds__(kAdamThreads) void adam_ptr_kernel(float* __restrict__ p, const float* const* __restrict__ gtab,
                                                                 const long long* __restrict__ seg_off, int nseg,
                                                                 float* __restrict__ m, float* __restrict__ v, size_t n4,
                                                                 size_t n, float step_size, float b1, float b2,
-                                                                float eps, float inv_sqrt_bc2, Scale gscale_src) {
+                                                                float eps, float inv_sqrt_bc2, Scale gscale_src,
+                                                                EmaArgs... ema_args) {
+  static_assert(sizeof...(EmaArgs) == (EMA ? 2 : 0), "the shadow and its weight, with EMA only");
+  [[maybe_unused]] float* __restrict__ const ema = ema_buffer(ema_args...);
+  [[maybe_unused]] const float ema_w = ema_weight_of(ema_args...);
   const float gscale = scale_of(gscale_src);
   const size_t stride = (size_t)gridDim.x * kAdamThreads;
   const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
@@ -347,12 +388,14 @@ __global__ __launch_bounds__(kAdamThreads) void adam_ptr_kernel(float* __restric
   // whole vectors, two per trip: six flat loads out, two table searches, two gradient loads, then the arithmetic
   // (one vector per trip: the search and the gradient load sat between the flat loads and their use every 16 bytes)
   for (; j + stride < n4; j += 2 * stride) {
+    [[maybe_unused]] v4f ev[2];
     v4f pv[2], mv[2], vv[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       pv[u] = reinterpret_cast<const v4f*>(p)[j + u * stride];
       mv[u] = reinterpret_cast<const v4f*>(m)[j + u * stride];
       vv[u] = reinterpret_cast<const v4f*>(v)[j + u * stride];
+      if constexpr (EMA) ev[u] = reinterpret_cast<const v4f*>(ema)[j + u * stride];
     }
     float gg[2][4];
 #pragma unroll
@@ -370,6 +413,10 @@ __global__ __launch_bounds__(kAdamThreads) void adam_ptr_kernel(float* __restric
       reinterpret_cast<v4f*>(p)[j + u * stride] = pv[u];
       reinterpret_cast<v4f*>(m)[j + u * stride] = mv[u];
       reinterpret_cast<v4f*>(v)[j + u * stride] = vv[u];
+      if constexpr (EMA) {
+        ema4(ev[u], pv[u], ema_w);
+        reinterpret_cast<v4f*>(ema)[j + u * stride] = ev[u];
+      }
     }
   }
   for (; j < n4 + 1; j += stride) {
@@ -377,11 +424,13 @@ __global__ __launch_bounds__(kAdamThreads) void adam_ptr_kernel(float* __restric
     const int cnt = j < n4 ? 4 : (int)(n - 4 * n4);          // the last "vector" is the tail
     if (cnt == 0) break;
     // the flat streams first: their loads fly while the table is searched and the gradient fetched
+    [[maybe_unused]] v4f ev;
     v4f pv = {0.0f, 0.0f, 0.0f, 0.0f}, mv = pv, vv = pv;
     if (cnt == 4) {
       pv = reinterpret_cast<const v4f*>(p)[j];
       mv = reinterpret_cast<const v4f*>(m)[j];
       vv = reinterpret_cast<const v4f*>(v)[j];
+      if constexpr (EMA) ev = reinterpret_cast<const v4f*>(ema)[j];
     }
     float gg[4];
     gather_grad4(gtab, seg_off, nseg, i, cnt, gg);
@@ -397,6 +446,10 @@ __global__ __launch_bounds__(kAdamThreads) void adam_ptr_kernel(float* __restric
       reinterpret_cast<v4f*>(p)[j] = pv;
       reinterpret_cast<v4f*>(m)[j] = mv;
       reinterpret_cast<v4f*>(v)[j] = vv;
+      if constexpr (EMA) {
+        ema4(ev, pv, ema_w);
+        reinterpret_cast<v4f*>(ema)[j] = ev;
+      }
     } else {
       for (int u = 0; u < cnt; ++u) {
         const size_t e = (size_t)i + u;
@@ -404,7 +457,13 @@ __global__ __launch_bounds__(kAdamThreads) void adam_ptr_kernel(float* __restric
         const float mm = fma_rn(omb1, gq - m[e], m[e]);
         const float vq = fma_rn(omb2 * gq, gq, b2 * v[e]);
         const float denom = fma_rn(__fsqrt_rn(vq), inv_sqrt_bc2, eps);
-        p[e] = fma_rn(-step_size, mm / denom, p[e]);
+        if constexpr (EMA) {
+          const float pn = fma_rn(-step_size, mm / denom, p[e]);
+          p[e] = pn;
+          ema[e] = fma_rn(ema_w, pn - ema[e], ema[e]);
+        } else {
+          p[e] = fma_rn(-step_size, mm / denom, p[e]);
+        }
         m[e] = mm;
         v[e] = vq;
       }
@@ -525,6 +584,26 @@ __global__ __launch_bounds__(kAdamThreads) void grad_clip_finalize_kernel(const 
   }
 }
 
+// K23: a <-> b in place, one vector of each per thread and trip (two reads, two writes per element, no temporary buffer)
+constexpr size_t kSwapBlocksMax = 1u << 20;
+
+__global__ __launch_bounds__(kAdamThreads) void flat_swap_kernel(float* __restrict__ a, float* __restrict__ b, size_t n4,
+                                                                 size_t n) {
+  const size_t stride = (size_t)gridDim.x * kAdamThreads;
+  for (size_t i = (size_t)blockIdx.x * kAdamThreads + threadIdx.x; i < n4; i += stride) {
+    const v4f av = ld4(a, i), bv = ld4(b, i);
+    st4(a, i, bv);
+    st4(b, i, av);
+  }
+  if (blockIdx.x == 0) {
+    for (size_t i = n4 * 4 + threadIdx.x; i < n; i += kAdamThreads) {
+      const float av = a[i], bv = b[i];
+      a[i] = bv;
+      b[i] = av;
+    }
+  }
+}
+
 // hyper-parameters of a step as the kernels take them (bias corrections in double, as torch does for python-scalar steps)
 struct AdamConsts { float step_size, inv_sqrt_bc2; };
 inline AdamConsts adam_consts(float lr, float beta1, float beta2, int step) {
@@ -533,9 +612,10 @@ inline AdamConsts adam_consts(float lr, float beta1, float beta2, int step) {
   return {(float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
 }
 
-template <typename Scale>
+template <typename Scale, bool EMA = false>
 int launch_adam(const char* what, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
-                float beta1, float beta2, float eps, int step, Scale scale, fpsg_stream_t stream) {
+                float beta1, float beta2, float eps, int step, Scale scale, fpsg_stream_t stream, float* ema = nullptr,
+                float ema_w = 0.0f) {
   const AdamConsts c = adam_consts(lr, beta1, beta2, step);
   const size_t n4 = n / 4;
   size_t blocks = (n4 + kAdamThreads - 1) / kAdamThreads;
@@ -544,22 +624,34 @@ int launch_adam(const char* what, float* param, const float* grad, float* exp_av
   // this one 356-389 us for the model's 77.4 M parameters (0.59 -> 0.64-0.75 of the HBM peak) -- a workgroup's 4 KB pieces of
   // the seven streams stay next to its neighbours' in time, whatever the residency.  (2 / 4 vectors per thread: 361-408 us.)
   if (blocks == 0) blocks = 1;
-  hipLaunchKernelGGL((adam_kernel<Scale>), dim3((unsigned)blocks), dim3(kAdamThreads), 0, static_cast<hipStream_t>(stream),
-                     param, grad, exp_avg, exp_avg_sq, n4, n, c.step_size, beta1, beta2, eps, c.inv_sqrt_bc2, scale);
+  if constexpr (EMA) {
+    hipLaunchKernelGGL((adam_kernel<Scale, true, float*, float>), dim3((unsigned)blocks), dim3(kAdamThreads), 0,
+                       static_cast<hipStream_t>(stream), param, grad, exp_avg, exp_avg_sq, n4, n, c.step_size, beta1, beta2,
+                       eps, c.inv_sqrt_bc2, scale, ema, ema_w);
+  } else {
+    hipLaunchKernelGGL((adam_kernel<Scale, false>), dim3((unsigned)blocks), dim3(kAdamThreads), 0, static_cast<hipStream_t>(stream),
+                       param, grad, exp_avg, exp_avg_sq, n4, n, c.step_size, beta1, beta2, eps, c.inv_sqrt_bc2, scale);
+  }
   return launch_status(what);
 }
 
-template <typename Scale>
+template <typename Scale, bool EMA = false>
 int launch_adam_segments(const char* what, float* param, const float* const* grad_ptrs, const long long* seg_off, int nseg,
                          float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2, float eps,
-                         int step, Scale scale, fpsg_stream_t stream) {
+                         int step, Scale scale, fpsg_stream_t stream, float* ema = nullptr, float ema_w = 0.0f) {
   const AdamConsts c = adam_consts(lr, beta1, beta2, step);
   const size_t n4 = n / 4;
   size_t blocks = (n4 + 1 + kAdamThreads - 1) / kAdamThreads;
   // no grid-stride cap, as adam_kernel (c3 same box, three alternating pairs: 43.99-44.01 -> 44.01-44.14 episodes/s)
-  hipLaunchKernelGGL((adam_ptr_kernel<Scale>), dim3((unsigned)blocks), dim3(kAdamThreads), 0,
-                     static_cast<hipStream_t>(stream), param, grad_ptrs, seg_off, nseg, exp_avg, exp_avg_sq, n4, n,
-                     c.step_size, beta1, beta2, eps, c.inv_sqrt_bc2, scale);
+  if constexpr (EMA) {
+    hipLaunchKernelGGL((adam_ptr_kernel<Scale, true, float*, float>), dim3((unsigned)blocks), dim3(kAdamThreads), 0,
+                       static_cast<hipStream_t>(stream), param, grad_ptrs, seg_off, nseg, exp_avg, exp_avg_sq, n4, n,
+                       c.step_size, beta1, beta2, eps, c.inv_sqrt_bc2, scale, ema, ema_w);
+  } else {
+    hipLaunchKernelGGL((adam_ptr_kernel<Scale, false>), dim3((unsigned)blocks), dim3(kAdamThreads), 0,
+                       static_cast<hipStream_t>(stream), param, grad_ptrs, seg_off, nseg, exp_avg, exp_avg_sq, n4, n,
+                       c.step_size, beta1, beta2, eps, c.inv_sqrt_bc2, scale);
+  }
   return launch_status(what);
 }
 
@@ -623,6 +715,61 @@ extern "C" int fpsg_adam_step_dscale(float* param, const float* grad, float* exp
   FPSG_REQUIRE_PTR(grad_scale_dev);
   return launch_adam<const float*>("fpsg_adam_step_dscale", param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step,
                                    grad_scale_dev, stream);
+}
+
+// K23: what the two _ema entries check on top of the step's own checks
+#define FPSG_ADAM_CHECK_EMA(NAME)                                                                                       \
+  FPSG_REQUIRE_PTR(ema);                                                                                                \
+  FPSG_REQUIRE((reinterpret_cast<uintptr_t>(ema) & 15) == 0, FPSG_E_ALIGN, NAME ": ema must be 16-byte aligned");       \
+  FPSG_REQUIRE(ema != param && ema != exp_avg && ema != exp_avg_sq, FPSG_E_SHAPE,                                       \
+               NAME ": ema must be a buffer of its own (it is param, exp_avg or exp_avg_sq)");                          \
+  FPSG_REQUIRE(__builtin_isfinite(ema_weight) && ema_weight > 0.0f && ema_weight <= 1.0f, FPSG_E_SHAPE,                 \
+               NAME ": ema_weight must lie in (0, 1] (got %g)", (double)ema_weight);                                    \
+  FPSG_REQUIRE(grad_scale_dev == nullptr || !fpsg::misaligned4(grad_scale_dev), FPSG_E_ALIGN,                           \
+               NAME ": 'grad_scale_dev' not 4-byte aligned")
+
+extern "C" int fpsg_adam_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, size_t n,
+                                  float lr, float beta1, float beta2, float eps, int step, float grad_scale,
+                                  const float* grad_scale_dev, float ema_weight, fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_ADAM_CHECK_FLAT("fpsg_adam_step_ema");
+  FPSG_ADAM_CHECK_EMA("fpsg_adam_step_ema");
+  if (grad_scale_dev)
+    return launch_adam<const float*, true>("fpsg_adam_step_ema", param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
+                                           step, grad_scale_dev, stream, ema, ema_weight);
+  return launch_adam<float, true>("fpsg_adam_step_ema", param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step,
+                                  grad_scale, stream, ema, ema_weight);
+}
+
+extern "C" int fpsg_adam_step_segments_ema(float* param, const float* const* grad_ptrs, const long long* seg_off, int nseg,
+                                           float* exp_avg, float* exp_avg_sq, float* ema, size_t n, float lr, float beta1,
+                                           float beta2, float eps, int step, float grad_scale, const float* grad_scale_dev,
+                                           float ema_weight, fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_ADAM_CHECK_SEGMENTS("fpsg_adam_step_segments_ema");
+  FPSG_ADAM_CHECK_EMA("fpsg_adam_step_segments_ema");
+  if (grad_scale_dev)
+    return launch_adam_segments<const float*, true>("fpsg_adam_step_segments_ema", param, grad_ptrs, seg_off, nseg, exp_avg,
+                                                    exp_avg_sq, n, lr, beta1, beta2, eps, step, grad_scale_dev, stream, ema,
+                                                    ema_weight);
+  return launch_adam_segments<float, true>("fpsg_adam_step_segments_ema", param, grad_ptrs, seg_off, nseg, exp_avg,
+                                           exp_avg_sq, n, lr, beta1, beta2, eps, step, grad_scale, stream, ema, ema_weight);
+}
+
+extern "C" int fpsg_flat_swap(float* a, float* b, size_t n, fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_REQUIRE(n > 0, FPSG_E_SHAPE, "fpsg_flat_swap: n must be positive (got %zu)", n);
+  FPSG_REQUIRE_PTR(a); FPSG_REQUIRE_PTR(b);
+  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0, FPSG_E_ALIGN,
+               "fpsg_flat_swap: a and b must be 16-byte aligned");
+  FPSG_REQUIRE(a != b, FPSG_E_SHAPE, "fpsg_flat_swap: a and b are the same buffer");
+  const size_t n4 = n / 4;
+  size_t blocks = (n4 + kAdamThreads - 1) / kAdamThreads;
+  if (blocks == 0) blocks = 1;
+  if (blocks > kSwapBlocksMax) blocks = kSwapBlocksMax;
+  hipLaunchKernelGGL(flat_swap_kernel, dim3((unsigned)blocks), dim3(kAdamThreads), 0, static_cast<hipStream_t>(stream), a, b,
+                     n4, n);
+  return launch_status("fpsg_flat_swap");
 }
 
 extern "C" size_t fpsg_grad_norm_workspace_bytes(size_t n) { return fpsg::grad_norm_blocks(n) * sizeof(double); }

@@ -19,6 +19,7 @@ from . import bn_counters, eval_report, winograd
 from .few_shot import ImgPCProtoNet
 from .image_net import ImageEncoderWarpper
 from .metrics import SINKHORN_TRAIN_DIAMETER, check_dcd_alpha, check_thresholds, nearest_rows
+from .ema import WeightEma, check_ema_decay
 from .optim import FlatAdam, check_max_grad_norm
 from .point_cloud_net import PCDecoder, PCEncoder
 
@@ -32,7 +33,7 @@ def default_options(**overrides) -> argparse.Namespace:
         raw_dim=3, num_nodes=4, device="cuda", bottleneck_size=1536, template_type="SQUARE",
         activation="relu", aggregate="single", pc_dist="cd", lr=1e-3, lr_decay=350, SGD=False,
         n_way=1, n_shot=20, n_query=0, clip_grad_norm=0.0, repulsion_weight=0.0, repulsion_k=4, repulsion_h=0.03,
-        swd_n_proj=64, swd_directions="random")
+        swd_n_proj=64, swd_directions="random", ema_decay=0.0)
     for k, v in overrides.items():
         setattr(opt, k, v)
     return opt
@@ -62,9 +63,12 @@ def build_model(opt) -> ImgPCProtoNet:
 def build_optimizer(model, opt):
     """Adam(lr, betas=(.9,.999)) or SGD(weight_decay=1e-2) + StepLR(gamma=.5)
     (``trainNetwork.py:118-130``).  ``opt.clip_grad_norm`` (0: off) becomes the optimizer's ``max_grad_norm``: K20 inside
-    ``FlatAdam.step``; on any other optimizer an attribute that ``TrainStep`` reads."""
+    ``FlatAdam.step``; on any other optimizer an attribute that ``TrainStep`` reads.  ``opt.ema_decay`` (0: off) makes a
+    ``WeightEma`` of the trainable parameters, ``optimizer.ema``: K23 inside ``FlatAdam.step``; on any other optimizer
+    ``TrainStep`` updates it after the step."""
     on_gpu = next(model.parameters()).is_cuda
     max_norm = check_max_grad_norm(getattr(opt, "clip_grad_norm", None), "clip_grad_norm")
+    decay = check_ema_decay(getattr(opt, "ema_decay", None), "ema_decay")
     if not opt.SGD:
         if on_gpu and os.environ.get("FPSG_FLAT_ADAM", "1") != "0":
             # K7: parameters, gradients and moments in flat buffers, the step is one HBM stream
@@ -76,6 +80,12 @@ def build_optimizer(model, opt):
         optimizer = optim.SGD(model.parameters(), lr=opt.lr, weight_decay=1e-2)
     if max_norm is not None and not isinstance(optimizer, FlatAdam):
         optimizer.max_grad_norm = max_norm
+    if decay is not None:
+        ema = WeightEma(model.parameters(), decay)
+        if isinstance(optimizer, FlatAdam):
+            optimizer.attach_ema(ema)
+        else:
+            optimizer.ema = ema
     scheduler = optim.lr_scheduler.StepLR(optimizer, step_size=int(opt.lr_decay), gamma=0.5)
     return optimizer, scheduler
 
@@ -110,7 +120,11 @@ class TrainStep:
     optimizer -- CPU runs, ``--SGD``, ``FPSG_FLAT_ADAM=0`` -- the attached gradients hold the mean and
     ``torch.nn.utils.clip_grad_norm_`` runs on them in front of the step.  ``last_grad_norm`` / ``clip_stats()`` report
     either form.  Note that after a step with ``FlatAdam`` ``p.grad`` holds the SUM over the step's episodes (the ``1/E``
-    is folded into the step): ``clip_grad_norm_`` called on it from outside clips at ``E`` times the wrong threshold."""
+    is folded into the step): ``clip_grad_norm_`` called on it from outside clips at ``E`` times the wrong threshold.
+
+    ``optimizer.ema`` (``build_optimizer`` sets it from ``--ema_decay``; absent or None: off): the ``WeightEma`` of the
+    model's weights.  ``FlatAdam.step()`` updates it inside its own stream (K23); with any other optimizer the step ends
+    with ``ema.update()``."""
 
     def __init__(self, model, optimizer, world: int = 1, bucket_mb: float = 80.0, graph: bool = False,
                  max_grad_norm=None):
@@ -263,6 +277,9 @@ class TrainStep:
         finally:
             if isinstance(self.optimizer, FlatAdam):
                 self.optimizer.grad_scale = 1.0
+        ema = getattr(self.optimizer, "ema", None)
+        if ema is not None and not ema.fused:       # (FlatAdam's step has updated a shadow that lives in its flat buffer)
+            ema.update()
         return results
 
 

@@ -24,6 +24,11 @@ coefficient folded into the factor the step multiplies the gradient by anyway, t
 ``TrainStep``'s folded ``1/E`` the MEAN over the step's episodes, so a threshold means the same for any number of
 episodes per step.  (``p.grad`` itself holds their SUM after such a step: ``clip_grad_norm_`` called on it would clip
 at ``E`` times the wrong threshold.)  ``last_grad_norm`` and ``clip_stats()`` report what happened.
+
+``attach_ema`` (K23): an exponential moving average of the weights (``fpsg_amd.ema.WeightEma``) as a fifth flat buffer
+of the same layout, updated inside the step's one stream from the parameters it has just computed
+(``fpsg_adam_step_ema``: 36 B per parameter instead of 28, no second launch).  A step without an attached average calls
+exactly what it called before.
 """
 from __future__ import annotations
 
@@ -116,6 +121,8 @@ class FlatAdam(Optimizer):
         self.grad_scale = 1.0                  # multiplies the gradient as the step reads it (TrainStep: 1/E, then reset)
         self._step_tensor = torch.zeros((), dtype=torch.float32)       # shared by every state entry
         self._clip = None                      # K20's buffers: (workspace, out2, stats), made by the first clipped step
+        self.ema = None                        # K23: the attached WeightEma, its shadow in flat_ema
+        self.flat_ema = None
         with torch.no_grad():
             for p, off, n in self._layout:
                 view = self.flat_param[off:off + n].view(p.shape)
@@ -197,6 +204,10 @@ class FlatAdam(Optimizer):
         self._t += 1
         self._step_tensor.fill_(float(self._t))
         lib = _hip.load()
+        if self.ema is not None:
+            _hip.check(self._ema_step(lib, group, g, table), "fpsg_adam_step_ema")
+            self.ema.updates += 1
+            return loss
         if check_max_grad_norm(self.max_grad_norm, "FlatAdam: max_grad_norm") is not None:
             _hip.check(self._clipped_step(lib, group, g, table), "fpsg_adam_step (clipped)")
             return loss
@@ -242,6 +253,51 @@ class FlatAdam(Optimizer):
                                                             _hip.ptr(self._seg_off), len(self._layout),
                                                             _hip.ptr(self.flat_exp_avg), _hip.ptr(self.flat_exp_avg_sq),
                                                             n, *hyper)
+
+    # ------------------------------------------------------------------ weight average (K23)
+    def attach_ema(self, ema) -> None:
+        """``ema``: a ``fpsg_amd.ema.WeightEma`` over this optimizer's parameters.  Its shadow moves into ``flat_ema`` (the
+        layout of ``flat_param``, per-parameter views like the moments') and every later ``step()`` updates it."""
+        if self.ema is not None:
+            raise RuntimeError("FlatAdam.attach_ema: an average is already attached")
+        if len(ema.params) != len(self._layout) or any(a is not b for a, (b, _, _) in zip(ema.params, self._layout)):
+            raise ValueError("FlatAdam.attach_ema: the average was not built over this optimizer's trainable parameters")
+        self.flat_ema = torch.empty_like(self.flat_param)
+        views = []
+        with torch.no_grad():
+            for (p, off, n), e in zip(self._layout, ema.shadow):
+                view = self.flat_ema[off:off + n].view(p.shape)
+                view.copy_(e)
+                views.append(view)
+        ema._bind_flat(self.flat_param, self.flat_ema, views)
+        self.ema = ema
+
+    def _ema_step(self, lib, group, g, table) -> int:
+        """The step with the shadow's update in it: the plain and the clipped form (K20's norm and factor in front, the
+        factor then read from device memory) through the same pair of entries."""
+        n, stream = self.flat_param.numel(), _hip.stream_of(self.flat_param)
+        scale_dev = None
+        with torch.cuda.device(self.flat_param.device):
+            if check_max_grad_norm(self.max_grad_norm, "FlatAdam: max_grad_norm") is not None:
+                ws, out2, stats = self._clip_buffers()
+                tail = (float(self.grad_scale), float(self.max_grad_norm), _hip.ptr(ws), ws.numel() * 8, _hip.ptr(out2),
+                        _hip.ptr(stats), stream)
+                if g is not None:
+                    rc = lib.fpsg_grad_clip_scale(_hip.ptr(g), n, *tail)
+                else:
+                    rc = lib.fpsg_grad_clip_scale_segments(_hip.ptr(table), _hip.ptr(self._seg_off), len(self._layout), n,
+                                                           *tail)
+                if rc:
+                    return rc
+                scale_dev = _hip.ptr(out2) + 4
+            hyper = (float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]), self._t,
+                     float(self.grad_scale), scale_dev, self.ema.next_weight(), stream)
+            if g is not None:
+                return lib.fpsg_adam_step_ema(_hip.ptr(self.flat_param), _hip.ptr(g), _hip.ptr(self.flat_exp_avg),
+                                              _hip.ptr(self.flat_exp_avg_sq), _hip.ptr(self.flat_ema), n, *hyper)
+            return lib.fpsg_adam_step_segments_ema(_hip.ptr(self.flat_param), _hip.ptr(table), _hip.ptr(self._seg_off),
+                                                   len(self._layout), _hip.ptr(self.flat_exp_avg),
+                                                   _hip.ptr(self.flat_exp_avg_sq), _hip.ptr(self.flat_ema), n, *hyper)
 
     @property
     def last_grad_norm(self):

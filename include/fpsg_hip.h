@@ -1027,6 +1027,34 @@ int fpsg_adam_step_segments_dscale(float* param, const float* const* grad_ptrs, 
                                    float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
                                    float eps, int step, const float* grad_scale_dev, fpsg_stream_t stream);
 
+/* ---- K23: an exponential moving average of the weights inside K7's stream ----------------------------
+ * The Adam step of fpsg_adam_step / fpsg_adam_step_segments with a fifth flat buffer of the parameters' layout, the
+ * shadow: wherever the step stores a new parameter p it also stores
+ *   ema = fma(ema_weight, p - ema, ema)         fp32, one rounding of p - ema and one of the fma
+ * with the p it has just computed (never re-read).  ema_weight = 1 - decay_t is the caller's (fpsg_amd/ema.py: the
+ * warm-up schedule formed in double, rounded to fp32 once).  5 reads + 4 writes, 36 B per parameter, one launch; a
+ * separate pass over parameters and shadow would be a second launch and 12 B.  param, exp_avg and exp_avg_sq get the
+ * bits the entry without the shadow gives them.
+ * grad_scale_dev may be NULL: the factor on the gradient is then grad_scale, as in fpsg_adam_step.  Otherwise it is
+ * read from device memory, as in fpsg_adam_step_dscale (K20), and grad_scale is ignored: one pair of entries serves the
+ * plain and the clipped step.  Deterministic: every element is read and written by one thread, no atomics.
+ * Errors, all before any launch: those of fpsg_adam_step / fpsg_adam_step_segments; FPSG_E_NULL for a null ema;
+ * FPSG_E_ALIGN for an ema that is not 16-byte aligned or a grad_scale_dev that is not 4-byte aligned; FPSG_E_SHAPE for
+ * an ema that is param, exp_avg or exp_avg_sq, or an ema_weight that is not a finite number in (0, 1].
+ */
+int fpsg_adam_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, size_t n, float lr,
+                       float beta1, float beta2, float eps, int step, float grad_scale, const float* grad_scale_dev,
+                       float ema_weight, fpsg_stream_t stream);
+int fpsg_adam_step_segments_ema(float* param, const float* const* grad_ptrs, const long long* seg_off, int nseg,
+                                float* exp_avg, float* exp_avg_sq, float* ema, size_t n, float lr, float beta1,
+                                float beta2, float eps, int step, float grad_scale, const float* grad_scale_dev,
+                                float ema_weight, fpsg_stream_t stream);
+/* a[i] <-> b[i] for i < n, in place: one launch, two reads and two writes per element, no temporary.  It is how a model
+ * is evaluated on its averaged weights: the parameters are views of the flat buffer and captured graphs hold their
+ * addresses, so the contents move and the pointers do not.  Calling it twice restores every bit.
+ * Errors before the launch: FPSG_E_SHAPE for n = 0 or a == b, FPSG_E_NULL, FPSG_E_ALIGN (both 16-byte aligned). */
+int fpsg_flat_swap(float* a, float* b, size_t n, fpsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

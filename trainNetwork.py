@@ -8,7 +8,9 @@ launched with ``python -m torch.distributed.run --nproc-per-node N trainNetwork.
 (every optimizer step then covers ``--episodes_per_step`` episodes, default one per rank;
 gradients are averaged with an RCCL all-reduce; the BatchNorm buffers of the ranks are reconciled before an
 evaluation or a save (``fpsg_amd.dist.BufferSync``); every rank evaluates a shard of the test items; rank 0 logs and
-saves).
+saves).  ``--ema_decay D`` keeps an exponential moving average of the weights (``fpsg_amd.ema``, K23): every evaluation
+is followed by one of the averaged weights on the same test items (``[EMA] `` lines), ``model_epoch_N_ema.pt`` is saved
+beside ``model_epoch_N.pt`` and the sidecar gains an ``"ema"`` entry.
 
     python trainNetwork.py --synthetic --n_shot 1 --n_query 1 --epoch 2 --n_episode 10 \
         --pc_encoder_path tests/golden/pretrained_pcencoder_pointnet.pt --model_path /tmp/ckpt
@@ -32,8 +34,9 @@ from fpsg_amd.episodes import EpisodePrefetcher
 from fpsg_amd.optim import check_max_grad_norm
 
 
-def evaluate(model, dl_test, n_query, n_shot, device, log, rank: int = 0, world: int = 1):
-    """Per-class Chamfer report (reference :157-189); returns the per-item values.
+def evaluate(model, dl_test, n_query, n_shot, device, log, rank: int = 0, world: int = 1, prefix: str = ""):
+    """Per-class Chamfer report (reference :157-189); returns the per-item values.  ``prefix`` goes in front of every
+    line (``[EMA] `` for the averaged weights).
 
     With ``world`` ranks every rank evaluates the test items ``rank, rank + world, ...`` (every rank walks the same
     loader, so the items and their order are the single-process ones) and the values are gathered: no rank sits in a
@@ -54,7 +57,7 @@ def evaluate(model, dl_test, n_query, n_shot, device, log, rank: int = 0, world:
     for name in sorted(per_class):
         vals = per_class[name]
         spread = statistics.stdev(vals) if len(vals) > 1 else 0.0
-        log(f"Class: {name} -- Rec CD: {statistics.mean(vals)} ({spread})")
+        log(f"{prefix}Class: {name} -- Rec CD: {statistics.mean(vals)} ({spread})")
     model.train()
     return every
 
@@ -109,12 +112,17 @@ def main(opt):
     fdist.broadcast_parameters(model)
 
     optimizer, scheduler = build_optimizer(model, opt)
+    ema = getattr(optimizer, "ema", None)       # --ema_decay: the average starts as a copy of the (loaded) weights
+    ema_how = ""
     if state_path is not None:
         err = None
         try:
             state = torch.load(state_path, map_location=device, weights_only=True)
             optimizer.load_state_dict(state["optimizer"])
             scheduler.load_state_dict(state["scheduler"])
+            if ema is not None and "ema" in state:      # (without --ema_decay an entry is ignored)
+                ema.load_state_dict(state["ema"])
+                ema_how = f"; EMA restored after {ema.updates} updates"
             # the sidecar holds the state AFTER epoch N's scheduler.step(): training continues with epoch
             # N+1 (the weights-only resume of the reference re-runs epoch N from fresh moments; doing that
             # here would step the LR schedule twice for epoch N and reuse post-epoch-N moments)
@@ -126,6 +134,8 @@ def main(opt):
     if opt.resume > 0 and is_main:
         how = (f"optimizer / scheduler state restored from {state_path}" if state_path is not None
                else "weights only, fresh optimizer state as in the reference")
+        if ema is not None:
+            how += ema_how or "; EMA started from the resumed weights"
         print(f"Resumed from model_epoch_{opt.resume}.pt ({how}): the next epoch is {start_epoch}")
     if start_epoch > opt.epoch:
         raise RuntimeError(f"nothing to do: the resumed run would start at epoch {start_epoch} but --epoch is "
@@ -192,10 +202,22 @@ def main(opt):
         if evaluating:
             if world > 1:
                 torch.manual_seed(2000003 * epoch)      # every rank walks the same test items (the shards partition them)
+            rng_state = torch.get_rng_state() if ema is not None else None
             every = evaluate(model, dl_test, n_query, opt.n_shot, device, log, rank, world)
             spread = statistics.stdev(every) if len(every) > 1 else 0.0
             log(f"Avg testing results across all classes Epoch -- {epoch} are: "
                 f"Query_rec: {sum(every) / max(len(every), 1)} ({spread})")
+            if ema is not None:
+                # the averaged weights on the same test items: the sampler draws them from the CPU generator, which
+                # goes back to where the evaluation above found it and ends where that one left it
+                after = torch.get_rng_state()
+                torch.set_rng_state(rng_state)
+                with ema.swapped():
+                    every = evaluate(model, dl_test, n_query, opt.n_shot, device, log, rank, world, prefix="[EMA] ")
+                torch.set_rng_state(after)
+                spread = statistics.stdev(every) if len(every) > 1 else 0.0
+                log(f"[EMA] Avg testing results across all classes Epoch -- {epoch} are: "
+                    f"Query_rec: {sum(every) / max(len(every), 1)} ({spread})")
             for sample in dl_test if is_main else ():
                 model.eval()
                 model.draw_reconstruction(to_device(sample, device),
@@ -205,8 +227,14 @@ def main(opt):
 
         if is_main and saving:
             torch.save(model.state_dict(), os.path.join(checkpoint_path, f"model_epoch_{epoch}.pt"))
-            torch.save({"optimizer": optimizer.state_dict(), "scheduler": scheduler.state_dict(),
-                        "epoch": epoch}, os.path.join(checkpoint_path, f"train_state_epoch_{epoch}.pt"))
+            train_state = {"optimizer": optimizer.state_dict(), "scheduler": scheduler.state_dict(), "epoch": epoch}
+            if ema is not None:
+                # the averaged weights as an ordinary weights file (--eval_model loads it): the state dict taken inside
+                # the swap, so the live BatchNorm buffers go with it
+                with ema.swapped():
+                    torch.save(model.state_dict(), os.path.join(checkpoint_path, f"model_epoch_{epoch}_ema.pt"))
+                train_state["ema"] = ema.state_dict()
+            torch.save(train_state, os.path.join(checkpoint_path, f"train_state_epoch_{epoch}.pt"))
             with open(checkpoint_logs, "a") as f:
                 f.writelines(f"{line}\n" for line in pending)
             pending.clear()
