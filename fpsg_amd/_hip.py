@@ -219,6 +219,11 @@ SIGNATURES = {
     "fpsg_repulsion_fwd": [_c_f32p, _c_int, _c_int, _c_int, ctypes.c_float, _c_i32p, _c_f32p, _c_f32p, ctypes.c_void_p,
                            ctypes.c_size_t, _c_stream],
     "fpsg_repulsion_bwd": [_c_f32p, _c_i32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, ctypes.c_float, _c_f32p, _c_stream],
+    "fpsg_expansion_workspace_bytes": [_c_int, _c_int, _c_int],
+    "fpsg_expansion_fwd": [_c_f32p, _c_int, _c_int, _c_int, ctypes.c_float, _c_i32p, _c_f32p, _c_i32p, _c_f32p, _c_f32p,
+                           ctypes.c_void_p, ctypes.c_size_t, _c_stream],
+    "fpsg_expansion_bwd": [_c_f32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, ctypes.c_float, _c_f32p,
+                           _c_stream],
     "fpsg_swd_workspace_bytes": [_c_int, _c_int, _c_int],
     "fpsg_swd": [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_i32p,
                  ctypes.c_void_p, ctypes.c_size_t, _c_stream],
@@ -231,6 +236,7 @@ _RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_grad_norm_workspace_bytes
              "fpsg_bn_workspace_floats": ctypes.c_size_t, "fpsg_bn_pool_workspace_floats": ctypes.c_size_t, "fpsg_bn_max_workspace_floats": ctypes.c_size_t, "fpsg_bn_max_dz_offset": ctypes.c_size_t, "fpsg_conv_first_dw_workspace_floats": ctypes.c_size_t, "fpsg_emd_workspace_floats": ctypes.c_size_t, "fpsg_emd_exact_workspace_floats": ctypes.c_size_t, "fpsg_emd_cross_workspace_bytes": ctypes.c_size_t, "fpsg_occupancy_grid_workspace_bytes": ctypes.c_size_t, "fpsg_fps_workspace_bytes": ctypes.c_size_t, "fpsg_max_bwd_scatter_workspace_floats": ctypes.c_size_t,
              "fpsg_wino_dw_fused_workspace_floats": ctypes.c_size_t, "fpsg_gemm_split_workspace_floats": ctypes.c_size_t, "fpsg_gemm_split_packed_a_bytes": ctypes.c_size_t, "fpsg_edgeconv_stats_ws_floats": ctypes.c_size_t,
              "fpsg_repulsion_workspace_bytes": ctypes.c_size_t,
+             "fpsg_expansion_workspace_bytes": ctypes.c_size_t,
              "fpsg_swd_workspace_bytes": ctypes.c_size_t}
 
 _lib = None

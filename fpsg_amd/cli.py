@@ -23,7 +23,9 @@ with ``--sinkhorn_blur`` / ``--sinkhorn_diameter`` (training on the Sinkhorn div
 ``--pc_dist swd`` with ``--swd_n_proj`` / ``--swd_directions`` (training on the sliced Wasserstein distance, K22),
 ``--repulsion_weight W`` with ``--repulsion_k`` / ``--repulsion_h`` (training: W times the repulsion term of the decoded
 clouds, K21, added to whichever ``--pc_dist`` is trained, and one extra line per epoch), ``--ema_decay D`` (training: an
-exponential moving average of the weights, K23, evaluated beside the raw weights and saved as ``model_epoch_N_ema.pt``).
+exponential moving average of the weights, K23, evaluated beside the raw weights and saved as ``model_epoch_N_ema.pt``),
+``--expansion_weight W`` with ``--expansion_lambda`` (training: W times the expansion penalty of the decoded clouds' patches,
+K24, added like the repulsion term, and one extra line per epoch).
 """
 from __future__ import annotations
 
@@ -36,8 +38,9 @@ from torch.utils.data import DataLoader
 
 from . import eval_report
 from .ema import check_ema_decay
-from .few_shot import check_repulsion_weight
-from .metrics import SINKHORN_TRAIN_DIAMETER, check_repulsion_options, check_sinkhorn_option, check_swd_options
+from .few_shot import check_expansion_weight, check_repulsion_weight
+from .metrics import (SINKHORN_TRAIN_DIAMETER, check_expansion_options, check_repulsion_options, check_sinkhorn_option,
+                      check_swd_options)
 from .episodes import EpisodicBatchSampler, SequentialBatchSampler, SyntheticFewShot
 
 
@@ -120,6 +123,14 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--repulsion_h", type=float, default=0.03, metavar="H",
                    help="With --repulsion_weight: the bandwidth of the term, a length -- clouds live in the unit ball "
                         "[default: 0.03];")
+    g.add_argument("--expansion_weight", type=float, default=0.0, metavar="W",
+                   help="Add W times the expansion penalty of the generated clouds (each decoder patch charged for the "
+                        "edges of its minimum spanning tree that are longer than L times the tree's mean edge) to the "
+                        "training loss, under any --pc_dist [default: 0 = off]; prints the mean penalty per cloud after "
+                        "every epoch;")
+    g.add_argument("--expansion_lambda", type=float, default=1.5, metavar="L",
+                   help="With --expansion_weight: an edge is charged where it is longer than L times its patch's mean "
+                        "edge, L >= 1 [default: 1.5];")
     g.add_argument("--ema_decay", type=float, default=0.0, metavar="D",
                    help="Keep an exponential moving average of the weights with decay D in (0, 1), warmed up as "
                         "min(D, (1 + t) / (10 + t)) [default: 0 = off]; every evaluation is followed by one on the "
@@ -169,6 +180,15 @@ def validate(opt) -> None:
             check_repulsion_options(opt.repulsion_k, opt.repulsion_h)
         except ValueError as e:
             raise SystemExit(f"--repulsion_{e}") from None
+    if getattr(opt, "expansion_weight", None) is not None:
+        try:
+            check_expansion_weight(opt.expansion_weight)
+        except ValueError as e:
+            raise SystemExit(f"--{e}") from None
+        try:
+            check_expansion_options(2, opt.expansion_lambda)
+        except ValueError as e:
+            raise SystemExit(f"--expansion_lambda: {e}") from None
     if getattr(opt, "ema_decay", None) is not None:
         try:
             check_ema_decay(opt.ema_decay)

@@ -33,7 +33,7 @@ def default_options(**overrides) -> argparse.Namespace:
         raw_dim=3, num_nodes=4, device="cuda", bottleneck_size=1536, template_type="SQUARE",
         activation="relu", aggregate="single", pc_dist="cd", lr=1e-3, lr_decay=350, SGD=False,
         n_way=1, n_shot=20, n_query=0, clip_grad_norm=0.0, repulsion_weight=0.0, repulsion_k=4, repulsion_h=0.03,
-        swd_n_proj=64, swd_directions="random", ema_decay=0.0)
+        swd_n_proj=64, swd_directions="random", ema_decay=0.0, expansion_weight=0.0, expansion_lambda=1.5)
     for k, v in overrides.items():
         setattr(opt, k, v)
     return opt
@@ -57,7 +57,9 @@ def build_model(opt) -> ImgPCProtoNet:
                          repulsion_weight=getattr(opt, "repulsion_weight", 0.0),
                          repulsion_k=getattr(opt, "repulsion_k", 4), repulsion_h=getattr(opt, "repulsion_h", 0.03),
                          swd_n_proj=getattr(opt, "swd_n_proj", 64),
-                         swd_directions=getattr(opt, "swd_directions", "random"))
+                         swd_directions=getattr(opt, "swd_directions", "random"),
+                         expansion_weight=getattr(opt, "expansion_weight", 0.0),
+                         expansion_lambda=getattr(opt, "expansion_lambda", 1.5))
 
 
 def build_optimizer(model, opt):

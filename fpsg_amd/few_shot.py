@@ -20,9 +20,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .metrics import (SINKHORN_TRAIN_DIAMETER, chamfer_distance, check_dcd_alpha, check_repulsion_options,
-                      check_sinkhorn_option, check_swd_options, dcd, emd_loss, episode_chamfer_losses, repulsion_loss,
-                      sinkhorn_loss, swd_directions, swd_loss)
+from .metrics import (SINKHORN_TRAIN_DIAMETER, chamfer_distance, check_dcd_alpha, check_expansion_options,
+                      check_repulsion_options, check_sinkhorn_option, check_swd_options, dcd, emd_loss,
+                      episode_chamfer_losses, expansion_penalty, repulsion_loss, sinkhorn_loss, swd_directions, swd_loss)
 from .utils import emd_wrapper
 
 _AGGREGATOR = ["single", "multi", "mask_single", "mask_multi"]
@@ -33,15 +33,24 @@ def _fused_losses_enabled() -> bool:
     return os.environ.get("FPSG_FUSED_LOSSES", "1") != "0"
 
 
-def check_repulsion_weight(weight) -> float:
-    """``repulsion_weight`` as a Python float: a finite, non-negative number (``ValueError`` otherwise)."""
+def _check_weight(weight, name) -> float:
     try:
         w = float(weight)
     except (TypeError, ValueError):
-        raise ValueError(f"repulsion_weight must be a number, got {weight!r}") from None
+        raise ValueError(f"{name} must be a number, got {weight!r}") from None
     if isinstance(weight, bool) or not (math.isfinite(w) and w >= 0.0):
-        raise ValueError(f"repulsion_weight must be finite and non-negative, got {weight!r}")
+        raise ValueError(f"{name} must be finite and non-negative, got {weight!r}")
     return w
+
+
+def check_repulsion_weight(weight) -> float:
+    """``repulsion_weight`` as a Python float: a finite, non-negative number (``ValueError`` otherwise)."""
+    return _check_weight(weight, "repulsion_weight")
+
+
+def check_expansion_weight(weight) -> float:
+    """``expansion_weight`` as a Python float: a finite, non-negative number (``ValueError`` otherwise)."""
+    return _check_weight(weight, "expansion_weight")
 
 
 class _SplitRows(torch.autograd.Function):
@@ -76,7 +85,7 @@ class ImgPCProtoNet(nn.Module):
     def __init__(self, img_encoder, pc_encoder, pc_decoder, mask_learner=None, query_factor=1.0,
                  support_factor=1.0, metric="cd", intra_support=False, aggregate="single", dcd_alpha=1000.0,
                  sinkhorn_blur=0.05, sinkhorn_diameter=SINKHORN_TRAIN_DIAMETER, repulsion_weight=0.0, repulsion_k=4,
-                 repulsion_h=0.03, swd_n_proj=64, swd_directions="random"):
+                 repulsion_h=0.03, swd_n_proj=64, swd_directions="random", expansion_weight=0.0, expansion_lambda=1.5):
         super().__init__()
         self.img_encoder = img_encoder
         self.pc_encoder = pc_encoder
@@ -121,6 +130,15 @@ class ImgPCProtoNet(nn.Module):
         # the loss is what it is without these arguments, launch for launch
         self.repulsion_weight = check_repulsion_weight(repulsion_weight)
         self.repulsion_k, self.repulsion_h = check_repulsion_options(repulsion_k, repulsion_h)
+        # the expansion penalty (K24) on the decoded clouds' patches, added like the repulsion term; 0: off.  The patch
+        # size is the decoder's: its cloud is (cluster, node) patches of that many consecutive rows
+        self.expansion_weight = check_expansion_weight(expansion_weight)
+        _, self.expansion_lambda = check_expansion_options(2, expansion_lambda)
+        self.expansion_patch = getattr(pc_decoder, "pts_per_patch", None)
+        if self.expansion_weight > 0:
+            if self.expansion_patch is None:
+                raise ValueError("expansion_weight needs a decoder that exposes its points per patch (pts_per_patch)")
+            self.expansion_patch, _ = check_expansion_options(self.expansion_patch, self.expansion_lambda)
         self.overlap_encoders = False      # see _encode; switched on by bench.py / the trainer
         self._side_stream = None
 
@@ -226,10 +244,30 @@ class ImgPCProtoNet(nn.Module):
         out["repulsion_loss"] = total
         return out
 
+    def _with_expansion(self, out, syn, n_q):
+        """Adds the expansion penalty of the episode's decoded clouds to the loss dict (behind the repulsion term where
+        both are on): ONE K24 call; ``ttl_loss`` gains ``expansion_weight * (query_factor * sum_q E + support_factor *
+        sum_s E)``, ``expansion_loss`` is the unweighted sum, every other entry stays as it is."""
+        pen = expansion_penalty(syn.contiguous(), self.expansion_patch, self.expansion_lambda)
+        pen_q = pen[:n_q].sum()
+        weighted = self.query_factor * pen_q
+        total = pen_q
+        if n_q < pen.size(0):
+            pen_s = pen[n_q:].sum()
+            weighted = weighted + self.support_factor * pen_s
+            total = total + pen_s
+        out = dict(out)
+        out["ttl_loss"] = out["ttl_loss"] + self.expansion_weight * weighted
+        out["expansion_loss"] = total
+        return out
+
     def _loss_single_class(self, img_s, img_q, img_ad, pc_s, pc_q, pc_ad):
-        out, syn, n_q = self._recon_losses(img_s, img_q, img_ad, pc_s, pc_q, pc_ad, self.repulsion_weight > 0)
+        want = self.repulsion_weight > 0 or self.expansion_weight > 0
+        out, syn, n_q = self._recon_losses(img_s, img_q, img_ad, pc_s, pc_q, pc_ad, want)
         if self.repulsion_weight > 0:
-            return self._with_repulsion(out, syn, n_q)
+            out = self._with_repulsion(out, syn, n_q)
+        if self.expansion_weight > 0:
+            out = self._with_expansion(out, syn, n_q)
         return out
 
     def _recon_losses(self, img_s, img_q, img_ad, pc_s, pc_q, pc_ad, want_clouds=False):

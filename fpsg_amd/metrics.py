@@ -841,6 +841,104 @@ def repulsion_loss(p: torch.Tensor, k: int = 4, h: float = 0.03, return_info: bo
     return (out, info) if return_info else out
 
 
+EXPANSION_MAX_P = 1024          # FPSG_EXPANSION_MAX_P (include/fpsg_hip.h)
+EXPANSION_MAX_N = 16384         # FPSG_EXPANSION_MAX_N
+
+
+def check_expansion_options(patch_size, lam):
+    """``(patch_size, lam)`` of ``expansion_penalty`` as a Python int and float: ``patch_size`` an integer in 2..1024,
+    ``lam`` a finite number of at least 1 (``ValueError`` naming the argument otherwise)."""
+    if isinstance(patch_size, bool) or not isinstance(patch_size, numbers.Integral):
+        raise ValueError(f"patch_size must be an integer in 2..{EXPANSION_MAX_P}, got {patch_size!r}")
+    if not 2 <= int(patch_size) <= EXPANSION_MAX_P:
+        raise ValueError(f"patch_size must be in 2..{EXPANSION_MAX_P}, got {patch_size!r}")
+    try:
+        lf = float(lam)
+    except (TypeError, ValueError):
+        raise ValueError(f"lam must be a number, got {lam!r}") from None
+    if isinstance(lam, bool) or not (math.isfinite(lf) and lf >= 1.0):
+        raise ValueError(f"lam must be finite and at least 1, got {lam!r}")
+    return int(patch_size), lf
+
+
+class _Expansion(torch.autograd.Function):
+    """K24's forward (the patches' spanning trees, mean edges and the value per cloud) and its gather backward on the
+    saved trees."""
+
+    @staticmethod
+    def forward(ctx, p, P, lam, info_out):
+        ctx.set_materialize_grads(False)
+        B, N, _ = p.shape
+        K = N // P
+        lib = _hip.load()
+        parent = torch.empty((B, N), dtype=torch.int32, device=p.device)
+        d2 = torch.empty((B, N), dtype=torch.float32, device=p.device)
+        order = torch.empty((B, N), dtype=torch.int32, device=p.device)
+        mean_len = torch.empty((B, K), dtype=torch.float32, device=p.device)
+        value = torch.empty((B,), dtype=torch.float32, device=p.device)
+        ws_bytes = lib.fpsg_expansion_workspace_bytes(B, N, P)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=p.device)
+        with torch.cuda.device(p.device), _probe("expansion_fwd", B, N, P):
+            rc = lib.fpsg_expansion_fwd(_hip.ptr(p), B, N, P, lam, _hip.ptr(parent), _hip.ptr(d2), _hip.ptr(order),
+                                        _hip.ptr(mean_len), _hip.ptr(value), _hip.ptr(ws), ws_bytes, _hip.stream_of(p))
+        _hip.check(rc, "fpsg_expansion_fwd")
+        if info_out is not None:
+            info_out.update(parent=parent, d2=d2, order=order, mean_len=mean_len)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(p, parent, d2, mean_len)
+            ctx.cfg = (P, lam)
+        return value
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        p, parent, d2, mean_len = ctx.saved_tensors
+        P, lam = ctx.cfg
+        B, N, _ = p.shape
+        g = g.reshape(B).contiguous().float()
+        gx = torch.empty_like(p)
+        with torch.cuda.device(p.device), _probe("expansion_bwd", B, N, P):
+            rc = _hip.load().fpsg_expansion_bwd(_hip.ptr(p), _hip.ptr(parent), _hip.ptr(d2), _hip.ptr(mean_len),
+                                                _hip.ptr(g), B, N, P, lam, _hip.ptr(gx), _hip.stream_of(p))
+        _hip.check(rc, "fpsg_expansion_bwd")
+        return gx, None, None, None
+
+
+def expansion_penalty(p: torch.Tensor, patch_size: int, lam: float = 1.5, return_info: bool = False):
+    """MSN's expansion penalty ``[B]`` fp32 of the multi-patch clouds ``p [B,N,3]`` (K24, HIP; the definition is in
+    ``include/fpsg_hip.h``): the cloud is ``K = N / patch_size`` patches of ``patch_size`` consecutive rows (the decoder's
+    layout); every patch gets its minimum spanning tree (Prim's from its first point, ties to the lower index) and is
+    charged ``(1 / (P - 1)) sum r_v`` over the tree edges with ``r_v > lam * (the tree's mean edge)``; the value is the mean
+    over the patches, in ``[0, inf)``.  It is 0 where every sheet is evenly spread and grows with edges that stretch a
+    patch across the shape.  It needs no ground truth and is added to whichever distance is trained.
+
+    Differentiable in ``p`` with the trees, the penalised sets and the mean edges held constant.  Bitwise the same on
+    every run and independent of the batch, forward and backward (no atomics).  The call only enqueues: it can be captured.
+
+    ``return_info=True``: returns ``(value, info)`` with ``info["parent"]`` int32 (local index, -1 at each patch's first
+    point), ``info["d2"]`` fp32 (the squared edge length), ``info["order"]`` int32 (the step at which Prim's added the point),
+    all ``[B,N]``, and ``info["mean_len"] [B,K]`` fp32.
+
+    ``ValueError`` (before anything else) for a bad ``patch_size`` or ``lam``, a shape that is not ``[B,N,3]``, ``B = 0``, ``N``
+    not a positive multiple of ``patch_size`` and more than 16384 points.  No CPU path: a CPU tensor raises
+    ``FpsgHipError``."""
+    P, lam = check_expansion_options(patch_size, lam)
+    if not isinstance(p, torch.Tensor) or p.dim() != 3 or p.size(2) != 3:
+        raise ValueError(f"expected a [B,N,3] cloud tensor, got {tuple(getattr(p, 'shape', ()))}")
+    if p.size(0) == 0:
+        raise ValueError(f"empty batches are not supported (got {tuple(p.shape)})")
+    if p.size(1) < P or p.size(1) % P != 0:
+        raise ValueError(f"expansion_penalty needs a positive multiple of patch_size = {P} points per cloud, "
+                         f"got {p.size(1)}")
+    if p.size(1) > EXPANSION_MAX_N:
+        raise ValueError(f"expansion_penalty supports at most {EXPANSION_MAX_N} points per cloud, got {p.size(1)}")
+    _hip.dev_tensor(p, torch.float32, "p")
+    info = {} if return_info else None
+    out = _Expansion.apply(p, P, lam, info)
+    return (out, info) if return_info else out
+
+
 SWD_MAX_N = 2048                # FPSG_SWD_MAX_N (include/fpsg_hip.h)
 SWD_MAX_L = 1024                # FPSG_SWD_MAX_L
 SWD_DIRECTION_MODES = ("random", "fixed")

@@ -722,6 +722,12 @@ class PCDecoder(nn.Module):
         ])
         self._tag_stack_groups()
 
+    @property
+    def pts_per_patch(self) -> int:
+        """Points per patch: the cloud is ``num_clusters * num_nodes`` patches of this many consecutive rows, patch
+        ``(cluster c, node n)`` at rows ``(c * num_nodes + n) * pts_per_patch ..`` (what K24's trees are built on)."""
+        return self.num_pts_per_cluster // self.num_nodes
+
     def _tag_stack_groups(self):
         """Marks the parameters ``pack_parameters`` stacks -- the same tensor of every deformer, of every node -- as
         stack groups (``fpsg_amd.optim.layout_order``): the flat optimizer then stores each group as one contiguous

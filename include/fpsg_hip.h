@@ -469,6 +469,57 @@ size_t fpsg_swd_workspace_bytes(int B, int N, int L);
 int fpsg_swd(const float* xyz1, const float* xyz2, const float* dirs, int B, int N, int L, float* value, float* gxyz1,
              float* gxyz2, int32_t* perm1, int32_t* perm2, void* ws, size_t ws_bytes, fpsg_stream_t stream);
 
+/* ---- K24: expansion penalty of a multi-patch cloud (per-patch minimum spanning trees) -----------------
+ * MSN's expansion penalty (Liu et al., AAAI 2020): the cloud is K patches of P consecutive points; each patch is
+ * charged for the edges of its minimum spanning tree that are much longer than the tree's mean edge.  The published
+ * code is not pinned; the definition below is the specification (parity UNPINNED).  Inputs: B clouds
+ * xyz [N,3] fp32, 2 <= P <= FPSG_EXPANSION_MAX_P, N % P == 0, K = N / P, patch q = rows q P .. q P + P - 1, lambda >= 1.
+ *   d2(u,v)  = K1's sq_dist: fma(dz,dz, fma(dy,dy, dx*dx)), dx = x_v - x_u (bitwise symmetric, never negative)
+ *   T_q      = Prim's tree from local vertex 0 under d2: every non-tree vertex keeps a key (the smallest d2 to a tree
+ *              vertex) and a parent; a later-added tree vertex replaces them only where its d2 is STRICTLY smaller (on
+ *              ties the earlier-added vertex stays the parent); each step adds the non-tree vertex with the smallest
+ *              (key, local index) in lexicographic order
+ *   parent [B,N] int32: local index, -1 at each patch's vertex 0;  edge_d2 [B,N] fp32: the final key, 0 at vertex 0;
+ *   order [B,N] int32: the step at which the vertex was added, 0 at vertex 0
+ *   r_v      = sqrt(edge_d2[v])                                   (correctly rounded)
+ *   l_q      = (sum_v r_v) / (P - 1)                              -> mean_len [B,K]
+ *   v is penalised iff r_v > lambda * l_q (strictly; one fp32 product): with every point identical, with P = 2 or
+ *              with all edges equal nothing is penalised
+ *   E_q      = (sum_{v penalised} r_v) / (P - 1)
+ *   value[b] = (sum_q E_q) / K                                    in [0, inf)
+ *   gxyz[u]  = gvalue[b] (1 / (K (P - 1))) [ [u penalised] (x_u - x_par(u)) / r_u
+ *                                            + sum_{v : par(v) = u, v penalised} (x_u - x_v) / r_v ]
+ * (the tree, the penalised set and l_q are held constant: no gradient flows through them).  A penalised edge has r > 0,
+ * so no floor is needed and duplicates give no NaN.  fp32 throughout; the divisions are fp32 divisions.
+ * Orders: vertex v = t + 64 s belongs to lane t, slot s.  A sum over a patch's vertices adds each lane's slots in
+ * ascending s from +0, then the 64 lanes by the balanced tree over the lane; the division by P - 1 follows.  A cloud's
+ * K values E_q are added in ascending q from +0, the division by K last.  A gradient row starts from +0, takes its own
+ * edge's term, then the child terms in ascending v, each term formed as a difference and a division per axis and
+ * added; the product with gvalue[b] * (1 / (K (P - 1))) (formed in double, rounded to fp32) last.  gxyz is written,
+ * not accumulated.
+ * The backward recomputes sqrt(edge_d2[v]) > lambda * mean_len[b,q] -- the forward's expression on the forward's bits --
+ * and skips every v whose parent is outside [0, P) or whose length is not positive: it is safe on any int32 / fp32
+ * arrays.  With coordinates that are not finite the patch's results are unspecified, but the loop still ends after
+ * P - 1 steps and every stored index is inside [0, P) (or the root's -1); no access goes out of bounds.
+ * Bitwise the same on every run, whatever B is and wherever the cloud sits in the batch or the patch in the cloud; no
+ * atomics.  One wavefront owns one patch.  The forward is two launches (the trees; one thread per cloud adds the
+ * partials), the backward one; the workspace holds the forward's B K partials.  The calls only enqueue work on
+ * `stream` (no host read; they can be captured in a graph).
+ * Errors, all before any launch, shape and limit checks in front of the pointer checks: FPSG_E_SHAPE for B < 1, P < 2,
+ * N not a positive multiple of P, lambda not finite or < 1, or a workspace smaller than
+ * fpsg_expansion_workspace_bytes; FPSG_E_LIMIT for P > FPSG_EXPANSION_MAX_P or N > FPSG_EXPANSION_MAX_N; FPSG_E_NULL
+ * for a null pointer; FPSG_E_ALIGN for a misaligned one.  fpsg_expansion_workspace_bytes returns 0 for a shape the
+ * entries refuse.
+ */
+#define FPSG_EXPANSION_MAX_P 1024
+#define FPSG_EXPANSION_MAX_N 16384
+size_t fpsg_expansion_workspace_bytes(int B, int N, int P);
+int fpsg_expansion_fwd(const float* xyz, int B, int N, int P, float lambda, int32_t* parent, float* edge_d2,
+                       int32_t* order, float* mean_len, float* value, void* workspace, size_t workspace_bytes,
+                       fpsg_stream_t stream);
+int fpsg_expansion_bwd(const float* xyz, const int32_t* parent, const float* edge_d2, const float* mean_len,
+                       const float* gvalue, int B, int N, int P, float lambda, float* gxyz, fpsg_stream_t stream);
+
 /* ---- K4b: fused EdgeConv (gather + BatchNorm statistics + max over k) -----------------
  * Replaces the chain get_graph_feature -> Conv2d 1x1 -> BatchNorm2d -> LeakyReLU -> max_k of
  * src/dgcnn/model.py:23-42,53-56,63-76 without materialising [B,2C,N,k].  The caller first

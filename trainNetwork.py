@@ -144,7 +144,7 @@ def main(opt):
     buffers = fdist.BufferSync(model)
     eps_per_step = opt.episodes_per_step or world
     local_n = len(range(rank, eps_per_step, world))
-    n_clouds = n_query + (opt.n_shot if opt.intra_recon else 0)     # decoded clouds per episode (the repulsion term's)
+    n_clouds = n_query + (opt.n_shot if opt.intra_recon else 0)     # decoded clouds per episode (the regularisers')
 
     pending: list[str] = []
 
@@ -156,7 +156,7 @@ def main(opt):
     for epoch in range(start_epoch, opt.epoch + 1):
         # every rank draws its own episodes; different seeds per (epoch, rank)
         torch.manual_seed(1000003 * epoch + rank)
-        sums = torch.zeros(3, dtype=torch.float64, device=device)
+        sums = torch.zeros(4, dtype=torch.float64, device=device)
         n_steps = max(1, opt.n_episode // eps_per_step)
         # exactly the episodes this rank uses (the worker must not draw one more from the global RNG: the
         # evaluation below and the next epoch's seed share it), drawn and uploaded behind the step
@@ -178,9 +178,11 @@ def main(opt):
                     sums[1] += out["support_rec_loss"].sum() / opt.n_shot
                     if "repulsion_loss" in out:     # only with --repulsion_weight: the unweighted sum over the clouds
                         sums[2] += out["repulsion_loss"].sum() / n_clouds
+                    if "expansion_loss" in out:     # only with --expansion_weight, likewise
+                        sums[3] += out["expansion_loss"].sum() / n_clouds
         finally:
             it.close()
-        q_sum, s_sum, r_sum = fdist.all_reduce_scalars(sums.tolist(), device)   # one host sync per epoch
+        q_sum, s_sum, r_sum, e_sum = fdist.all_reduce_scalars(sums.tolist(), device)   # one host sync per epoch
         done = n_steps * eps_per_step
         dt = time.perf_counter() - t0
         log(f"Training Results for Epoch -- {epoch} are: Query_rec: {q_sum / done}, "
@@ -193,6 +195,8 @@ def main(opt):
                   f"{cs['nonfinite']} non-finite]")
         if is_main and opt.repulsion_weight > 0:
             print(f"  [repulsion: mean {r_sum / done:.6g} per cloud]")
+        if is_main and opt.expansion_weight > 0:
+            print(f"  [expansion: mean {e_sum / done:.6g} per cloud]")
         scheduler.step()
 
         evaluating = epoch % opt.eval_interval == 0 or epoch == opt.epoch
