@@ -224,6 +224,12 @@ SIGNATURES = {
                            ctypes.c_void_p, ctypes.c_size_t, _c_stream],
     "fpsg_expansion_bwd": [_c_f32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, ctypes.c_float, _c_f32p,
                            _c_stream],
+    "fpsg_uniform_workspace_bytes": [_c_int, _c_int, _c_int, _c_int, _c_int],
+    "fpsg_uniform_fwd": [_c_f32p, _c_i32p, _c_int, _c_int, _c_int, ctypes.POINTER(ctypes.c_float), _c_int, ctypes.c_float,
+                         _c_int, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p,
+                         ctypes.c_size_t, _c_stream],
+    "fpsg_uniform_bwd": [_c_f32p, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int,
+                         ctypes.POINTER(ctypes.c_float), ctypes.c_float, _c_int, _c_f32p, _c_stream],
     "fpsg_swd_workspace_bytes": [_c_int, _c_int, _c_int],
     "fpsg_swd": [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_i32p,
                  ctypes.c_void_p, ctypes.c_size_t, _c_stream],
@@ -237,6 +243,7 @@ _RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_grad_norm_workspace_bytes
              "fpsg_wino_dw_fused_workspace_floats": ctypes.c_size_t, "fpsg_gemm_split_workspace_floats": ctypes.c_size_t, "fpsg_gemm_split_packed_a_bytes": ctypes.c_size_t, "fpsg_edgeconv_stats_ws_floats": ctypes.c_size_t,
              "fpsg_repulsion_workspace_bytes": ctypes.c_size_t,
              "fpsg_expansion_workspace_bytes": ctypes.c_size_t,
+             "fpsg_uniform_workspace_bytes": ctypes.c_size_t,
              "fpsg_swd_workspace_bytes": ctypes.c_size_t}
 
 _lib = None

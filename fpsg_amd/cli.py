@@ -25,7 +25,10 @@ with ``--sinkhorn_blur`` / ``--sinkhorn_diameter`` (training on the Sinkhorn div
 clouds, K21, added to whichever ``--pc_dist`` is trained, and one extra line per epoch), ``--ema_decay D`` (training: an
 exponential moving average of the weights, K23, evaluated beside the raw weights and saved as ``model_epoch_N_ema.pt``),
 ``--expansion_weight W`` with ``--expansion_lambda`` (training: W times the expansion penalty of the decoded clouds' patches,
-K24, added like the repulsion term, and one extra line per epoch).
+K24, added like the repulsion term, and one extra line per epoch), ``--uniform_weight W`` with ``--uniform_percent`` /
+``--uniform_radius`` (training: W times PU-GAN's uniform loss of the decoded clouds, K25 -- balls of the given sizes, in
+percent of the cloud, around farthest-point seeds, each charged for its count's imbalance and its members' clutter --
+added like the two terms above, and one extra line per epoch).
 """
 from __future__ import annotations
 
@@ -38,9 +41,9 @@ from torch.utils.data import DataLoader
 
 from . import eval_report
 from .ema import check_ema_decay
-from .few_shot import check_expansion_weight, check_repulsion_weight
-from .metrics import (SINKHORN_TRAIN_DIAMETER, check_expansion_options, check_repulsion_options, check_sinkhorn_option,
-                      check_swd_options)
+from .few_shot import check_expansion_weight, check_repulsion_weight, check_uniform_weight
+from .metrics import (SINKHORN_TRAIN_DIAMETER, UNIFORM_MAX_T, check_expansion_options,
+                      check_repulsion_options, check_sinkhorn_option, check_swd_options, check_uniform_options)
 from .episodes import EpisodicBatchSampler, SequentialBatchSampler, SyntheticFewShot
 
 
@@ -131,6 +134,17 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--expansion_lambda", type=float, default=1.5, metavar="L",
                    help="With --expansion_weight: an edge is charged where it is longer than L times its patch's mean "
                         "edge, L >= 1 [default: 1.5];")
+    g.add_argument("--uniform_weight", type=float, default=0.0, metavar="W",
+                   help="Add W times the uniform loss of the generated clouds (balls of several sizes around farthest-point "
+                        "seeds, each charged for how far its point count is from its share and how far its members' "
+                        "nearest-neighbour distances are from an even spacing) to the training loss, under any --pc_dist "
+                        "[default: 0 = off]; prints the mean loss per cloud after every epoch;")
+    g.add_argument("--uniform_percent", type=float, nargs="+", default=[0.4, 0.6, 0.8, 1.0, 1.2], metavar="P",
+                   help="With --uniform_weight: the balls' sizes in percent of the cloud, each in (0, 100], at most 8 "
+                        "[default: 0.4 0.6 0.8 1.0 1.2];")
+    g.add_argument("--uniform_radius", type=float, default=1.0, metavar="R",
+                   help="With --uniform_weight: the radius of the disc whose area the surface is taken to have, a length "
+                        "-- clouds live in the unit ball [default: 1.0];")
     g.add_argument("--ema_decay", type=float, default=0.0, metavar="D",
                    help="Keep an exponential moving average of the weights with decay D in (0, 1), warmed up as "
                         "min(D, (1 + t) / (10 + t)) [default: 0 = off]; every evaluation is followed by one on the "
@@ -152,6 +166,21 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
         g.add_argument("--npy_folder", type=str, default="", help="Where draw_reconstruction dumps go;")
         eval_report.add_arguments(g)
     return p
+
+
+def uniform_fractions(percent) -> tuple:
+    """``--uniform_percent`` (percent of the cloud) as the fractions ``metrics.uniform_loss`` takes: 1..8 finite values in
+    (0, 100] (``ValueError`` otherwise)."""
+    try:
+        values = [float(p) for p in percent]
+    except (TypeError, ValueError):
+        raise ValueError(f"1..{UNIFORM_MAX_T} numbers in (0, 100], got {percent!r}") from None
+    if not 1 <= len(values) <= UNIFORM_MAX_T:
+        raise ValueError(f"1..{UNIFORM_MAX_T} values, got {len(values)}")
+    for v in values:
+        if not (v == v and 0.0 < v <= 100.0):
+            raise ValueError(f"each value must be in (0, 100], got {v!r}")
+    return tuple(v / 100.0 for v in values)
 
 
 def validate(opt) -> None:
@@ -189,6 +218,19 @@ def validate(opt) -> None:
             check_expansion_options(2, opt.expansion_lambda)
         except ValueError as e:
             raise SystemExit(f"--expansion_lambda: {e}") from None
+    if getattr(opt, "uniform_weight", None) is not None:
+        try:
+            check_uniform_weight(opt.uniform_weight)
+        except ValueError as e:
+            raise SystemExit(f"--{e}") from None
+        try:
+            opt.uniform_percentages = uniform_fractions(opt.uniform_percent)
+        except ValueError as e:
+            raise SystemExit(f"--uniform_percent: {e}") from None
+        try:
+            check_uniform_options(opt.uniform_percentages, opt.uniform_radius)
+        except ValueError as e:
+            raise SystemExit(f"--uniform_{e}") from None
     if getattr(opt, "ema_decay", None) is not None:
         try:
             check_ema_decay(opt.ema_decay)

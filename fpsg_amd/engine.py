@@ -18,7 +18,7 @@ from . import dist as fdist
 from . import bn_counters, eval_report, winograd
 from .few_shot import ImgPCProtoNet
 from .image_net import ImageEncoderWarpper
-from .metrics import SINKHORN_TRAIN_DIAMETER, check_dcd_alpha, check_thresholds, nearest_rows
+from .metrics import SINKHORN_TRAIN_DIAMETER, UNIFORM_PERCENTAGES, check_dcd_alpha, check_thresholds, nearest_rows
 from .ema import WeightEma, check_ema_decay
 from .optim import FlatAdam, check_max_grad_norm
 from .point_cloud_net import PCDecoder, PCEncoder
@@ -33,7 +33,8 @@ def default_options(**overrides) -> argparse.Namespace:
         raw_dim=3, num_nodes=4, device="cuda", bottleneck_size=1536, template_type="SQUARE",
         activation="relu", aggregate="single", pc_dist="cd", lr=1e-3, lr_decay=350, SGD=False,
         n_way=1, n_shot=20, n_query=0, clip_grad_norm=0.0, repulsion_weight=0.0, repulsion_k=4, repulsion_h=0.03,
-        swd_n_proj=64, swd_directions="random", ema_decay=0.0, expansion_weight=0.0, expansion_lambda=1.5)
+        swd_n_proj=64, swd_directions="random", ema_decay=0.0, expansion_weight=0.0, expansion_lambda=1.5,
+        uniform_weight=0.0, uniform_percentages=UNIFORM_PERCENTAGES, uniform_radius=1.0)
     for k, v in overrides.items():
         setattr(opt, k, v)
     return opt
@@ -59,7 +60,10 @@ def build_model(opt) -> ImgPCProtoNet:
                          swd_n_proj=getattr(opt, "swd_n_proj", 64),
                          swd_directions=getattr(opt, "swd_directions", "random"),
                          expansion_weight=getattr(opt, "expansion_weight", 0.0),
-                         expansion_lambda=getattr(opt, "expansion_lambda", 1.5))
+                         expansion_lambda=getattr(opt, "expansion_lambda", 1.5),
+                         uniform_weight=getattr(opt, "uniform_weight", 0.0),
+                         uniform_percentages=getattr(opt, "uniform_percentages", UNIFORM_PERCENTAGES),
+                         uniform_radius=getattr(opt, "uniform_radius", 1.0))
 
 
 def build_optimizer(model, opt):

@@ -20,9 +20,10 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .metrics import (SINKHORN_TRAIN_DIAMETER, chamfer_distance, check_dcd_alpha, check_expansion_options,
+from .metrics import (SINKHORN_TRAIN_DIAMETER, UNIFORM_PERCENTAGES, chamfer_distance, check_dcd_alpha, check_expansion_options,
                       check_repulsion_options, check_sinkhorn_option, check_swd_options, dcd, emd_loss,
-                      episode_chamfer_losses, expansion_penalty, repulsion_loss, sinkhorn_loss, swd_directions, swd_loss)
+                      check_uniform_options, episode_chamfer_losses, expansion_penalty, repulsion_loss, sinkhorn_loss,
+                      swd_directions, swd_loss, uniform_loss)
 from .utils import emd_wrapper
 
 _AGGREGATOR = ["single", "multi", "mask_single", "mask_multi"]
@@ -51,6 +52,11 @@ def check_repulsion_weight(weight) -> float:
 def check_expansion_weight(weight) -> float:
     """``expansion_weight`` as a Python float: a finite, non-negative number (``ValueError`` otherwise)."""
     return _check_weight(weight, "expansion_weight")
+
+
+def check_uniform_weight(weight) -> float:
+    """``uniform_weight`` as a Python float: a finite, non-negative number (``ValueError`` otherwise)."""
+    return _check_weight(weight, "uniform_weight")
 
 
 class _SplitRows(torch.autograd.Function):
@@ -85,7 +91,8 @@ class ImgPCProtoNet(nn.Module):
     def __init__(self, img_encoder, pc_encoder, pc_decoder, mask_learner=None, query_factor=1.0,
                  support_factor=1.0, metric="cd", intra_support=False, aggregate="single", dcd_alpha=1000.0,
                  sinkhorn_blur=0.05, sinkhorn_diameter=SINKHORN_TRAIN_DIAMETER, repulsion_weight=0.0, repulsion_k=4,
-                 repulsion_h=0.03, swd_n_proj=64, swd_directions="random", expansion_weight=0.0, expansion_lambda=1.5):
+                 repulsion_h=0.03, swd_n_proj=64, swd_directions="random", expansion_weight=0.0, expansion_lambda=1.5,
+                 uniform_weight=0.0, uniform_percentages=UNIFORM_PERCENTAGES, uniform_radius=1.0):
         super().__init__()
         self.img_encoder = img_encoder
         self.pc_encoder = pc_encoder
@@ -139,6 +146,10 @@ class ImgPCProtoNet(nn.Module):
             if self.expansion_patch is None:
                 raise ValueError("expansion_weight needs a decoder that exposes its points per patch (pts_per_patch)")
             self.expansion_patch, _ = check_expansion_options(self.expansion_patch, self.expansion_lambda)
+        # the uniform loss (K25) on the decoded clouds, added like the two terms above; 0: off.  The seeds are K16's farthest
+        # point sample of each decoded cloud (5 % of its points)
+        self.uniform_weight = check_uniform_weight(uniform_weight)
+        self.uniform_percentages, self.uniform_radius = check_uniform_options(uniform_percentages, uniform_radius)
         self.overlap_encoders = False      # see _encode; switched on by bench.py / the trainer
         self._side_stream = None
 
@@ -261,13 +272,33 @@ class ImgPCProtoNet(nn.Module):
         out["expansion_loss"] = total
         return out
 
+    def _with_uniform(self, out, syn, n_q):
+        """Adds the uniform loss of the episode's decoded clouds to the loss dict (behind the repulsion and expansion
+        terms where they are on): ONE K16 call for the seeds and ONE K25 call; ``ttl_loss`` gains ``uniform_weight *
+        (query_factor * sum_q U + support_factor * sum_s U)``, ``uniform_loss`` is the unweighted sum, every other entry
+        stays as it is."""
+        uni = uniform_loss(syn.contiguous(), self.uniform_percentages, self.uniform_radius)
+        uni_q = uni[:n_q].sum()
+        weighted = self.query_factor * uni_q
+        total = uni_q
+        if n_q < uni.size(0):
+            uni_s = uni[n_q:].sum()
+            weighted = weighted + self.support_factor * uni_s
+            total = total + uni_s
+        out = dict(out)
+        out["ttl_loss"] = out["ttl_loss"] + self.uniform_weight * weighted
+        out["uniform_loss"] = total
+        return out
+
     def _loss_single_class(self, img_s, img_q, img_ad, pc_s, pc_q, pc_ad):
-        want = self.repulsion_weight > 0 or self.expansion_weight > 0
+        want = self.repulsion_weight > 0 or self.expansion_weight > 0 or self.uniform_weight > 0
         out, syn, n_q = self._recon_losses(img_s, img_q, img_ad, pc_s, pc_q, pc_ad, want)
         if self.repulsion_weight > 0:
             out = self._with_repulsion(out, syn, n_q)
         if self.expansion_weight > 0:
             out = self._with_expansion(out, syn, n_q)
+        if self.uniform_weight > 0:
+            out = self._with_uniform(out, syn, n_q)
         return out
 
     def _recon_losses(self, img_s, img_q, img_ad, pc_s, pc_q, pc_ad, want_clouds=False):

@@ -7,6 +7,7 @@ contiguity / dtype / device assertions.  There is no CPU path.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import numbers
 
@@ -936,6 +937,165 @@ def expansion_penalty(p: torch.Tensor, patch_size: int, lam: float = 1.5, return
     _hip.dev_tensor(p, torch.float32, "p")
     info = {} if return_info else None
     out = _Expansion.apply(p, P, lam, info)
+    return (out, info) if return_info else out
+
+
+UNIFORM_MAX_N = 16384           # FPSG_UNIFORM_MAX_N (include/fpsg_hip.h)
+UNIFORM_MAX_T = 8               # FPSG_UNIFORM_MAX_T
+UNIFORM_CAPS = (64, 128, 256)   # the retained members per ball; the largest is FPSG_UNIFORM_MAX_MEMBERS
+UNIFORM_PERCENTAGES = (0.004, 0.006, 0.008, 0.010, 0.012)      # PU-GAN's, as fractions of the cloud
+
+
+def check_uniform_options(percentages, radius):
+    """``(percentages, radius)`` of ``uniform_loss`` as a tuple of Python floats and a float: 1..8 percentages, each a
+    fraction in (0, 1], and a positive, finite radius (``ValueError`` naming the argument otherwise)."""
+    if isinstance(percentages, (str, bytes, bool, numbers.Number)) or percentages is None:
+        raise ValueError(f"percentages must be a sequence of 1..{UNIFORM_MAX_T} fractions in (0, 1], got {percentages!r}")
+    try:
+        ps = tuple(percentages)
+    except TypeError:
+        raise ValueError(f"percentages must be a sequence of 1..{UNIFORM_MAX_T} fractions in (0, 1], "
+                         f"got {percentages!r}") from None
+    if not 1 <= len(ps) <= UNIFORM_MAX_T:
+        raise ValueError(f"percentages must hold 1..{UNIFORM_MAX_T} values, got {len(ps)}")
+    out = []
+    for p in ps:
+        try:
+            pf = float(p)
+        except (TypeError, ValueError):
+            raise ValueError(f"percentages must be numbers, got {p!r}") from None
+        if isinstance(p, bool) or not (math.isfinite(pf) and 0.0 < pf <= 1.0):
+            raise ValueError(f"percentages must be in (0, 1], got {p!r}")
+        out.append(pf)
+    try:
+        rf = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError(f"radius must be a number, got {radius!r}") from None
+    if isinstance(radius, bool) or not (math.isfinite(rf) and rf > 0.0):
+        raise ValueError(f"radius must be positive and finite, got {radius!r}")
+    return tuple(out), rf
+
+
+def _uniform_percent_array(percentages):
+    return (ctypes.c_float * len(percentages))(*percentages)
+
+
+class _Uniform(torch.autograd.Function):
+    """K25's forward (ball lists, nearest neighbours inside the balls, the values) and its gather backward on the saved
+    lists."""
+
+    @staticmethod
+    def forward(ctx, p, seeds, percentages, radius, cap, info_out):
+        ctx.set_materialize_grads(False)
+        B, N, _ = p.shape
+        S, T = seeds.size(1), len(percentages)
+        lib = _hip.load()
+        dev = p.device
+        count = torch.empty((B, T, S), dtype=torch.int32, device=dev)
+        member = torch.empty((B, T, S, cap), dtype=torch.int32, device=dev)
+        nn = torch.empty((B, T, S, cap), dtype=torch.int32, device=dev)
+        nn_d2 = torch.empty((B, T, S, cap), dtype=torch.float32, device=dev)
+        ball_value = torch.empty((B, T, S), dtype=torch.float32, device=dev)
+        per_percent = torch.empty((B, T), dtype=torch.float32, device=dev)
+        value = torch.empty((B,), dtype=torch.float32, device=dev)
+        ws_bytes = lib.fpsg_uniform_workspace_bytes(B, N, S, T, cap)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev), _probe("uniform_fwd", B, N, S):
+            rc = lib.fpsg_uniform_fwd(_hip.ptr(p), _hip.ptr(seeds), B, N, S, _uniform_percent_array(percentages), T,
+                                      radius, cap, _hip.ptr(count), _hip.ptr(member), _hip.ptr(nn), _hip.ptr(nn_d2),
+                                      _hip.ptr(ball_value), _hip.ptr(per_percent), _hip.ptr(value), _hip.ptr(ws),
+                                      ws_bytes, _hip.stream_of(p))
+        _hip.check(rc, "fpsg_uniform_fwd")
+        if info_out is not None:
+            info_out.update(count=count, member=member, nn=nn, nn_d2=nn_d2, ball_value=ball_value,
+                            per_percent=per_percent, seeds=seeds)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(p, seeds, count, member, nn, nn_d2)
+            ctx.cfg = (percentages, radius, cap)
+        return value
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None, None
+        p, seeds, count, member, nn, nn_d2 = ctx.saved_tensors
+        percentages, radius, cap = ctx.cfg
+        B, N, _ = p.shape
+        S, T = seeds.size(1), len(percentages)
+        g = g.reshape(B).contiguous().float()
+        gx = torch.empty_like(p)
+        with torch.cuda.device(p.device), _probe("uniform_bwd", B, N, S):
+            rc = _hip.load().fpsg_uniform_bwd(_hip.ptr(p), _hip.ptr(seeds), _hip.ptr(count), _hip.ptr(member),
+                                              _hip.ptr(nn), _hip.ptr(nn_d2), _hip.ptr(g), B, N, S, T,
+                                              _uniform_percent_array(percentages), radius, cap, _hip.ptr(gx),
+                                              _hip.stream_of(p))
+        _hip.check(rc, "fpsg_uniform_bwd")
+        return gx, None, None, None, None, None
+
+
+def uniform_loss(p: torch.Tensor, percentages=UNIFORM_PERCENTAGES, radius: float = 1.0, seeds=None, n_seeds=None,
+                 max_members=None, return_info: bool = False):
+    """PU-GAN's uniform loss ``[B]`` fp32 of the clouds ``p [B,N,3]`` (K25, HIP; the definition is in
+    ``include/fpsg_hip.h``): around every seed point one ball per percentage ``p_t``, of squared radius ``p_t radius^2``;
+    a ball with ``c`` points is charged ``((c - N p_t)^2 / (N p_t)) * sum_i (d_i - dhat)^2 / dhat`` over its members, ``d_i``
+    the distance to the nearest other member and ``dhat = sqrt((2 pi / sqrt 3) p_t radius^2 / c)`` the spacing of ``c``
+    evenly spread points; the value is the mean over the balls.  It is 0 where every ball holds its expected share of an
+    evenly spread surface of area ``pi radius^2`` and grows with balls that are too full, too empty or cluttered.  It
+    needs no ground truth and is added to whichever distance is trained.
+
+    ``seeds``: an integer tensor ``[B,S]`` of indices into the own cloud; ``None``: farthest point sampling (K16) from index
+    0 with ``n_seeds`` picks, by default ``max(1, N // 20)`` (PU-GAN's 5 %).  An index outside ``[0, N)`` owns an empty ball.
+    ``max_members``: the cap on the members a ball retains for the nearest-neighbour search, 64, 128 or 256; ``None``: the
+    smallest of them that is at least ``2 N max(percentages)``, else 256.  The count in the first factor is never capped.
+
+    Differentiable in ``p`` with the counts, the lists and the nearest-neighbour choices held constant; a duplicate pair
+    pushes nobody.  Bitwise the same on every run and independent of the batch, forward and backward (no atomics).  The
+    calls only enqueue: they can be captured.
+
+    ``return_info=True``: returns ``(value, info)`` with ``info["count"] [B,T,S]`` int32 (the full counts),
+    ``info["member"]``, ``info["nn"]`` int32 and ``info["nn_d2"]`` fp32 ``[B,T,S,cap]`` (-1, -1 and +inf behind a list),
+    ``info["ball_value"] [B,T,S]``, ``info["per_percent"] [B,T]`` fp32 and ``info["seeds"] [B,S]`` int32.
+
+    ``ValueError`` (before anything else) for bad percentages or radius, a shape that is not ``[B,N,3]``, ``B = 0``, ``N < 2``,
+    more than 16384 points, bad seeds, ``n_seeds`` outside ``1..N`` or a bad ``max_members``.  No CPU path: a CPU tensor raises
+    ``FpsgHipError``."""
+    percentages, radius = check_uniform_options(percentages, radius)
+    if not isinstance(p, torch.Tensor) or p.dim() != 3 or p.size(2) != 3:
+        raise ValueError(f"expected a [B,N,3] cloud tensor, got {tuple(getattr(p, 'shape', ()))}")
+    B, N, _ = p.shape
+    if B == 0:
+        raise ValueError(f"empty batches are not supported (got {tuple(p.shape)})")
+    if N < 2:
+        raise ValueError(f"uniform_loss needs at least 2 points per cloud, got {N}")
+    if N > UNIFORM_MAX_N:
+        raise ValueError(f"uniform_loss supports at most {UNIFORM_MAX_N} points per cloud, got {N}")
+    if max_members is None:
+        need = 2.0 * N * max(percentages)
+        cap = next((c for c in UNIFORM_CAPS if c >= need), UNIFORM_CAPS[-1])
+    elif isinstance(max_members, bool) or max_members not in UNIFORM_CAPS:
+        raise ValueError(f"max_members must be one of {UNIFORM_CAPS} or None, got {max_members!r}")
+    else:
+        cap = int(max_members)
+    if seeds is not None:
+        if n_seeds is not None:
+            raise ValueError("give seeds or n_seeds, not both")
+        if (not isinstance(seeds, torch.Tensor) or seeds.is_floating_point() or seeds.is_complex()
+                or seeds.dtype == torch.bool):
+            raise ValueError(f"seeds must be an integer tensor, got {getattr(seeds, 'dtype', type(seeds))}")
+        if seeds.dim() != 2 or seeds.size(0) != B or not 1 <= seeds.size(1) <= N:
+            raise ValueError(f"seeds must have shape [B,S] with B = {B} and 1 <= S <= {N}, got {tuple(seeds.shape)}")
+    else:
+        if n_seeds is None:
+            n_seeds = max(1, N // 20)
+        if isinstance(n_seeds, bool) or not isinstance(n_seeds, numbers.Integral) or not 1 <= int(n_seeds) <= N:
+            raise ValueError(f"n_seeds must be an integer from 1 to N = {N}, got {n_seeds!r}")
+    _hip.dev_tensor(p, torch.float32, "p")
+    if seeds is None:
+        from .sampling import farthest_point_sample            # sampling.py imports from this module
+        seeds = farthest_point_sample(p, int(n_seeds))
+    seeds = seeds.detach().to(device=p.device, dtype=torch.int32).contiguous()
+    info = {} if return_info else None
+    out = _Uniform.apply(p, seeds, percentages, radius, cap, info)
     return (out, info) if return_info else out
 
 

@@ -520,6 +520,68 @@ int fpsg_expansion_fwd(const float* xyz, int B, int N, int P, float lambda, int3
 int fpsg_expansion_bwd(const float* xyz, const int32_t* parent, const float* edge_d2, const float* mean_len,
                        const float* gvalue, int B, int N, int P, float lambda, float* gxyz, fpsg_stream_t stream);
 
+/* ---- K25: uniform loss of a cloud (ball query, nearest neighbour inside a ball) -------------------------
+ * PU-GAN's uniform loss (Li et al., ICCV 2019, sec. 3.3): balls of several sizes around seed points; each ball is
+ * charged by how far its point count is from the expected count (imbalance) times how far its members' nearest-
+ * neighbour distances are from the expected spacing (clutter).  The published code is not pinned; the definition below
+ * is the specification (parity UNPINNED).  Inputs: B clouds xyz [N,3] fp32; seeds [B,S] int32 indices
+ * into the own cloud; percent [T] fp32, a HOST array read during the call, each p_t in (0, 1], T <= FPSG_UNIFORM_MAX_T;
+ * a scale radius R > 0; a cap C on the retained members of a ball, 64, 128 or 256.
+ *   r2_t     = fp32(p_t R R), area_t = fp32((2 pi / sqrt 3) r2_t), nhat_t = fp32(N p_t): each product formed in double
+ *              on the host and rounded once (nhat assumes a surface of area pi R^2, as PU-GAN does)
+ *   d2(i,j)  = K1's sq_dist: fma(dz,dz, fma(dy,dy, dx*dx)) (bitwise symmetric, never negative)
+ *   ball(j,t)= the ascending-index list of all i with d2(i, seeds[j]) <= r2_t (fp32 <=: a point exactly on the sphere
+ *              is inside, the seed is its own member, a NaN distance is outside); c = the full count -> count [B,T,S]
+ *              int32; the first m = min(c, C) members are retained -> member [B,T,S,C] int32, -1 behind them
+ *   e_i      = for a retained member i the minimum of d2(i, i') over the OTHER retained members i', nn_i the lowest
+ *              such index -> nn_d2, nn [B,T,S,C] at i's slot; +inf and -1 behind the list and where m = 1
+ *   d_i      = sqrt(e_i) (correctly rounded);  dhat = sqrt(area_t / float(c)): the hexagonal-packing spacing of c
+ *              points in the ball's disc
+ *   term_i   = (d_i - dhat)^2 / dhat, and exactly dhat where e_i == 0 (a duplicate; it has no gradient)
+ *   U(j,t)   = ((float(c) - nhat_t)^2 / nhat_t) * sum_i term_i over the retained members -> ball_value [B,T,S];
+ *              0 where m < 2 and where seeds[j] is outside [0, N): such a seed owns an empty ball (c = 0, nothing read)
+ *   per_percent[b,t] = (sum_j U(j,t)) / S;    value[b] = (sum_t sum_j U(j,t)) / (T S)
+ *   gxyz[i]  = gvalue[b] (1 / (T S)) sum over the balls that retain i of
+ *                [e_i > 0] s_i (x_i - x_nn_i)  +  sum_{i' retained, nn_i' = i, e_i' > 0} s_i' (x_i - x_i'),
+ *              s_i = ((2 w / dhat) (d_i - dhat)) / d_i, w = (float(c) - nhat_t)^2 / nhat_t
+ * (counts, lists and nn choices are piecewise constant: gradient flows through the d_i only).  fp32 throughout; the
+ * divisions and square roots are IEEE.
+ * Orders: retained member q (its place in the list) belongs to lane q % 64, slot q / 64 of its wavefront.  A ball's sum
+ * adds each lane's slots in ascending order from +0, then the 64 lanes by the balanced tree over the lane; the product
+ * with w follows.  A row (b, t) adds U(j, t), j = l, l + 64, ... in ascending order from +0 per lane l, then the lanes by
+ * the same tree; the division by S gives per_percent.  A cloud's T row sums are added in ascending t from +0 and
+ * divided by float(T) * float(S).  A gradient row starts from +0 and walks the balls in ascending (t, j); in a ball that
+ * retains the point it takes its own term, then the terms of the members whose nn it is in list order, each as
+ * fma(s, x_i - x_other, acc) per axis; the product with gvalue[b] * (1 / (T S)) (formed in double, rounded to fp32)
+ * last.  gxyz is written, not accumulated.
+ * The backward repeats the forward's compare d2(i, seeds[j]) <= r2_t on the same bits and finds the point's slot in
+ * the ascending list; it takes count, member, nn and nn_d2 as the forward wrote them but is safe on any int32 / fp32
+ * contents: a count is clamped to the cap, a ball with fewer than two retained members or a seed outside [0, N) is
+ * skipped, as is every member or nn index outside [0, N) and every nn_d2 that is not positive.  Coordinates that are
+ * not finite give unspecified values for their own cloud only, never an access out of bounds.
+ * Bitwise the same on every run, whatever B is and wherever the cloud sits in the batch; no atomics.  Every loop
+ * count depends on N, S, T and C only.  One wavefront owns one (cloud, seed).  The forward is three launches (the
+ * balls; one wave per (cloud, percentage) adds a row; one thread per cloud adds the rows), the backward one (one thread
+ * per point); the workspace holds the forward's B T row sums.  The calls only enqueue work on `stream` (no host
+ * read; they can be captured in a graph).
+ * Errors, all before any launch, in this order: FPSG_E_SHAPE for B, S or T < 1, N < 2, S > N, a radius not positive and
+ * finite, a cap other than 64, 128 or 256; FPSG_E_LIMIT for N > FPSG_UNIFORM_MAX_N or T > FPSG_UNIFORM_MAX_T;
+ * FPSG_E_NULL for a null percent (it is read next); FPSG_E_SHAPE for a percentage outside (0, 1] or not finite;
+ * FPSG_E_NULL for any other null pointer, FPSG_E_ALIGN for a misaligned one; FPSG_E_SHAPE for a workspace smaller than
+ * fpsg_uniform_workspace_bytes, which returns 0 for a shape the entries refuse.
+ */
+#define FPSG_UNIFORM_MAX_N 16384
+#define FPSG_UNIFORM_MAX_T 8
+#define FPSG_UNIFORM_MAX_MEMBERS 256
+size_t fpsg_uniform_workspace_bytes(int B, int N, int S, int T, int cap);
+int fpsg_uniform_fwd(const float* xyz, const int32_t* seeds, int B, int N, int S, const float* percent, int T,
+                     float radius, int cap, int32_t* count, int32_t* member, int32_t* nn, float* nn_d2,
+                     float* ball_value, float* per_percent, float* value, void* workspace, size_t workspace_bytes,
+                     fpsg_stream_t stream);
+int fpsg_uniform_bwd(const float* xyz, const int32_t* seeds, const int32_t* count, const int32_t* member,
+                     const int32_t* nn, const float* nn_d2, const float* gvalue, int B, int N, int S, int T,
+                     const float* percent, float radius, int cap, float* gxyz, fpsg_stream_t stream);
+
 /* ---- K4b: fused EdgeConv (gather + BatchNorm statistics + max over k) -----------------
  * Replaces the chain get_graph_feature -> Conv2d 1x1 -> BatchNorm2d -> LeakyReLU -> max_k of
  * src/dgcnn/model.py:23-42,53-56,63-76 without materialising [B,2C,N,k].  The caller first

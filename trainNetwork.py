@@ -156,7 +156,7 @@ def main(opt):
     for epoch in range(start_epoch, opt.epoch + 1):
         # every rank draws its own episodes; different seeds per (epoch, rank)
         torch.manual_seed(1000003 * epoch + rank)
-        sums = torch.zeros(4, dtype=torch.float64, device=device)
+        sums = torch.zeros(5, dtype=torch.float64, device=device)
         n_steps = max(1, opt.n_episode // eps_per_step)
         # exactly the episodes this rank uses (the worker must not draw one more from the global RNG: the
         # evaluation below and the next epoch's seed share it), drawn and uploaded behind the step
@@ -180,9 +180,11 @@ def main(opt):
                         sums[2] += out["repulsion_loss"].sum() / n_clouds
                     if "expansion_loss" in out:     # only with --expansion_weight, likewise
                         sums[3] += out["expansion_loss"].sum() / n_clouds
+                    if "uniform_loss" in out:       # only with --uniform_weight, likewise
+                        sums[4] += out["uniform_loss"].sum() / n_clouds
         finally:
             it.close()
-        q_sum, s_sum, r_sum, e_sum = fdist.all_reduce_scalars(sums.tolist(), device)   # one host sync per epoch
+        q_sum, s_sum, r_sum, e_sum, u_sum = fdist.all_reduce_scalars(sums.tolist(), device)   # one host sync per epoch
         done = n_steps * eps_per_step
         dt = time.perf_counter() - t0
         log(f"Training Results for Epoch -- {epoch} are: Query_rec: {q_sum / done}, "
@@ -197,6 +199,8 @@ def main(opt):
             print(f"  [repulsion: mean {r_sum / done:.6g} per cloud]")
         if is_main and opt.expansion_weight > 0:
             print(f"  [expansion: mean {e_sum / done:.6g} per cloud]")
+        if is_main and opt.uniform_weight > 0:
+            print(f"  [uniform: mean {u_sum / done:.6g} per cloud]")
         scheduler.step()
 
         evaluating = epoch % opt.eval_interval == 0 or epoch == opt.epoch
