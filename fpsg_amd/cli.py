@@ -29,6 +29,11 @@ K24, added like the repulsion term, and one extra line per epoch), ``--uniform_w
 ``--uniform_radius`` (training: W times PU-GAN's uniform loss of the decoded clouds, K25 -- balls of the given sizes, in
 percent of the cloud, around farthest-point seeds, each charged for its count's imbalance and its members' clutter --
 added like the two terms above, and one extra line per epoch).
+
+A flag that maps one-to-one onto a loss option of the model takes its default from ``few_shot.LOSS_OPTION_DEFAULTS``
+(``--uniform_percent`` is in percent and keeps its own); ``validate`` runs the option checks as the rows of ``_CHECKS``,
+in order, and exits with the first refusal.  A new loss term: its wrapper in ``metrics.py``, a row in
+``few_shot.REGULARISERS``, its options in ``LOSS_OPTION_DEFAULTS``, its flags here.
 """
 from __future__ import annotations
 
@@ -41,9 +46,9 @@ from torch.utils.data import DataLoader
 
 from . import eval_report
 from .ema import check_ema_decay
-from .few_shot import check_expansion_weight, check_repulsion_weight, check_uniform_weight
-from .metrics import (SINKHORN_TRAIN_DIAMETER, UNIFORM_MAX_T, check_expansion_options,
-                      check_repulsion_options, check_sinkhorn_option, check_swd_options, check_uniform_options)
+from .few_shot import LOSS_OPTION_DEFAULTS, check_weight
+from .metrics import (UNIFORM_MAX_T, check_expansion_options, check_repulsion_options, check_sinkhorn_option,
+                      check_swd_options, check_uniform_options)
 from .episodes import EpisodicBatchSampler, SequentialBatchSampler, SyntheticFewShot
 
 
@@ -97,44 +102,44 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--lr_decay", type=float, default=350)
     g.add_argument("--resume", type=int, default=-1)
     g.add_argument("--pc_dist", type=str, default="cd", choices=["cd", "emd", "dcd", "sinkhorn", "swd"])
-    g.add_argument("--dcd_alpha", type=float, default=1000.0,
+    g.add_argument("--dcd_alpha", type=float, default=LOSS_OPTION_DEFAULTS["dcd_alpha"],
                    help="With --pc_dist dcd: the factor on the squared nearest-neighbour distance inside the exponential "
                         "of the density-aware Chamfer distance [default: 1000];")
-    g.add_argument("--sinkhorn_blur", type=float, default=0.05,
+    g.add_argument("--sinkhorn_blur", type=float, default=LOSS_OPTION_DEFAULTS["sinkhorn_blur"],
                    help="With --pc_dist sinkhorn: the blur of the Sinkhorn divergence, the annealing ends at blur^2 "
                         "[default: 0.05, as the evaluation's EMD];")
-    g.add_argument("--sinkhorn_diameter", type=float, default=SINKHORN_TRAIN_DIAMETER,
+    g.add_argument("--sinkhorn_diameter", type=float, default=LOSS_OPTION_DEFAULTS["sinkhorn_diameter"],
                    help="With --pc_dist sinkhorn: the FIXED diameter the annealing schedule starts from [default: 2*sqrt(3), "
                         "the diagonal of [-1,1]^3].  The evaluation's EMD takes each item's own bounding-box diagonal "
                         "instead, so its value differs slightly (under 1 %% on unit-ball clouds); a fixed one keeps the "
                         "training step free of host reads;")
-    g.add_argument("--swd_n_proj", type=int, default=64, metavar="L",
+    g.add_argument("--swd_n_proj", type=int, default=LOSS_OPTION_DEFAULTS["swd_n_proj"], metavar="L",
                    help="With --pc_dist swd: the number of directions the sliced Wasserstein distance projects on, "
                         "1..1024 [default: 64];")
-    g.add_argument("--swd_directions", type=str, default="random", metavar="{random,fixed}",
+    g.add_argument("--swd_directions", type=str, default=LOSS_OPTION_DEFAULTS["swd_directions"], metavar="{random,fixed}",
                    help="With --pc_dist swd: 'random' draws fresh unit vectors for every loss, 'fixed' uses one Fibonacci "
                         "lattice on the sphere throughout [default: random];")
     g.add_argument("--clip_grad_norm", type=_clip_norm, default=0.0, metavar="X",
                    help="Clip the 2-norm of every optimizer step's mean gradient to X [default: 0 = off]; prints the "
                         "largest norm and the number of clipped steps after every epoch;")
-    g.add_argument("--repulsion_weight", type=float, default=0.0, metavar="W",
+    g.add_argument("--repulsion_weight", type=float, default=LOSS_OPTION_DEFAULTS["repulsion_weight"], metavar="W",
                    help="Add W times the repulsion term of the generated clouds (each point against its nearest "
                         "neighbours in its own cloud) to the training loss, under any --pc_dist [default: 0 = off]; prints "
                         "the mean term per cloud after every epoch;")
-    g.add_argument("--repulsion_k", type=int, default=4, metavar="K",
+    g.add_argument("--repulsion_k", type=int, default=LOSS_OPTION_DEFAULTS["repulsion_k"], metavar="K",
                    help="With --repulsion_weight: neighbours per point, 1..8 [default: 4];")
-    g.add_argument("--repulsion_h", type=float, default=0.03, metavar="H",
+    g.add_argument("--repulsion_h", type=float, default=LOSS_OPTION_DEFAULTS["repulsion_h"], metavar="H",
                    help="With --repulsion_weight: the bandwidth of the term, a length -- clouds live in the unit ball "
                         "[default: 0.03];")
-    g.add_argument("--expansion_weight", type=float, default=0.0, metavar="W",
+    g.add_argument("--expansion_weight", type=float, default=LOSS_OPTION_DEFAULTS["expansion_weight"], metavar="W",
                    help="Add W times the expansion penalty of the generated clouds (each decoder patch charged for the "
                         "edges of its minimum spanning tree that are longer than L times the tree's mean edge) to the "
                         "training loss, under any --pc_dist [default: 0 = off]; prints the mean penalty per cloud after "
                         "every epoch;")
-    g.add_argument("--expansion_lambda", type=float, default=1.5, metavar="L",
+    g.add_argument("--expansion_lambda", type=float, default=LOSS_OPTION_DEFAULTS["expansion_lambda"], metavar="L",
                    help="With --expansion_weight: an edge is charged where it is longer than L times its patch's mean "
                         "edge, L >= 1 [default: 1.5];")
-    g.add_argument("--uniform_weight", type=float, default=0.0, metavar="W",
+    g.add_argument("--uniform_weight", type=float, default=LOSS_OPTION_DEFAULTS["uniform_weight"], metavar="W",
                    help="Add W times the uniform loss of the generated clouds (balls of several sizes around farthest-point "
                         "seeds, each charged for how far its point count is from its share and how far its members' "
                         "nearest-neighbour distances are from an even spacing) to the training loss, under any --pc_dist "
@@ -142,7 +147,7 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--uniform_percent", type=float, nargs="+", default=[0.4, 0.6, 0.8, 1.0, 1.2], metavar="P",
                    help="With --uniform_weight: the balls' sizes in percent of the cloud, each in (0, 100], at most 8 "
                         "[default: 0.4 0.6 0.8 1.0 1.2];")
-    g.add_argument("--uniform_radius", type=float, default=1.0, metavar="R",
+    g.add_argument("--uniform_radius", type=float, default=LOSS_OPTION_DEFAULTS["uniform_radius"], metavar="R",
                    help="With --uniform_weight: the radius of the disc whose area the surface is taken to have, a length "
                         "-- clouds live in the unit ball [default: 1.0];")
     g.add_argument("--ema_decay", type=float, default=0.0, metavar="D",
@@ -183,59 +188,40 @@ def uniform_fractions(percent) -> tuple:
     return tuple(v / 100.0 for v in values)
 
 
+def _uniform_percent(opt) -> None:
+    opt.uniform_percentages = uniform_fractions(opt.uniform_percent)       # what the model takes
+
+
+# validate()'s option checks in the order they run: (the attribute without which -- an older namespace -- the check is
+# skipped, the check: ValueError for a bad value, what goes in front of its message)
+_CHECKS = (
+    ("sinkhorn_blur", lambda o: check_sinkhorn_option(o.sinkhorn_blur, "sinkhorn_blur"), "--"),
+    ("sinkhorn_diameter", lambda o: check_sinkhorn_option(o.sinkhorn_diameter, "sinkhorn_diameter"), "--"),
+    ("swd_n_proj", lambda o: check_swd_options(o.swd_n_proj, getattr(o, "swd_directions",
+                                                                      LOSS_OPTION_DEFAULTS["swd_directions"])), "--swd_"),
+    ("repulsion_weight", lambda o: check_weight(o.repulsion_weight, "repulsion_weight"), "--"),
+    ("repulsion_weight", lambda o: check_repulsion_options(o.repulsion_k, o.repulsion_h), "--repulsion_"),
+    ("expansion_weight", lambda o: check_weight(o.expansion_weight, "expansion_weight"), "--"),
+    ("expansion_weight", lambda o: check_expansion_options(2, o.expansion_lambda), "--expansion_lambda: "),
+    ("uniform_weight", lambda o: check_weight(o.uniform_weight, "uniform_weight"), "--"),
+    ("uniform_weight", _uniform_percent, "--uniform_percent: "),
+    ("uniform_weight", lambda o: check_uniform_options(o.uniform_percentages, o.uniform_radius), "--uniform_"),
+    ("ema_decay", lambda o: check_ema_decay(o.ema_decay), "--"),
+)
+
+
 def validate(opt) -> None:
     if not opt.synthetic and not (opt.config_path and opt.test_path):
         raise SystemExit("--config_path and --test_path are required unless --synthetic is given")
     if opt.n_way != 1:
         raise SystemExit("only 1-way episodes are defined by the model (as in the reference)")
     eval_report.check_alpha_option(opt, "dcd_alpha")
-    for flag in ("sinkhorn_blur", "sinkhorn_diameter"):
-        if getattr(opt, flag, None) is not None:
+    for gate, check, prefix in _CHECKS:
+        if getattr(opt, gate, None) is not None:
             try:
-                check_sinkhorn_option(getattr(opt, flag), flag)
+                check(opt)
             except ValueError as e:
-                raise SystemExit(f"--{e}") from None
-    if getattr(opt, "swd_n_proj", None) is not None:
-        try:
-            check_swd_options(opt.swd_n_proj, getattr(opt, "swd_directions", "random"))
-        except ValueError as e:
-            raise SystemExit(f"--swd_{e}") from None
-    if getattr(opt, "repulsion_weight", None) is not None:
-        try:
-            check_repulsion_weight(opt.repulsion_weight)
-        except ValueError as e:
-            raise SystemExit(f"--{e}") from None
-        try:
-            check_repulsion_options(opt.repulsion_k, opt.repulsion_h)
-        except ValueError as e:
-            raise SystemExit(f"--repulsion_{e}") from None
-    if getattr(opt, "expansion_weight", None) is not None:
-        try:
-            check_expansion_weight(opt.expansion_weight)
-        except ValueError as e:
-            raise SystemExit(f"--{e}") from None
-        try:
-            check_expansion_options(2, opt.expansion_lambda)
-        except ValueError as e:
-            raise SystemExit(f"--expansion_lambda: {e}") from None
-    if getattr(opt, "uniform_weight", None) is not None:
-        try:
-            check_uniform_weight(opt.uniform_weight)
-        except ValueError as e:
-            raise SystemExit(f"--{e}") from None
-        try:
-            opt.uniform_percentages = uniform_fractions(opt.uniform_percent)
-        except ValueError as e:
-            raise SystemExit(f"--uniform_percent: {e}") from None
-        try:
-            check_uniform_options(opt.uniform_percentages, opt.uniform_radius)
-        except ValueError as e:
-            raise SystemExit(f"--uniform_{e}") from None
-    if getattr(opt, "ema_decay", None) is not None:
-        try:
-            check_ema_decay(opt.ema_decay)
-        except ValueError as e:
-            raise SystemExit(f"--{e}") from None
+                raise SystemExit(f"{prefix}{e}") from None
     eval_report.check(opt)          # the evaluation report's options; a training namespace has none of them
 
 

@@ -16,9 +16,9 @@ import torch.optim as optim
 
 from . import dist as fdist
 from . import bn_counters, eval_report, winograd
-from .few_shot import ImgPCProtoNet
+from .few_shot import LOSS_OPTION_DEFAULTS, ImgPCProtoNet
 from .image_net import ImageEncoderWarpper
-from .metrics import SINKHORN_TRAIN_DIAMETER, UNIFORM_PERCENTAGES, check_dcd_alpha, check_thresholds, nearest_rows
+from .metrics import check_dcd_alpha, check_thresholds, nearest_rows
 from .ema import WeightEma, check_ema_decay
 from .optim import FlatAdam, check_max_grad_norm
 from .point_cloud_net import PCDecoder, PCEncoder
@@ -26,15 +26,13 @@ from .point_cloud_net import PCDecoder, PCEncoder
 
 def default_options(**overrides) -> argparse.Namespace:
     """The reference's argparse defaults (``trainNetwork.py:215-261``) for everything the
-    model constructors read."""
+    model constructors read, and the model's loss options (``few_shot.LOSS_OPTION_DEFAULTS``)."""
     opt = argparse.Namespace(
         img_encoder="vgg_16", pc_encoder="pointnet", pc_encoder_path="", img_encoder_path="",
         support_factor=1.0, query_factor=1.0, intra_recon=False, num_clusters=4, ori_dim=2,
         raw_dim=3, num_nodes=4, device="cuda", bottleneck_size=1536, template_type="SQUARE",
         activation="relu", aggregate="single", pc_dist="cd", lr=1e-3, lr_decay=350, SGD=False,
-        n_way=1, n_shot=20, n_query=0, clip_grad_norm=0.0, repulsion_weight=0.0, repulsion_k=4, repulsion_h=0.03,
-        swd_n_proj=64, swd_directions="random", ema_decay=0.0, expansion_weight=0.0, expansion_lambda=1.5,
-        uniform_weight=0.0, uniform_percentages=UNIFORM_PERCENTAGES, uniform_radius=1.0)
+        n_way=1, n_shot=20, n_query=0, clip_grad_norm=0.0, ema_decay=0.0, **LOSS_OPTION_DEFAULTS)
     for k, v in overrides.items():
         setattr(opt, k, v)
     return opt
@@ -52,18 +50,8 @@ def build_model(opt) -> ImgPCProtoNet:
     return ImgPCProtoNet(img_encoder, pc_encoder, pc_decoder, mask_learner=None,
                          query_factor=opt.query_factor, support_factor=opt.support_factor,
                          metric=getattr(opt, "pc_dist", "cd"), intra_support=opt.intra_recon,
-                         aggregate=opt.aggregate, dcd_alpha=getattr(opt, "dcd_alpha", 1000.0),
-                         sinkhorn_blur=getattr(opt, "sinkhorn_blur", 0.05),
-                         sinkhorn_diameter=getattr(opt, "sinkhorn_diameter", SINKHORN_TRAIN_DIAMETER),
-                         repulsion_weight=getattr(opt, "repulsion_weight", 0.0),
-                         repulsion_k=getattr(opt, "repulsion_k", 4), repulsion_h=getattr(opt, "repulsion_h", 0.03),
-                         swd_n_proj=getattr(opt, "swd_n_proj", 64),
-                         swd_directions=getattr(opt, "swd_directions", "random"),
-                         expansion_weight=getattr(opt, "expansion_weight", 0.0),
-                         expansion_lambda=getattr(opt, "expansion_lambda", 1.5),
-                         uniform_weight=getattr(opt, "uniform_weight", 0.0),
-                         uniform_percentages=getattr(opt, "uniform_percentages", UNIFORM_PERCENTAGES),
-                         uniform_radius=getattr(opt, "uniform_radius", 1.0))
+                         aggregate=opt.aggregate,
+                         **{name: getattr(opt, name, default) for name, default in LOSS_OPTION_DEFAULTS.items()})
 
 
 def build_optimizer(model, opt):

@@ -13,17 +13,16 @@ and ``metric='emd'`` works instead of raising AttributeError.
 """
 from __future__ import annotations
 
-import math
 import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from .metrics import (SINKHORN_TRAIN_DIAMETER, UNIFORM_PERCENTAGES, chamfer_distance, check_dcd_alpha, check_expansion_options,
-                      check_repulsion_options, check_sinkhorn_option, check_swd_options, dcd, emd_loss,
-                      check_uniform_options, episode_chamfer_losses, expansion_penalty, repulsion_loss, sinkhorn_loss,
-                      swd_directions, swd_loss, uniform_loss)
+from .metrics import (DCD_DEFAULT_ALPHA, SINKHORN_TRAIN_DIAMETER, UNIFORM_PERCENTAGES, _finite_number, chamfer_distance,
+                      check_dcd_alpha, check_expansion_options, check_repulsion_options, check_sinkhorn_option,
+                      check_swd_options, check_uniform_options, dcd, emd_loss, episode_chamfer_losses, expansion_penalty,
+                      repulsion_loss, sinkhorn_loss, swd_directions, swd_loss, uniform_loss)
 from .utils import emd_wrapper
 
 _AGGREGATOR = ["single", "multi", "mask_single", "mask_multi"]
@@ -34,29 +33,42 @@ def _fused_losses_enabled() -> bool:
     return os.environ.get("FPSG_FUSED_LOSSES", "1") != "0"
 
 
-def _check_weight(weight, name) -> float:
-    try:
-        w = float(weight)
-    except (TypeError, ValueError):
-        raise ValueError(f"{name} must be a number, got {weight!r}") from None
-    if isinstance(weight, bool) or not (math.isfinite(w) and w >= 0.0):
-        raise ValueError(f"{name} must be finite and non-negative, got {weight!r}")
-    return w
+# The regularisers: scalar terms on the episode's decoded clouds, added to whichever distance is trained.  One row per
+# term: (name, the key it writes into the loss dict, the model attribute that holds its weight); the model's method
+# ``_<name>_term(clouds)`` gives the term's value per cloud.  The order of the rows is the order in which the terms are
+# added to ``ttl_loss`` (float addition: the order is observable) and in which their keys enter the dict.
+REGULARISERS = (("repulsion", "repulsion_loss", "repulsion_weight"),
+                ("expansion", "expansion_loss", "expansion_weight"),
+                ("uniform", "uniform_loss", "uniform_weight"))
+
+# Every loss option of ``ImgPCProtoNet`` and its default: what ``engine.default_options``, ``engine.build_model`` and the
+# parser's flags of the same names take theirs from.  The constructor's signature repeats them
+# (tests/test_loss_terms_cpu.py holds the two together).
+LOSS_OPTION_DEFAULTS = {
+    "dcd_alpha": DCD_DEFAULT_ALPHA, "sinkhorn_blur": 0.05, "sinkhorn_diameter": SINKHORN_TRAIN_DIAMETER,
+    "swd_n_proj": 64, "swd_directions": "random", "repulsion_weight": 0.0, "repulsion_k": 4, "repulsion_h": 0.03,
+    "expansion_weight": 0.0, "expansion_lambda": 1.5, "uniform_weight": 0.0, "uniform_percentages": UNIFORM_PERCENTAGES,
+    "uniform_radius": 1.0}
+
+
+def check_weight(weight, name) -> float:
+    """A regulariser's weight ``name`` as a Python float: a finite, non-negative number (``ValueError`` otherwise)."""
+    return _finite_number(weight, name, lambda w: w >= 0.0, "finite and non-negative")
 
 
 def check_repulsion_weight(weight) -> float:
     """``repulsion_weight`` as a Python float: a finite, non-negative number (``ValueError`` otherwise)."""
-    return _check_weight(weight, "repulsion_weight")
+    return check_weight(weight, "repulsion_weight")
 
 
 def check_expansion_weight(weight) -> float:
     """``expansion_weight`` as a Python float: a finite, non-negative number (``ValueError`` otherwise)."""
-    return _check_weight(weight, "expansion_weight")
+    return check_weight(weight, "expansion_weight")
 
 
 def check_uniform_weight(weight) -> float:
     """``uniform_weight`` as a Python float: a finite, non-negative number (``ValueError`` otherwise)."""
-    return _check_weight(weight, "uniform_weight")
+    return check_weight(weight, "uniform_weight")
 
 
 class _SplitRows(torch.autograd.Function):
@@ -133,22 +145,22 @@ class ImgPCProtoNet(nn.Module):
         # can drive the module on CPU with the oracle's implementations
         self.emd_metric = emd_wrapper
         self._batched_pairs = metric in ("dcd", "sinkhorn", "swd")      # one call over the Q + S pairs (below)
-        # the repulsion regulariser (K21) on the decoded clouds, added to whichever distance is trained; 0: off, and
-        # the loss is what it is without these arguments, launch for launch
-        self.repulsion_weight = check_repulsion_weight(repulsion_weight)
+        # the regularisers (REGULARISERS) on the decoded clouds; weight 0: off, and the loss is what it is without these
+        # arguments, launch for launch.  The repulsion regulariser (K21):
+        self.repulsion_weight = check_weight(repulsion_weight, "repulsion_weight")
         self.repulsion_k, self.repulsion_h = check_repulsion_options(repulsion_k, repulsion_h)
-        # the expansion penalty (K24) on the decoded clouds' patches, added like the repulsion term; 0: off.  The patch
-        # size is the decoder's: its cloud is (cluster, node) patches of that many consecutive rows
-        self.expansion_weight = check_expansion_weight(expansion_weight)
+        # the expansion penalty (K24) on the decoded clouds' patches.  The patch size is the decoder's: its cloud is
+        # (cluster, node) patches of that many consecutive rows
+        self.expansion_weight = check_weight(expansion_weight, "expansion_weight")
         _, self.expansion_lambda = check_expansion_options(2, expansion_lambda)
         self.expansion_patch = getattr(pc_decoder, "pts_per_patch", None)
         if self.expansion_weight > 0:
             if self.expansion_patch is None:
                 raise ValueError("expansion_weight needs a decoder that exposes its points per patch (pts_per_patch)")
             self.expansion_patch, _ = check_expansion_options(self.expansion_patch, self.expansion_lambda)
-        # the uniform loss (K25) on the decoded clouds, added like the two terms above; 0: off.  The seeds are K16's farthest
-        # point sample of each decoded cloud (5 % of its points)
-        self.uniform_weight = check_uniform_weight(uniform_weight)
+        # the uniform loss (K25) on the decoded clouds.  The seeds are K16's farthest point sample of each decoded cloud
+        # (5 % of its points)
+        self.uniform_weight = check_weight(uniform_weight, "uniform_weight")
         self.uniform_percentages, self.uniform_radius = check_uniform_options(uniform_percentages, uniform_radius)
         self.overlap_encoders = False      # see _encode; switched on by bench.py / the trainer
         self._side_stream = None
@@ -238,67 +250,38 @@ class ImgPCProtoNet(nn.Module):
         return self._loss_single_class(sample["xs"], sample["xq"], sample["xad"], sample["pcs"],
                                        sample["pcq"], sample["pcad"])
 
-    def _with_repulsion(self, out, syn, n_q):
-        """Adds the repulsion term of the episode's decoded clouds ``syn`` (the first ``n_q`` are the queries', the rest
-        the supports') to the loss dict: ONE K21 call; ``ttl_loss`` gains ``repulsion_weight * (query_factor * sum_q R
-        + support_factor * sum_s R)``, ``repulsion_loss`` is the unweighted sum, every other entry stays as it is."""
-        rep = repulsion_loss(syn.contiguous(), self.repulsion_k, self.repulsion_h)
-        rep_q = rep[:n_q].sum()
-        weighted = self.query_factor * rep_q
-        total = rep_q
-        if n_q < rep.size(0):
-            rep_s = rep[n_q:].sum()
-            weighted = weighted + self.support_factor * rep_s
-            total = total + rep_s
-        out = dict(out)
-        out["ttl_loss"] = out["recon_loss"] + self.repulsion_weight * weighted
-        out["repulsion_loss"] = total
-        return out
+    # a regulariser's value per cloud, [Q+S] fp32: ONE call of its function (K21; K24; K16 for the seeds and K25), looked
+    # up in the module at call time
+    def _repulsion_term(self, syn):
+        return repulsion_loss(syn, self.repulsion_k, self.repulsion_h)
 
-    def _with_expansion(self, out, syn, n_q):
-        """Adds the expansion penalty of the episode's decoded clouds to the loss dict (behind the repulsion term where
-        both are on): ONE K24 call; ``ttl_loss`` gains ``expansion_weight * (query_factor * sum_q E + support_factor *
-        sum_s E)``, ``expansion_loss`` is the unweighted sum, every other entry stays as it is."""
-        pen = expansion_penalty(syn.contiguous(), self.expansion_patch, self.expansion_lambda)
-        pen_q = pen[:n_q].sum()
-        weighted = self.query_factor * pen_q
-        total = pen_q
-        if n_q < pen.size(0):
-            pen_s = pen[n_q:].sum()
-            weighted = weighted + self.support_factor * pen_s
-            total = total + pen_s
-        out = dict(out)
-        out["ttl_loss"] = out["ttl_loss"] + self.expansion_weight * weighted
-        out["expansion_loss"] = total
-        return out
+    def _expansion_term(self, syn):
+        return expansion_penalty(syn, self.expansion_patch, self.expansion_lambda)
 
-    def _with_uniform(self, out, syn, n_q):
-        """Adds the uniform loss of the episode's decoded clouds to the loss dict (behind the repulsion and expansion
-        terms where they are on): ONE K16 call for the seeds and ONE K25 call; ``ttl_loss`` gains ``uniform_weight *
-        (query_factor * sum_q U + support_factor * sum_s U)``, ``uniform_loss`` is the unweighted sum, every other entry
-        stays as it is."""
-        uni = uniform_loss(syn.contiguous(), self.uniform_percentages, self.uniform_radius)
-        uni_q = uni[:n_q].sum()
-        weighted = self.query_factor * uni_q
-        total = uni_q
-        if n_q < uni.size(0):
-            uni_s = uni[n_q:].sum()
-            weighted = weighted + self.support_factor * uni_s
-            total = total + uni_s
-        out = dict(out)
-        out["ttl_loss"] = out["ttl_loss"] + self.uniform_weight * weighted
-        out["uniform_loss"] = total
-        return out
+    def _uniform_term(self, syn):
+        return uniform_loss(syn, self.uniform_percentages, self.uniform_radius)
+
+    def _add_term(self, out, values, n_q, weight, key):
+        """Adds a regulariser's values per decoded cloud (the first ``n_q`` are the queries', the rest the supports') to
+        the loss dict: ``ttl_loss`` gains ``weight * (query_factor * sum_q + support_factor * sum_s)``, ``out[key]`` is the
+        unweighted sum, every other entry stays as it is."""
+        q_sum = values[:n_q].sum()
+        weighted = self.query_factor * q_sum
+        total = q_sum
+        if n_q < values.size(0):
+            s_sum = values[n_q:].sum()
+            weighted = weighted + self.support_factor * s_sum
+            total = total + s_sum
+        out["ttl_loss"] = out["ttl_loss"] + weight * weighted
+        out[key] = total
 
     def _loss_single_class(self, img_s, img_q, img_ad, pc_s, pc_q, pc_ad):
-        want = self.repulsion_weight > 0 or self.expansion_weight > 0 or self.uniform_weight > 0
-        out, syn, n_q = self._recon_losses(img_s, img_q, img_ad, pc_s, pc_q, pc_ad, want)
-        if self.repulsion_weight > 0:
-            out = self._with_repulsion(out, syn, n_q)
-        if self.expansion_weight > 0:
-            out = self._with_expansion(out, syn, n_q)
-        if self.uniform_weight > 0:
-            out = self._with_uniform(out, syn, n_q)
+        active = [(name, key, getattr(self, attr)) for name, key, attr in REGULARISERS if getattr(self, attr) > 0]
+        out, syn, n_q = self._recon_losses(img_s, img_q, img_ad, pc_s, pc_q, pc_ad, bool(active))
+        if active:
+            syn = syn.contiguous()
+            for name, key, weight in active:
+                self._add_term(out, getattr(self, f"_{name}_term")(syn), n_q, weight, key)
         return out
 
     def _recon_losses(self, img_s, img_q, img_ad, pc_s, pc_q, pc_ad, want_clouds=False):

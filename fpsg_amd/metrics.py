@@ -58,6 +58,43 @@ def _check_clouds(p1: torch.Tensor, p2: torch.Tensor):
     _hip.dev_tensor(p2, torch.float32, "p2")
 
 
+def _finite_number(value, name, ok, wording, allow_bool=False, number="a number") -> float:
+    """``value`` as a Python float: a number that is finite and passes ``ok`` -- ``ValueError`` ``"<name> must be
+    <wording>, got ..."`` otherwise, ``"<name> must be <number>, got ..."`` where ``float()`` refuses it.  ``bool`` counts as
+    a number only where ``allow_bool``."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be {number}, got {value!r}") from None
+    if (isinstance(value, bool) and not allow_bool) or not (math.isfinite(v) and ok(v)):
+        raise ValueError(f"{name} must be {wording}, got {value!r}")
+    return v
+
+
+def _integer_in(value, name, lo, hi) -> int:
+    """``value`` as a Python int: an integer (never ``bool``) in ``lo..hi`` (``ValueError`` naming ``name`` otherwise)."""
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral):
+        raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {value!r}")
+    if not lo <= int(value) <= hi:
+        raise ValueError(f"{name} must be in {lo}..{hi}, got {value!r}")
+    return int(value)
+
+
+def _check_cloud(p, fn, max_n, n_ok, n_rule):
+    """What a loss of ONE cloud batch checks in front of its launch: ``p`` is ``[B,N,3]``, ``B > 0``, ``n_ok(N)`` (worded
+    ``n_rule``) and ``N <= max_n``; ``ValueError`` otherwise, in that order.  Returns ``(B, N)``."""
+    if not isinstance(p, torch.Tensor) or p.dim() != 3 or p.size(2) != 3:
+        raise ValueError(f"expected a [B,N,3] cloud tensor, got {tuple(getattr(p, 'shape', ()))}")
+    B, N, _ = p.shape
+    if B == 0:
+        raise ValueError(f"empty batches are not supported (got {tuple(p.shape)})")
+    if not n_ok(N):
+        raise ValueError(f"{fn} needs {n_rule} points per cloud, got {N}")
+    if N > max_n:
+        raise ValueError(f"{fn} supports at most {max_n} points per cloud, got {N}")
+    return B, N
+
+
 def _sided_forward(p1, p2, losses=None):
     """K1 forward through the C ABI: ``(dist1 [B,N], dist2 [B,M], idx1, idx2)``, idx int32.
     ``losses = (n_first, w_first, w_rest)``: also K1l's three sums (``out3``, a fifth result) -- fused into the
@@ -635,13 +672,7 @@ DCD_DEFAULT_ALPHA = 1000.0
 
 def check_dcd_alpha(alpha) -> float:
     """``alpha`` of ``dcd`` as a Python float: a finite, non-negative number (``ValueError`` otherwise)."""
-    try:
-        a = float(alpha)
-    except (TypeError, ValueError):
-        raise ValueError(f"alpha must be a number, got {alpha!r}") from None
-    if not (math.isfinite(a) and a >= 0.0):
-        raise ValueError(f"alpha must be finite and non-negative, got {alpha!r}")
-    return a
+    return _finite_number(alpha, "alpha", lambda a: a >= 0.0, "finite and non-negative", allow_bool=True)
 
 
 def _dcd_from_rows(dist1, idx1, dist2, idx2, alpha, need1, need2):
@@ -758,17 +789,8 @@ REPULSION_MAX_K = 8             # FPSG_REPULSION_MAX_K
 def check_repulsion_options(k, h):
     """``(k, h)`` of ``repulsion_loss`` as a Python int and float: ``k`` an integer in 1..8, ``h`` a positive, finite
     number (``ValueError`` naming the argument otherwise)."""
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral):
-        raise ValueError(f"k must be an integer in 1..{REPULSION_MAX_K}, got {k!r}")
-    if not 1 <= int(k) <= REPULSION_MAX_K:
-        raise ValueError(f"k must be in 1..{REPULSION_MAX_K}, got {k!r}")
-    try:
-        hf = float(h)
-    except (TypeError, ValueError):
-        raise ValueError(f"h must be a number, got {h!r}") from None
-    if isinstance(h, bool) or not (math.isfinite(hf) and hf > 0.0):
-        raise ValueError(f"h must be positive and finite, got {h!r}")
-    return int(k), hf
+    k = _integer_in(k, "k", 1, REPULSION_MAX_K)
+    return k, _finite_number(h, "h", lambda v: v > 0.0, "positive and finite")
 
 
 class _Repulsion(torch.autograd.Function):
@@ -828,14 +850,7 @@ def repulsion_loss(p: torch.Tensor, k: int = 4, h: float = 0.03, return_info: bo
     ``ValueError`` (before anything else) for a bad ``k`` or ``h``, a shape that is not ``[B,N,3]``, ``B = 0``, ``N < k + 1``
     and more than 16384 points.  No CPU path: a CPU tensor raises ``FpsgHipError``."""
     k, h = check_repulsion_options(k, h)
-    if not isinstance(p, torch.Tensor) or p.dim() != 3 or p.size(2) != 3:
-        raise ValueError(f"expected a [B,N,3] cloud tensor, got {tuple(getattr(p, 'shape', ()))}")
-    if p.size(0) == 0:
-        raise ValueError(f"empty batches are not supported (got {tuple(p.shape)})")
-    if p.size(1) < k + 1:
-        raise ValueError(f"repulsion_loss needs at least k + 1 = {k + 1} points per cloud, got {p.size(1)}")
-    if p.size(1) > REPULSION_MAX_N:
-        raise ValueError(f"repulsion_loss supports at most {REPULSION_MAX_N} points per cloud, got {p.size(1)}")
+    _check_cloud(p, "repulsion_loss", REPULSION_MAX_N, lambda N: N >= k + 1, f"at least k + 1 = {k + 1}")
     _hip.dev_tensor(p, torch.float32, "p")
     info = {} if return_info else None
     out = _Repulsion.apply(p, k, h, info)
@@ -849,17 +864,8 @@ EXPANSION_MAX_N = 16384         # FPSG_EXPANSION_MAX_N
 def check_expansion_options(patch_size, lam):
     """``(patch_size, lam)`` of ``expansion_penalty`` as a Python int and float: ``patch_size`` an integer in 2..1024,
     ``lam`` a finite number of at least 1 (``ValueError`` naming the argument otherwise)."""
-    if isinstance(patch_size, bool) or not isinstance(patch_size, numbers.Integral):
-        raise ValueError(f"patch_size must be an integer in 2..{EXPANSION_MAX_P}, got {patch_size!r}")
-    if not 2 <= int(patch_size) <= EXPANSION_MAX_P:
-        raise ValueError(f"patch_size must be in 2..{EXPANSION_MAX_P}, got {patch_size!r}")
-    try:
-        lf = float(lam)
-    except (TypeError, ValueError):
-        raise ValueError(f"lam must be a number, got {lam!r}") from None
-    if isinstance(lam, bool) or not (math.isfinite(lf) and lf >= 1.0):
-        raise ValueError(f"lam must be finite and at least 1, got {lam!r}")
-    return int(patch_size), lf
+    patch_size = _integer_in(patch_size, "patch_size", 2, EXPANSION_MAX_P)
+    return patch_size, _finite_number(lam, "lam", lambda v: v >= 1.0, "finite and at least 1")
 
 
 class _Expansion(torch.autograd.Function):
@@ -925,15 +931,8 @@ def expansion_penalty(p: torch.Tensor, patch_size: int, lam: float = 1.5, return
     not a positive multiple of ``patch_size`` and more than 16384 points.  No CPU path: a CPU tensor raises
     ``FpsgHipError``."""
     P, lam = check_expansion_options(patch_size, lam)
-    if not isinstance(p, torch.Tensor) or p.dim() != 3 or p.size(2) != 3:
-        raise ValueError(f"expected a [B,N,3] cloud tensor, got {tuple(getattr(p, 'shape', ()))}")
-    if p.size(0) == 0:
-        raise ValueError(f"empty batches are not supported (got {tuple(p.shape)})")
-    if p.size(1) < P or p.size(1) % P != 0:
-        raise ValueError(f"expansion_penalty needs a positive multiple of patch_size = {P} points per cloud, "
-                         f"got {p.size(1)}")
-    if p.size(1) > EXPANSION_MAX_N:
-        raise ValueError(f"expansion_penalty supports at most {EXPANSION_MAX_N} points per cloud, got {p.size(1)}")
+    _check_cloud(p, "expansion_penalty", EXPANSION_MAX_N, lambda N: N >= P and N % P == 0,
+                 f"a positive multiple of patch_size = {P}")
     _hip.dev_tensor(p, torch.float32, "p")
     info = {} if return_info else None
     out = _Expansion.apply(p, P, lam, info)
@@ -958,22 +957,8 @@ def check_uniform_options(percentages, radius):
                          f"got {percentages!r}") from None
     if not 1 <= len(ps) <= UNIFORM_MAX_T:
         raise ValueError(f"percentages must hold 1..{UNIFORM_MAX_T} values, got {len(ps)}")
-    out = []
-    for p in ps:
-        try:
-            pf = float(p)
-        except (TypeError, ValueError):
-            raise ValueError(f"percentages must be numbers, got {p!r}") from None
-        if isinstance(p, bool) or not (math.isfinite(pf) and 0.0 < pf <= 1.0):
-            raise ValueError(f"percentages must be in (0, 1], got {p!r}")
-        out.append(pf)
-    try:
-        rf = float(radius)
-    except (TypeError, ValueError):
-        raise ValueError(f"radius must be a number, got {radius!r}") from None
-    if isinstance(radius, bool) or not (math.isfinite(rf) and rf > 0.0):
-        raise ValueError(f"radius must be positive and finite, got {radius!r}")
-    return tuple(out), rf
+    ps = tuple(_finite_number(p, "percentages", lambda v: 0.0 < v <= 1.0, "in (0, 1]", number="numbers") for p in ps)
+    return ps, _finite_number(radius, "radius", lambda v: v > 0.0, "positive and finite")
 
 
 def _uniform_percent_array(percentages):
@@ -1060,15 +1045,7 @@ def uniform_loss(p: torch.Tensor, percentages=UNIFORM_PERCENTAGES, radius: float
     more than 16384 points, bad seeds, ``n_seeds`` outside ``1..N`` or a bad ``max_members``.  No CPU path: a CPU tensor raises
     ``FpsgHipError``."""
     percentages, radius = check_uniform_options(percentages, radius)
-    if not isinstance(p, torch.Tensor) or p.dim() != 3 or p.size(2) != 3:
-        raise ValueError(f"expected a [B,N,3] cloud tensor, got {tuple(getattr(p, 'shape', ()))}")
-    B, N, _ = p.shape
-    if B == 0:
-        raise ValueError(f"empty batches are not supported (got {tuple(p.shape)})")
-    if N < 2:
-        raise ValueError(f"uniform_loss needs at least 2 points per cloud, got {N}")
-    if N > UNIFORM_MAX_N:
-        raise ValueError(f"uniform_loss supports at most {UNIFORM_MAX_N} points per cloud, got {N}")
+    B, N = _check_cloud(p, "uniform_loss", UNIFORM_MAX_N, lambda N: N >= 2, "at least 2")
     if max_members is None:
         need = 2.0 * N * max(percentages)
         cap = next((c for c in UNIFORM_CAPS if c >= need), UNIFORM_CAPS[-1])
@@ -1122,13 +1099,10 @@ def swd_directions(L: int, device=None) -> torch.Tensor:
 def check_swd_options(n_proj, directions):
     """``(n_proj, directions)`` of the sliced Wasserstein loss as a Python int and str: ``n_proj`` an integer in
     1..1024, ``directions`` ``"random"`` or ``"fixed"`` (``ValueError`` naming the argument otherwise)."""
-    if isinstance(n_proj, bool) or not isinstance(n_proj, numbers.Integral):
-        raise ValueError(f"n_proj must be an integer in 1..{SWD_MAX_L}, got {n_proj!r}")
-    if not 1 <= int(n_proj) <= SWD_MAX_L:
-        raise ValueError(f"n_proj must be in 1..{SWD_MAX_L}, got {n_proj!r}")
+    n_proj = _integer_in(n_proj, "n_proj", 1, SWD_MAX_L)
     if not isinstance(directions, str) or directions not in SWD_DIRECTION_MODES:
         raise ValueError(f"directions must be one of {SWD_DIRECTION_MODES}, got {directions!r}")
-    return int(n_proj), directions
+    return n_proj, directions
 
 
 def _check_swd_inputs(p1, p2, directions):
@@ -1288,13 +1262,7 @@ SINKHORN_TRAIN_DIAMETER = 2.0 * math.sqrt(3.0)      # the diagonal of [-1, 1]^3:
 def check_sinkhorn_option(value, name: str) -> float:
     """``blur`` / ``diameter`` of ``sinkhorn_loss`` as a Python float: a finite number > 0 (``ValueError`` naming the
     option otherwise)."""
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        raise ValueError(f"{name} must be a number, got {value!r}") from None
-    if not (math.isfinite(v) and v > 0.0):
-        raise ValueError(f"{name} must be finite and positive, got {value!r}")
-    return v
+    return _finite_number(value, name, lambda v: v > 0.0, "finite and positive", allow_bool=True)
 
 
 class _SinkhornLoss(torch.autograd.Function):

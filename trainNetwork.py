@@ -31,6 +31,7 @@ from fpsg_amd import cli, winograd
 from fpsg_amd import dist as fdist
 from fpsg_amd.engine import TrainStep, build_model, build_optimizer, to_device
 from fpsg_amd.episodes import EpisodePrefetcher
+from fpsg_amd.few_shot import REGULARISERS
 from fpsg_amd.optim import check_max_grad_norm
 
 
@@ -156,7 +157,7 @@ def main(opt):
     for epoch in range(start_epoch, opt.epoch + 1):
         # every rank draws its own episodes; different seeds per (epoch, rank)
         torch.manual_seed(1000003 * epoch + rank)
-        sums = torch.zeros(5, dtype=torch.float64, device=device)
+        sums = torch.zeros(2 + len(REGULARISERS), dtype=torch.float64, device=device)    # query, support, the regularisers
         n_steps = max(1, opt.n_episode // eps_per_step)
         # exactly the episodes this rank uses (the worker must not draw one more from the global RNG: the
         # evaluation below and the next epoch's seed share it), drawn and uploaded behind the step
@@ -176,15 +177,12 @@ def main(opt):
                 for out in step(local, n_episodes_global=eps_per_step):
                     sums[0] += out["query_rec_loss"].sum() / n_query
                     sums[1] += out["support_rec_loss"].sum() / opt.n_shot
-                    if "repulsion_loss" in out:     # only with --repulsion_weight: the unweighted sum over the clouds
-                        sums[2] += out["repulsion_loss"].sum() / n_clouds
-                    if "expansion_loss" in out:     # only with --expansion_weight, likewise
-                        sums[3] += out["expansion_loss"].sum() / n_clouds
-                    if "uniform_loss" in out:       # only with --uniform_weight, likewise
-                        sums[4] += out["uniform_loss"].sum() / n_clouds
+                    for i, (_, key, _) in enumerate(REGULARISERS, 2):
+                        if key in out:      # only with the term's weight above 0: the unweighted sum over the clouds
+                            sums[i] += out[key].sum() / n_clouds
         finally:
             it.close()
-        q_sum, s_sum, r_sum, e_sum, u_sum = fdist.all_reduce_scalars(sums.tolist(), device)   # one host sync per epoch
+        q_sum, s_sum, *term_sums = fdist.all_reduce_scalars(sums.tolist(), device)    # one host sync per epoch
         done = n_steps * eps_per_step
         dt = time.perf_counter() - t0
         log(f"Training Results for Epoch -- {epoch} are: Query_rec: {q_sum / done}, "
@@ -195,12 +193,9 @@ def main(opt):
             cs = step.clip_stats()      # one host read per epoch; printed only, not part of the reference-format log
             print(f"  [grad norm: max {cs['max_norm_seen']:.6g}; clipped {cs['clipped']} of {cs['steps']} steps; "
                   f"{cs['nonfinite']} non-finite]")
-        if is_main and opt.repulsion_weight > 0:
-            print(f"  [repulsion: mean {r_sum / done:.6g} per cloud]")
-        if is_main and opt.expansion_weight > 0:
-            print(f"  [expansion: mean {e_sum / done:.6g} per cloud]")
-        if is_main and opt.uniform_weight > 0:
-            print(f"  [uniform: mean {u_sum / done:.6g} per cloud]")
+        for (name, _, weight), term_sum in zip(REGULARISERS, term_sums):
+            if is_main and getattr(opt, weight) > 0:
+                print(f"  [{name}: mean {term_sum / done:.6g} per cloud]")
         scheduler.step()
 
         evaluating = epoch % opt.eval_interval == 0 or epoch == opt.epoch
