@@ -10,10 +10,12 @@
 // as x = x1 + x2 + x3 with x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2) (round to nearest even; the
 // subtractions are exact, the three pieces carry 3 x 9 >= 24 significant bits, so the split is exact but for overflow of
 // bf16(x) beyond 3.39e38).  The six products of order <= 2^-18 -- a3 b1, a2 b2, a1 b3, a2 b1, a1 b2, a1 b1, bf16 x bf16 is
-// exact in fp32 -- go through v_mfma_f32_32x32x16_bf16 into ONE fp32 accumulator, smallest first inside a k-step; the
-// dropped a2 b3 + a3 b2 + a3 b3 are below 2^-26 of |a b|, a quarter of the fp32 product's own rounding.  The
+// exact in fp32 -- go through v_mfma_f32_32x32x16_bf16, smallest first inside a k-step: the five low-order ones into a
+// block that starts from zero, a1 b1 into the running sum, and the block joins the running sum by one fp32 addition
+// per k-step (split_step below, and why); the dropped a2 b3 + a3 b2 + a3 b3 are below 2^-26 of |a b|, a quarter of
+// the fp32 product's own rounding.  The
 // accumulation is fp32 with one rounding per MFMA (16 products) instead of one per product.  Measured error against
-// float64 products: tools/bench_gemm_split.py, profiles/r05/.
+// float64 products: tools/bench_gemm_split.py, profiles/r05/; the bias: profiles/vgg_stage/gemm_split_bias.txt.
 //
 // Data path.  The operands are split on the way from global memory into LDS (no bf16 planes in HBM): a thread loads 8
 // consecutive k of one row (A, and B when transB) or 8 rows of one column (B, N-contiguous: eight coalesced dword
@@ -93,6 +95,27 @@ typedef u32x4 frag_t;      // carried as four dwords through the control flow, c
 __device__ __forceinline__ frag_t lds_frag(const unsigned char* p) { return *reinterpret_cast<const u32x4*>(p); }
 __device__ __forceinline__ f32x16 mfma_bf16(frag_t a, frag_t b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// One 16-deep k-step of one 32 x 32 block: c + (the six products of b = b0 + b1 + b2 and a = a0 + a1 + a2 kept).
+// The five products of order 2^-8 and below are summed from ZERO, smallest first, and join the running sum through one
+// fp32 addition (round to nearest even).  Fed into the running sum one MFMA at a time -- the first form of this file --
+// each of them was aligned to the much larger accumulator inside the MFMA and lost its low bits there towards -inf,
+// whatever its sign: a coherent error of 1e-8 of the product's rms per element (a quarter of the element's rms error,
+// so no per-element bound saw it) that does not average out in sums over a row of the product -- the sums BatchNorm's
+// backward takes over a data gradient were 6x further from float64 than the library's
+// (tests/test_vgg_stage_gpu.py).  This form: the bias 7x smaller, row sums as close as the library's,
+// the element's rms error halved; 7-11 % more time per product (the 16 additions, and the extra block's registers
+// spill in the larger tiles).
+__device__ __forceinline__ f32x16 split_step(frag_t b0, frag_t b1, frag_t b2, frag_t a0, frag_t a1, frag_t a2, f32x16 c) {
+  f32x16 t = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  t = mfma_bf16(b0, a2, t);
+  t = mfma_bf16(b1, a1, t);
+  t = mfma_bf16(b2, a0, t);
+  t = mfma_bf16(b0, a1, t);
+  t = mfma_bf16(b1, a0, t);
+  c = mfma_bf16(b0, a0, c);
+  return c + t;
 }
 
 constexpr unsigned kOut = 0x7fffffffu;     // a lane offset beyond every buffer: the load returns 0, the store is dropped
@@ -392,12 +415,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void gemm_split_kernel(const Ge
 #pragma unroll
         for (int j = 0; j < TJ; ++j) {
           f32x16 c = acc[i][j];
-          c = mfma_bf16(fb[0][j], a[2], c);
-          c = mfma_bf16(fb[1][j], a[1], c);
-          c = mfma_bf16(fb[2][j], a[0], c);
-          c = mfma_bf16(fb[0][j], a[1], c);
-          c = mfma_bf16(fb[1][j], a[0], c);
-          c = mfma_bf16(fb[0][j], a[0], c);
+          c = split_step(fb[0][j], fb[1][j], fb[2][j], a[0], a[1], a[2], c);
           acc[i][j] = c;
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -448,12 +466,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void gemm_split_kernel(const Ge
 #pragma unroll
         for (int j = 0; j < TJ; ++j) {
           f32x16 c = acc[i][j];
-          c = mfma_bf16(fb[0][j], a[2], c);
-          c = mfma_bf16(fb[1][j], a[1], c);
-          c = mfma_bf16(fb[2][j], a[0], c);
-          c = mfma_bf16(fb[0][j], a[1], c);
-          c = mfma_bf16(fb[1][j], a[0], c);
-          c = mfma_bf16(fb[0][j], a[0], c);
+          c = split_step(fb[0][j], fb[1][j], fb[2][j], a[0], a[1], a[2], c);
           acc[i][j] = c;
         }
         if (i + 2 < TI) read_a(i + 2, fa[i & 1]);
@@ -662,12 +675,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void gemm_split_pa_kernel(const
 #pragma unroll
         for (int j = 0; j < TJ; ++j) {
           f32x16 c = acc[i][j];
-          c = mfma_bf16(fb[0][j], a[2], c);
-          c = mfma_bf16(fb[1][j], a[1], c);
-          c = mfma_bf16(fb[2][j], a[0], c);
-          c = mfma_bf16(fb[0][j], a[1], c);
-          c = mfma_bf16(fb[1][j], a[0], c);
-          c = mfma_bf16(fb[0][j], a[0], c);
+          c = split_step(fb[0][j], fb[1][j], fb[2][j], a[0], a[1], a[2], c);
           acc[i][j] = c;
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -912,12 +920,7 @@ __global__ __launch_bounds__(512, 2) void gemm_split_pnn_kernel(const PersistArg
           if (j + 1 < TJ) read_b(j + 1, fb[(j + 1) & 1]);
           const frag_t (&b)[3] = fb[j & 1];
           f32x16 c = acc[j];
-          c = mfma_bf16(b[0], fa[2], c);
-          c = mfma_bf16(b[1], fa[1], c);
-          c = mfma_bf16(b[2], fa[0], c);
-          c = mfma_bf16(b[0], fa[1], c);
-          c = mfma_bf16(b[1], fa[0], c);
-          c = mfma_bf16(b[0], fa[0], c);
+          c = split_step(b[0], b[1], b[2], fa[0], fa[1], fa[2], c);
           acc[j] = c;
         }
         // the split of B(s+1) in four parts behind the first column blocks' MFMAs (11 vector instructions each)
@@ -1163,12 +1166,7 @@ __global__ __launch_bounds__(512, MINW) void gemm_split_ws_kernel(const PersistA
 #pragma unroll
         for (int i = 0; i < TI; ++i) {
           f32x16 c = acc[i][j];
-          c = mfma_bf16(b[0], fa[i][2], c);
-          c = mfma_bf16(b[1], fa[i][1], c);
-          c = mfma_bf16(b[2], fa[i][0], c);
-          c = mfma_bf16(b[0], fa[i][1], c);
-          c = mfma_bf16(b[1], fa[i][0], c);
-          c = mfma_bf16(b[0], fa[i][0], c);
+          c = split_step(b[0], b[1], b[2], fa[i][0], fa[i][1], fa[i][2], c);
           acc[i][j] = c;
         }
       }

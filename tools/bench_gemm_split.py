@@ -5,6 +5,8 @@ time, interleaved in one process, and the error of both against a float64 produc
     python tools/bench_gemm_split.py [--variants -1,0,1] [--rounds 5] [--quick]
 
 VERDICT r4 item 1's gate: >= 1.6x at 256 -> 256 @56 and max / median error no worse than 1.5x the library's.
+Beside them: the mean signed error (``bias``, ``bias_t``) and the error of row sums (``row_sum_err``), which no per-element
+figure shows (profiles/vgg_stage/gemm_split_bias.txt).
 """
 from __future__ import annotations
 
@@ -31,10 +33,17 @@ def _time(fn, reps):
 
 
 def _errors(C, ref64):
-    """max and median |C - ref| over the reference's RMS (one scale per problem)."""
-    d = (C.double() - ref64).abs()
+    """max and median |C - ref| over the reference's RMS (one scale per problem); then what a per-element figure does not
+    show: the MEAN SIGNED error over that RMS (bias) with its t statistic mean / (std / sqrt(n)), and the rms error of the
+    sums over a row of the product over the rms of the exact row sums (what a consumer that sums a row sees: a coherent
+    bias does not average out there)."""
+    e = C.double() - ref64
+    d = e.abs()
     scale = ref64.pow(2).mean().sqrt()
-    return float(d.max() / scale), float(d.flatten()[:: max(1, d.numel() // 4_000_000)].median() / scale)
+    mean, std = e.mean(), e.std()
+    rows = e.sum(-1).pow(2).mean().sqrt() / ref64.sum(-1).pow(2).mean().sqrt()
+    return (float(d.max() / scale), float(d.flatten()[:: max(1, d.numel() // 4_000_000)].median() / scale),
+            float(mean / scale), float(mean / (std / e.numel() ** 0.5)), float(rows))
 
 
 def main():
@@ -102,7 +111,8 @@ def main():
                 ref = torch.bmm(gM[:nb].double(), V[:nb].double().transpose(1, 2))
             e_lib = _errors(lib_fn()[:nb], ref)
             row = {"shape": f"{C}->{K} @{H}", "leg": leg, "dims": f"{nb_} x [{K}x{C}].[{C}x{P}]" if leg == "fwd" else f"{nb_} x [{K}x{P}].[{P}x{C}]",
-                   "lib_err_max": e_lib[0], "lib_err_med": e_lib[1]}
+                   "lib_err_max": e_lib[0], "lib_err_med": e_lib[1], "lib_bias": e_lib[2], "lib_bias_t": round(e_lib[3], 1),
+                   "lib_row_sum_err": e_lib[4]}
             outs = {}
             for v in variants:
                 try:
@@ -129,7 +139,9 @@ def main():
                 row[f"v{v}"] = {"us": round(tv * 1e6, 1), "min_us": round(min(t_v[v]) * 1e6, 1), "speedup": round(tl / tv, 3),
                                 "fp32_equiv_TFLOPs": round(flop / tv / 1e12, 1), "bf16_TFLOPs": round(6 * flop / tv / 1e12, 1),
                                 "err_max": outs[v][0], "err_med": outs[v][1],
-                                "err_max_ratio": round(outs[v][0] / e_lib[0], 3), "err_med_ratio": round(outs[v][1] / e_lib[1], 3)}
+                                "err_max_ratio": round(outs[v][0] / e_lib[0], 3), "err_med_ratio": round(outs[v][1] / e_lib[1], 3),
+                                "bias": outs[v][2], "bias_t": round(outs[v][3], 1), "row_sum_err": outs[v][4],
+                                "row_sum_err_ratio": round(outs[v][4] / e_lib[4], 3)}
             print(json.dumps(row), flush=True)
         if packed:
             t = _time(lambda: pack_a(U, next(iter(packed))), args.reps)
