@@ -1,0 +1,331 @@
+// mesh_render.hip -- K27: orthographic, flat-shaded Phong views of a triangle mesh, for gfx950.  The definition is in
+// include/fpsg_hip.h (K27) and DESIGN.md: vertices snapped to 1/256 pixel, coverage by int64 edge functions with the
+// top-left rule, a 64-bit (depth, face) z-buffer filled with atomicMin, so the image does not depend on launch order.
+//
+// Structure, all views of a mesh in one launch of each kernel:
+//   * render_project_kernel: one (vertex, view) per thread -> camera-space (x, y, depth) and the snapped (X, Y);
+//   * render_raster_kernel: one (face, view) per thread; a bounding box of at most kSmallBox pixel centres is drawn by
+//     the thread, a larger one is appended to a list;
+//   * render_raster_large_kernel: a fixed grid strides over the list's entries, kChunks waves each, lanes over the
+//     bounding box's pixels;
+//   * render_shade_kernel: one output pixel per thread: its ssaa^2 samples shaded and composited over the background.
+#include "fpsg_common.h"
+
+namespace fpsg {
+namespace {
+
+typedef unsigned long long u64;
+typedef long long i64;
+
+constexpr int kSmallBox = 64;            // pixel centres a single thread still draws
+constexpr int kChunks = 16;              // waves that share one large triangle
+constexpr float kSnapLimit = 268435456.0f;   // 2^28: snapped coordinates stay below it, edge functions below 2^60
+constexpr u64 kEmpty = ~0ull;
+
+struct RenderParams {
+  float ka[3], kd[3], ks[3], light[3], bg[3];
+  int log2_shininess;
+};
+
+__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// float -> unsigned with the same order (negative depths included)
+__device__ __forceinline__ unsigned depth_key(float z) {
+  const unsigned b = __float_as_uint(z);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_depth(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+__device__ __forceinline__ int snap(float p) {
+  const float v = p * 256.0f;
+  return (int)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(v, -kSnapLimit), kSnapLimit));
+}
+
+__global__ __launch_bounds__(256) void render_project_kernel(const float* __restrict__ verts, int V,
+                                                             const float* __restrict__ views, float ortho_scale,
+                                                             int W, int H, v4f* __restrict__ cam,
+                                                             v4i* __restrict__ snapped) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= V) return;
+  const float* M = views + (size_t)blockIdx.y * 12;    // right, up, forward, position
+  const float dx = verts[(size_t)v * 3] - M[9], dy = verts[(size_t)v * 3 + 1] - M[10],
+              dz = verts[(size_t)v * 3 + 2] - M[11];
+  const float x = (dx * M[0] + dy * M[1]) + dz * M[2];
+  const float y = (dx * M[3] + dy * M[4]) + dz * M[5];
+  const float d = (dx * M[6] + dy * M[7]) + dz * M[8];
+  const float S = (float)(W > H ? W : H);
+  const float px = (x / ortho_scale) * S + 0.5f * (float)W;
+  const float py = 0.5f * (float)H - (y / ortho_scale) * S;
+  const bool ok = finite_f(px) && finite_f(py) && finite_f(d);
+  const size_t o = (size_t)blockIdx.y * V + v;
+  cam[o] = v4f{x, y, d, 0.0f};
+  snapped[o] = v4i{ok ? snap(px) : 0, ok ? snap(py) : 0, ok ? 1 : 0, 0};
+}
+
+// A face of one view ready to draw: winding normalised (A2 > 0), bounding box clipped to the image.
+struct Tri {
+  int x0, y0, x1, y1, x2, y2;
+  float z0, z1, z2;
+  i64 A2;
+  int b0, b1, b2;                        // 0 for an edge that owns its boundary (top or left), 1 otherwise
+  int i0, i1, j0, j1;                    // pixel range, inclusive; empty when i1 < i0 or j1 < j0
+};
+
+__device__ __forceinline__ int edge_bias(int ax, int ay, int bx, int by) {
+  const int dx = bx - ax, dy = by - ay;
+  return (dy < 0 || (dy == 0 && dx > 0)) ? 0 : 1;
+}
+
+__device__ __forceinline__ bool tri_setup(const int* __restrict__ faces, int f, int V, const v4f* __restrict__ cam,
+                                          const v4i* __restrict__ snapped, int W, int H, Tri& t) {
+  const int a = faces[(size_t)f * 3], b = faces[(size_t)f * 3 + 1], c = faces[(size_t)f * 3 + 2];
+  if ((unsigned)a >= (unsigned)V || (unsigned)b >= (unsigned)V || (unsigned)c >= (unsigned)V) return false;
+  const v4i sa = snapped[a], sb = snapped[b], sc = snapped[c];
+  if (!(sa.z & sb.z & sc.z)) return false;
+  t.x0 = sa.x; t.y0 = sa.y; t.z0 = cam[a].z;
+  t.x1 = sb.x; t.y1 = sb.y; t.z1 = cam[b].z;
+  t.x2 = sc.x; t.y2 = sc.y; t.z2 = cam[c].z;
+  t.A2 = (i64)(t.x1 - t.x0) * (i64)(t.y2 - t.y0) - (i64)(t.y1 - t.y0) * (i64)(t.x2 - t.x0);
+  if (t.A2 == 0) return false;
+  if (t.A2 < 0) {                                      // both windings are drawn
+    int s = t.x1; t.x1 = t.x2; t.x2 = s;
+    s = t.y1; t.y1 = t.y2; t.y2 = s;
+    const float z = t.z1; t.z1 = t.z2; t.z2 = z;
+    t.A2 = -t.A2;
+  }
+  t.b0 = edge_bias(t.x1, t.y1, t.x2, t.y2);
+  t.b1 = edge_bias(t.x2, t.y2, t.x0, t.y0);
+  t.b2 = edge_bias(t.x0, t.y0, t.x1, t.y1);
+  const int xmin = min(t.x0, min(t.x1, t.x2)), xmax = max(t.x0, max(t.x1, t.x2));
+  const int ymin = min(t.y0, min(t.y1, t.y2)), ymax = max(t.y0, max(t.y1, t.y2));
+  // pixel i has its centre at 256 i + 128 (>> on a negative int is an arithmetic shift: floor)
+  t.i0 = max((xmin + 127) >> 8, 0); t.i1 = min((xmax - 128) >> 8, W - 1);
+  t.j0 = max((ymin + 127) >> 8, 0); t.j1 = min((ymax - 128) >> 8, H - 1);
+  return t.i0 <= t.i1 && t.j0 <= t.j1;
+}
+
+__device__ __forceinline__ i64 edge_fn(int ax, int ay, int bx, int by, int px, int py) {
+  return (i64)(bx - ax) * (i64)(py - ay) - (i64)(by - ay) * (i64)(px - ax);
+}
+
+// i in [0, W), j in [0, H) by the clipped bounding box: the z-buffer index is in range
+__device__ __forceinline__ void tri_pixel(const Tri& t, int i, int j, unsigned face, u64* __restrict__ zrow0, int W) {
+  const int px = 256 * i + 128, py = 256 * j + 128;
+  const i64 E0 = edge_fn(t.x1, t.y1, t.x2, t.y2, px, py);
+  const i64 E1 = edge_fn(t.x2, t.y2, t.x0, t.y0, px, py);
+  const i64 E2 = edge_fn(t.x0, t.y0, t.x1, t.y1, px, py);
+  if (E0 < t.b0 || E1 < t.b1 || E2 < t.b2) return;
+  const float A = (float)t.A2;
+  const float l0 = (float)E0 / A, l1 = (float)E1 / A, l2 = (float)E2 / A;
+  const float z = (l0 * t.z0 + l1 * t.z1) + l2 * t.z2;
+  if (!finite_f(z)) return;
+  atomicMin(zrow0 + (size_t)j * W + i, ((u64)depth_key(z) << 32) | face);
+}
+
+__global__ __launch_bounds__(256) void render_raster_kernel(const int* __restrict__ faces, int F, int V,
+                                                            const v4f* __restrict__ cam,
+                                                            const v4i* __restrict__ snapped, int W, int H,
+                                                            u64* __restrict__ zbuf, unsigned* __restrict__ large,
+                                                            unsigned* __restrict__ n_large) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= F) return;
+  const int view = blockIdx.y;
+  Tri t;
+  if (!tri_setup(faces, f, V, cam + (size_t)view * V, snapped + (size_t)view * V, W, H, t)) return;
+  const int bw = t.i1 - t.i0 + 1, bh = t.j1 - t.j0 + 1;
+  if ((i64)bw * bh > kSmallBox) {                      // the list has room for every (face, view)
+    large[atomicAdd(n_large, 1u)] = (unsigned)view * (unsigned)F + (unsigned)f;
+    return;
+  }
+  u64* z0 = zbuf + (size_t)view * W * H;
+  for (int j = t.j0; j <= t.j1; ++j)
+    for (int i = t.i0; i <= t.i1; ++i) tri_pixel(t, i, j, (unsigned)f, z0, W);
+}
+
+__global__ __launch_bounds__(256) void render_raster_large_kernel(const int* __restrict__ faces, int F, int V,
+                                                                  const v4f* __restrict__ cam,
+                                                                  const v4i* __restrict__ snapped, int W, int H,
+                                                                  u64* __restrict__ zbuf,
+                                                                  const unsigned* __restrict__ large,
+                                                                  const unsigned* __restrict__ n_large,
+                                                                  unsigned n_views) {
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+  const unsigned n_waves = gridDim.x * 4u;
+  unsigned n = *n_large;
+  n = n < n_views * (unsigned)F ? n : n_views * (unsigned)F;   // the list's capacity
+  const u64 items = (u64)n * kChunks;
+  for (u64 w = wave; w < items; w += n_waves) {
+    const unsigned e = large[w / kChunks], chunk = (unsigned)(w % kChunks);
+    const unsigned view = e / (unsigned)F, f = e % (unsigned)F;
+    if (view >= n_views) continue;
+    Tri t;
+    if (!tri_setup(faces, (int)f, V, cam + (size_t)view * V, snapped + (size_t)view * V, W, H, t)) continue;
+    const unsigned bw = (unsigned)(t.i1 - t.i0 + 1), bh = (unsigned)(t.j1 - t.j0 + 1);
+    const unsigned npix = bw * bh;                     // W, H <= FPSG_RENDER_MAX_SIZE: below 2^32
+    u64* z0 = zbuf + (size_t)view * W * H;
+    for (unsigned p = chunk * 64u + lane; p < npix; p += 64u * kChunks)
+      tri_pixel(t, t.i0 + (int)(p % bw), t.j0 + (int)(p / bw), f, z0, W);
+  }
+}
+
+__global__ __launch_bounds__(256) void render_shade_kernel(const float* __restrict__ verts,
+                                                           const int* __restrict__ faces,
+                                                           const float* __restrict__ views,
+                                                           const u64* __restrict__ zbuf, int W, int H, int ssaa,
+                                                           RenderParams P, const unsigned char* __restrict__ bg_img,
+                                                           unsigned char* __restrict__ image,
+                                                           float* __restrict__ radiance, int* __restrict__ face_id,
+                                                           float* __restrict__ depth) {
+  const int ow = W / ssaa, oh = H / ssaa;
+  const int ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (ox >= ow || oy >= oh) return;
+  const int view = blockIdx.z;
+  const float* M = views + (size_t)view * 12;
+  const u64* z0 = zbuf + (size_t)view * W * H;
+  float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f;
+  int covered = 0;
+  for (int sy = 0; sy < ssaa; ++sy) {
+    for (int sx = 0; sx < ssaa; ++sx) {
+      const int i = ox * ssaa + sx, j = oy * ssaa + sy;
+      const size_t pix = (size_t)j * W + i;
+      const u64 key = z0[pix];
+      const bool hit = key != kEmpty;
+      if (face_id) face_id[(size_t)view * W * H + pix] = hit ? (int)(unsigned)key : -1;
+      if (depth) depth[(size_t)view * W * H + pix] = hit ? key_depth((unsigned)(key >> 32)) : __builtin_inff();
+      if (!hit) continue;
+      const unsigned f = (unsigned)key;                // written by the rasteriser: a face with indices in range
+      const float* a = verts + (size_t)faces[(size_t)f * 3] * 3;
+      const float* b = verts + (size_t)faces[(size_t)f * 3 + 1] * 3;
+      const float* c = verts + (size_t)faces[(size_t)f * 3 + 2] * 3;
+      // world-space edges turned into the camera frame: no cancellation against the camera's distance
+      const float w1x = b[0] - a[0], w1y = b[1] - a[1], w1z = b[2] - a[2];
+      const float w2x = c[0] - a[0], w2y = c[1] - a[1], w2z = c[2] - a[2];
+      const float e1x = (w1x * M[0] + w1y * M[1]) + w1z * M[2], e1y = (w1x * M[3] + w1y * M[4]) + w1z * M[5],
+                  e1z = (w1x * M[6] + w1y * M[7]) + w1z * M[8];
+      const float e2x = (w2x * M[0] + w2y * M[1]) + w2z * M[2], e2y = (w2x * M[3] + w2y * M[4]) + w2z * M[5],
+                  e2z = (w2x * M[6] + w2y * M[7]) + w2z * M[8];
+      float nx = e1y * e2z - e1z * e2y;
+      float ny = e1z * e2x - e1x * e2z;
+      float nz = e1x * e2y - e1y * e2x;
+      const float len = __builtin_sqrtf((nx * nx + ny * ny) + nz * nz);
+      if (len > 0.0f && finite_f(len)) { nx = nx / len; ny = ny / len; nz = nz / len; }
+      else { nx = 0.0f; ny = 0.0f; nz = -1.0f; }
+      if (nz > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }   // two-sided: towards the camera, which looks along +z
+      const float ndl = (nx * P.light[0] + ny * P.light[1]) + nz * P.light[2];
+      const float diff = __builtin_fmaxf(ndl, 0.0f);
+      // r = 2 (n.l) n - l, v = (0, 0, -1): r.v = l_z - 2 (n.l) n_z
+      float spec = ndl > 0.0f ? __builtin_fmaxf(P.light[2] - (2.0f * ndl) * nz, 0.0f) : 0.0f;
+      for (int k = 0; k < P.log2_shininess; ++k) spec = spec * spec;
+      acc0 += (P.ka[0] + P.kd[0] * diff) + P.ks[0] * spec;
+      acc1 += (P.ka[1] + P.kd[1] * diff) + P.ks[1] * spec;
+      acc2 += (P.ka[2] + P.kd[2] * diff) + P.ks[2] * spec;
+      ++covered;
+    }
+  }
+  const float inv = 1.0f / (float)(ssaa * ssaa);
+  const float rest = 1.0f - (float)covered * inv;
+  const size_t o = (((size_t)view * oh + oy) * ow + ox) * 3;
+  float bg0 = P.bg[0], bg1 = P.bg[1], bg2 = P.bg[2];
+  if (bg_img) {
+    const unsigned char* q = bg_img + ((size_t)oy * ow + ox) * 3;
+    bg0 = (float)q[0] / 255.0f; bg1 = (float)q[1] / 255.0f; bg2 = (float)q[2] / 255.0f;
+  }
+  const float r0 = acc0 * inv + bg0 * rest, r1 = acc1 * inv + bg1 * rest, r2 = acc2 * inv + bg2 * rest;
+  if (radiance) { radiance[o] = r0; radiance[o + 1] = r1; radiance[o + 2] = r2; }
+  if (image) {
+    image[o] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r0, 0.0f), 1.0f) * 255.0f);
+    image[o + 1] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r1, 0.0f), 1.0f) * 255.0f);
+    image[o + 2] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r2, 0.0f), 1.0f) * 255.0f);
+  }
+}
+
+struct RenderWs {
+  size_t cam, snapped, zbuf, list, counter, total;
+};
+
+inline RenderWs render_ws(int V, int F, int NV, int W, int H) {
+  RenderWs w;
+  size_t o = 0;
+  w.cam = o; o += (size_t)NV * V * 16;
+  w.snapped = o; o += (size_t)NV * V * 16;
+  w.zbuf = o; o += (size_t)NV * W * H * 8;
+  w.list = o; o += (((size_t)NV * F * 4) + 15) & ~(size_t)15;
+  w.counter = o; o += 16;
+  w.total = o;
+  return w;
+}
+
+inline bool render_shape_ok(int V, int F, int NV, int W, int H, int ssaa) {
+  return V > 0 && F > 0 && NV > 0 && W > 0 && H > 0 && ssaa >= 1 && ssaa <= FPSG_RENDER_MAX_SSAA && W % ssaa == 0 &&
+         H % ssaa == 0;
+}
+inline bool render_limit_ok(int F, int NV, int W, int H) {
+  return W <= FPSG_RENDER_MAX_SIZE && H <= FPSG_RENDER_MAX_SIZE && NV <= FPSG_RENDER_MAX_VIEWS &&
+         (uint64_t)F * (uint64_t)NV <= 0x7fffffffull;
+}
+
+}  // namespace
+}  // namespace fpsg
+
+extern "C" size_t fpsg_mesh_render_workspace_bytes(int V, int F, int n_views, int W, int H) {
+  using namespace fpsg;
+  if (!render_shape_ok(V, F, n_views, W, H, 1) || !render_limit_ok(F, n_views, W, H)) return 0;
+  return render_ws(V, F, n_views, W, H).total;
+}
+
+extern "C" int fpsg_mesh_render(const float* verts, int V, const int32_t* faces, int F, const float* views,
+                                int n_views, int W, int H, int ssaa, float ortho_scale, const float* params,
+                                int log2_shininess, const uint8_t* bg_image, uint8_t* image, float* radiance,
+                                int32_t* face_id, float* depth, void* ws, size_t ws_bytes, fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_REQUIRE(render_shape_ok(V, F, n_views, W, H, ssaa), FPSG_E_SHAPE,
+               "fpsg_mesh_render: V,F,n_views,W,H must be positive, ssaa from 1 to %d and a divisor of W and H "
+               "(got %d,%d,%d,%d,%d,%d)", FPSG_RENDER_MAX_SSAA, V, F, n_views, W, H, ssaa);
+  FPSG_REQUIRE(ortho_scale > 0.0f && ortho_scale <= 3.0e38f, FPSG_E_SHAPE,
+               "fpsg_mesh_render: ortho_scale must be positive and finite");
+  FPSG_REQUIRE(log2_shininess >= 0 && log2_shininess <= FPSG_RENDER_MAX_LOG2_SHININESS, FPSG_E_SHAPE,
+               "fpsg_mesh_render: log2_shininess must be from 0 to %d (got %d)", FPSG_RENDER_MAX_LOG2_SHININESS,
+               log2_shininess);
+  FPSG_REQUIRE(render_limit_ok(F, n_views, W, H), FPSG_E_LIMIT,
+               "fpsg_mesh_render: W,H <= %d, n_views <= %d and F n_views < 2^31 are supported (got %d,%d,%d,%d)",
+               FPSG_RENDER_MAX_SIZE, FPSG_RENDER_MAX_VIEWS, W, H, n_views, F);
+  FPSG_REQUIRE_PTR(verts); FPSG_REQUIRE_PTR(faces); FPSG_REQUIRE_PTR(views); FPSG_REQUIRE_PTR(ws);
+  FPSG_REQUIRE(params != nullptr, FPSG_E_NULL, "fpsg_mesh_render: null pointer 'params'");
+  FPSG_REQUIRE(image || radiance || face_id || depth, FPSG_E_NULL, "fpsg_mesh_render: no output requested");
+  FPSG_REQUIRE(!misaligned4(radiance) && !misaligned4(face_id) && !misaligned4(depth), FPSG_E_ALIGN,
+               "fpsg_mesh_render: an output is not 4-byte aligned");
+  FPSG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15u) == 0, FPSG_E_ALIGN, "fpsg_mesh_render: 'ws' must be 16-byte aligned");
+  const RenderWs L = render_ws(V, F, n_views, W, H);
+  FPSG_REQUIRE(ws_bytes >= L.total, FPSG_E_SHAPE, "fpsg_mesh_render: workspace of %zu bytes, %zu needed", ws_bytes,
+               L.total);
+  RenderParams P;
+  for (int k = 0; k < 3; ++k) {
+    P.ka[k] = params[k]; P.kd[k] = params[3 + k]; P.ks[k] = params[6 + k];
+    P.light[k] = params[9 + k]; P.bg[k] = params[12 + k];
+  }
+  P.log2_shininess = log2_shininess;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  v4f* cam = reinterpret_cast<v4f*>(base + L.cam);
+  v4i* snapped = reinterpret_cast<v4i*>(base + L.snapped);
+  u64* zbuf = reinterpret_cast<u64*>(base + L.zbuf);
+  unsigned* list = reinterpret_cast<unsigned*>(base + L.list);
+  unsigned* counter = reinterpret_cast<unsigned*>(base + L.counter);
+  hipError_t e = hipMemsetAsync(zbuf, 0xff, (size_t)n_views * W * H * 8, st);
+  if (e == hipSuccess) e = hipMemsetAsync(counter, 0, 16, st);
+  if (e != hipSuccess) { set_error("fpsg_mesh_render: %s", hipGetErrorString(e)); return (int)e; }
+  hipLaunchKernelGGL(render_project_kernel, dim3((unsigned)((V + 255) / 256), (unsigned)n_views), dim3(256), 0, st,
+                     verts, V, views, ortho_scale, W, H, cam, snapped);
+  hipLaunchKernelGGL(render_raster_kernel, dim3((unsigned)((F + 255) / 256), (unsigned)n_views), dim3(256), 0, st,
+                     faces, F, V, cam, snapped, W, H, zbuf, list, counter);
+  // a fixed grid strides over the list, whose length only the device knows
+  hipLaunchKernelGGL(render_raster_large_kernel, dim3(1024), dim3(256), 0, st, faces, F, V, cam, snapped, W, H, zbuf,
+                     list, counter, (unsigned)n_views);
+  const int ow = W / ssaa, oh = H / ssaa;
+  hipLaunchKernelGGL(render_shade_kernel, dim3((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4), (unsigned)n_views),
+                     dim3(256), 0, st, verts, faces, views, zbuf, W, H, ssaa, P, bg_image, image, radiance, face_id, depth);
+  return launch_status("fpsg_mesh_render");
+}

@@ -1,0 +1,443 @@
+"""Datasets from meshes: mesh files in, sampled clouds (K26) and rendered views (K27) out, plus the list files that
+``fpsg_amd.datasets`` reads.  The definitions of both kernels are in ``include/fpsg_hip.h``.
+
+The host part (``load_mesh``, ``normalize_mesh``, ``write_ply_points``, ``camera_views``, ``write_modelnet_lists``)
+needs no GPU.  ``sample_surface`` and ``render_views`` run on the GPU only: a CPU tensor raises ``FpsgHipError``.
+"""
+from __future__ import annotations
+
+import ctypes
+import dataclasses
+import math
+import os
+import re
+
+import numpy as np
+import torch
+
+from . import _hip
+
+MESH_MAX_FACES = 1 << 24        # FPSG_MESH_MAX_FACES (include/fpsg_hip.h)
+RENDER_MAX_SIZE = 8192          # FPSG_RENDER_MAX_SIZE
+RENDER_MAX_SSAA = 4             # FPSG_RENDER_MAX_SSAA
+
+# the reference's TRAIN_SET_DIC['modelnet'] / TEST_SET_DIC['modelnet'] (generate_dataset.py): base and novel classes
+MODELNET_TRAIN_CLASSES = ("airplane", "bathtub", "bed", "chair", "desk", "dresser", "monitor", "sofa", "table",
+                          "toilet")
+MODELNET_TEST_CLASSES = ("cup", "keyboard", "door", "laptop", "bowl")
+
+
+# ------------------------------------------------------------------------------------------ files
+def _lines(path: str):
+    """-> (stripped non-empty lines without comments as a numpy array of str, their 1-based line numbers)."""
+    with open(path, "r", errors="replace") as f:
+        text = f.read()
+    text = re.sub(r"#[^\n]*", "", text)
+    text = re.sub(r"[ \t\r\f\v]+", " ", text)
+    arr = np.char.strip(np.array(text.split("\n"), dtype=np.str_))
+    keep = arr != ""
+    return arr[keep], np.nonzero(keep)[0] + 1
+
+
+def _numbers(lines, dtype, path, what):
+    if len(lines) == 0:
+        return np.zeros((0,), dtype)
+    try:
+        return np.array(" ".join(lines.tolist()).split(), dtype=np.float64).astype(dtype)
+    except ValueError as e:
+        raise ValueError(f"{path}: bad {what}: {e}") from None
+
+
+def _fan(flat, starts, counts, lineno):
+    """Polygons ``flat[starts[k] : starts[k] + counts[k]]`` -> fan triangles [T,3] and each triangle's line number."""
+    ok = counts >= 3
+    starts, counts, lineno = starts[ok], counts[ok], lineno[ok]
+    per = counts - 2
+    total = int(per.sum())
+    if total == 0:
+        return np.zeros((0, 3), np.int64), np.zeros((0,), np.int64)
+    owner = np.repeat(np.arange(len(per)), per)
+    k = np.arange(total) - np.repeat(np.cumsum(per) - per, per)           # 0 .. per-1 inside each polygon
+    s = starts[owner]
+    return np.stack([flat[s], flat[s + 1 + k], flat[s + 2 + k]], axis=1), lineno[owner]
+
+
+def _check_range(tri, tri_line, n_verts, path):
+    bad = (tri < 0) | (tri >= n_verts)
+    if bad.any():
+        row = int(np.nonzero(bad.any(axis=1))[0][0])
+        raise ValueError(f"{path}, line {int(tri_line[row])}: face index out of range "
+                         f"({tri[row].tolist()} with {n_verts} vertices)")
+
+
+def _load_off(path):
+    lines, lineno = _lines(path)
+    if len(lines) == 0 or not lines[0].upper().startswith("OFF"):
+        raise ValueError(f"{path}: not an OFF file")
+    rest = lines[0][3:].strip()          # 'OFF123 456 0': the counts fused to the keyword, as the reference tolerates
+    body = 1
+    if not rest:
+        if len(lines) < 2:
+            raise ValueError(f"{path}: no counts")
+        rest, body = lines[1], 2
+    try:
+        nv, nf = (int(t) for t in rest.split()[:2])
+    except ValueError:
+        raise ValueError(f"{path}, line {int(lineno[body - 1])}: bad counts {rest!r}") from None
+    if nv < 0 or nf < 0 or len(lines) < body + nv + nf:
+        raise ValueError(f"{path}: {nv} vertices and {nf} faces announced, {len(lines) - body} lines present")
+    verts = _numbers(lines[body:body + nv], np.float32, path, "vertex")
+    if verts.size != nv * 3:
+        raise ValueError(f"{path}: vertex lines do not hold 3 numbers each")
+    flines, fno = lines[body + nv:body + nv + nf], lineno[body + nv:body + nv + nf]
+    flat = _numbers(flines, np.int64, path, "face")
+    ntok = np.char.count(flines, " ") + 1 if nf else np.zeros((0,), np.int64)
+    starts = np.cumsum(ntok) - ntok
+    counts = flat[starts] if nf else flat[:0]
+    short = counts + 1 > ntok            # colours may follow the indices, fewer tokens than announced may not
+    if short.any():
+        raise ValueError(f"{path}, line {int(fno[np.nonzero(short)[0][0]])}: face with fewer indices than its count")
+    tri, tri_line = _fan(flat, starts + 1, counts, fno)
+    _check_range(tri, tri_line, nv, path)
+    return verts.reshape(nv, 3), tri.astype(np.int32)
+
+
+def _load_obj(path):
+    lines, lineno = _lines(path)
+    is_v = np.char.startswith(lines, "v ")
+    is_f = np.char.startswith(lines, "f ")
+    vlines = np.char.partition(lines[is_v], " ")[:, 2] if is_v.any() else lines[:0]
+    vals = _numbers(vlines, np.float32, path, "vertex")
+    nv = int(is_v.sum())
+    per = np.char.count(vlines, " ") + 1 if nv else np.zeros((0,), np.int64)
+    if nv and (per < 3).any():
+        raise ValueError(f"{path}: a 'v' record with fewer than 3 numbers")
+    if nv and not (per == per[0]).all():
+        raise ValueError(f"{path}: 'v' records of different lengths")
+    verts = vals.reshape(nv, -1)[:, :3] if nv else np.zeros((0, 3), np.float32)
+    flines, fno = lines[is_f], lineno[is_f]
+    if len(flines) == 0:
+        return np.ascontiguousarray(verts), np.zeros((0, 3), np.int32)
+    ftext = np.char.partition(flines, " ")[:, 2]
+    ntok = np.char.count(ftext, " ") + 1
+    tokens = np.array(" ".join(ftext.tolist()).split(), dtype=np.str_)
+    try:
+        flat = np.char.partition(tokens, "/")[:, 0].astype(np.int64)      # v, v/vt, v/vt/vn, v//vn
+    except ValueError as e:
+        raise ValueError(f"{path}: bad face record: {e}") from None
+    # a negative index counts back from the vertices defined so far; a positive one is 1-based; 0 is no vertex
+    seen = np.cumsum(is_v)[is_f]
+    seen_tok = np.repeat(seen, ntok)
+    flat = np.where(flat < 0, flat + seen_tok, np.where(flat > 0, flat - 1, -1))
+    starts = np.cumsum(ntok) - ntok
+    tri, tri_line = _fan(flat, starts, ntok, fno)
+    _check_range(tri, tri_line, nv, path)
+    return np.ascontiguousarray(verts), tri.astype(np.int32)
+
+
+def load_mesh(path: str):
+    """``.off`` or ``.obj`` -> ``(verts float32 [V,3], faces int32 [F,3])``, polygons fan-triangulated.
+
+    OFF: comments (``#``) and blank lines anywhere, the counts on the keyword's line (``OFF 8 6 0``), fused to it
+    (``OFF8 6 0``, which ModelNet40 has and the reference's ``off2ply`` tolerates) or on the next; colours behind a
+    face's indices are ignored.  OBJ: ``v`` and ``f`` records only, ``f`` with ``/vt/vn`` parts and negative
+    (relative) indices; everything else is ignored.  A face index outside the vertices raises ``ValueError`` with the
+    file and the line.  The text is parsed by numpy over the split file, not line by line."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".off":
+        return _load_off(path)
+    if ext == ".obj":
+        return _load_obj(path)
+    raise ValueError(f"{path}: unsupported mesh format {ext!r} (.off and .obj are read)")
+
+
+def normalize_mesh(verts, mode: str = "bbox") -> np.ndarray:
+    """``"bbox"``: the bounding box's centre to the origin and its largest extent to 1 (what ``phong.py``'s
+    ``center_model`` / ``normalize_model`` did for ModelNet); ``"none"``: unchanged (ShapeNet's ``model_normalized.obj``).
+    -> float32 ``[V,3]``.  A mesh without extent is only centred."""
+    v = np.asarray(verts, dtype=np.float64)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError(f"expected [V,3] vertices, got {v.shape}")
+    if mode == "none" or v.shape[0] == 0:
+        return np.ascontiguousarray(v, dtype=np.float32)
+    if mode != "bbox":
+        raise ValueError(f"mode must be 'bbox' or 'none', got {mode!r}")
+    lo, hi = v.min(axis=0), v.max(axis=0)
+    extent = float((hi - lo).max())
+    v = v - (lo + hi) / 2.0
+    if extent > 0 and math.isfinite(extent):
+        v = v / extent
+    return np.ascontiguousarray(v, dtype=np.float32)
+
+
+def write_ply_points(path: str, pts) -> None:
+    """The ASCII vertex-only PLY that ``datasets.ply_reader`` reads back; ``%.9g`` keeps every float32 bit."""
+    p = np.asarray(pts.detach().cpu() if isinstance(pts, torch.Tensor) else pts, dtype=np.float32)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError(f"expected [N,3] points, got {p.shape}")
+    head = ("ply\nformat ascii 1.0\n"
+            f"element vertex {p.shape[0]}\nproperty float x\nproperty float y\nproperty float z\nend_header\n")
+    body = "\n".join("%.9g %.9g %.9g" % (x, y, z) for x, y, z in p.tolist())
+    with open(path, "w") as f:
+        f.write(head + body + "\n")
+
+
+# -------------------------------------------------------------------------------------------- K26
+def _mesh_tensors(verts, faces):
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.size(1) != 3 or verts.size(0) < 1:
+        raise ValueError(f"expected [V,3] vertices, got {tuple(getattr(verts, 'shape', ()))}")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.size(1) != 3 or faces.size(0) < 1:
+        raise ValueError(f"expected [F,3] faces, got {tuple(getattr(faces, 'shape', ()))}")
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"faces must be int32 or int64, got {faces.dtype}")
+    if faces.size(0) > MESH_MAX_FACES:
+        raise ValueError(f"meshes of more than {MESH_MAX_FACES} faces are not supported (got {faces.size(0)})")
+    verts = verts.detach()
+    _hip.dev_tensor(verts, torch.float32, "verts")
+    if faces.device != verts.device:
+        raise ValueError(f"faces are on {faces.device}, verts on {verts.device}")
+    lo, hi = int(faces.min()), int(faces.max())
+    if lo < 0 or hi >= verts.size(0):
+        raise ValueError(f"face indices must be in [0, {verts.size(0)}), got {lo}..{hi}")
+    return verts, faces.to(torch.int32).contiguous()
+
+
+def surface_cdf(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """The integer CDF of K26: ``[F]`` int64 (the kernel's uint64, below 2^57), ``cdf[-1]`` the total weight."""
+    verts, faces = _mesh_tensors(verts, faces)
+    return _cdf(verts, faces)
+
+
+def _cdf(verts, faces):
+    V, F = verts.size(0), faces.size(0)
+    lib = _hip.load()
+    cdf = torch.empty((F,), dtype=torch.int64, device=verts.device)
+    ws_bytes = lib.fpsg_mesh_cdf_workspace_bytes(V, F)
+    ws = torch.empty((ws_bytes // 8 + 1,), dtype=torch.int64, device=verts.device)
+    with torch.cuda.device(verts.device):
+        rc = lib.fpsg_mesh_cdf(_hip.ptr(verts), V, _hip.ptr(faces), F, _hip.ptr(cdf), _hip.ptr(ws), ws.numel() * 8,
+                               _hip.stream_of(verts))
+    _hip.check(rc, "fpsg_mesh_cdf")
+    return cdf
+
+
+def sample_surface(verts: torch.Tensor, faces: torch.Tensor, n: int, *, generator=None, u=None, oversample: int = 1):
+    """``n`` points on the surface of the mesh, area-weighted (K26) -> ``(points [n,3] float32, face_idx [n] int64)``.
+
+    ``u`` ``[n * oversample, 3]`` float32 in [0, 1) picks the samples: column 0 the face through the integer CDF,
+    columns 1 and 2 the point in it.  When it is not given it is drawn with ``torch.rand`` from ``generator`` (on the
+    generator's device, the CPU without one).  The kernel is a pure function of ``(verts, faces, u)``, bitwise the same
+    on every run.  With ``oversample > 1`` the ``n * oversample`` samples are thinned to ``n`` well-spread ones by
+    farthest point sampling (K16, start index 0), the role of PCL's ``-leaf_size``.
+
+    ``ValueError`` for bad shapes or face indices outside the vertices; ``FpsgHipError`` for CPU tensors and for a
+    mesh without area (every face degenerate): that one is found on the device, and no sampling kernel is launched."""
+    if isinstance(n, bool) or int(n) != n or int(n) < 1:
+        raise ValueError(f"n must be a positive integer, got {n}")
+    if isinstance(oversample, bool) or int(oversample) != oversample or int(oversample) < 1:
+        raise ValueError(f"oversample must be a positive integer, got {oversample}")
+    n, oversample = int(n), int(oversample)
+    m = n * oversample
+    verts, faces = _mesh_tensors(verts, faces)
+    dev = verts.device
+    if u is None:
+        gdev = generator.device if generator is not None else torch.device("cpu")
+        u = torch.rand((m, 3), generator=generator, device=gdev, dtype=torch.float32)
+    if not isinstance(u, torch.Tensor) or tuple(u.shape) != (m, 3):
+        raise ValueError(f"u must have shape ({m}, 3), got {tuple(getattr(u, 'shape', ()))}")
+    u = u.detach().to(dev)
+    _hip.dev_tensor(u, torch.float32, "u")
+    V, F = verts.size(0), faces.size(0)
+    cdf = _cdf(verts, faces)
+    total = int(cdf[-1])                                   # one read-back: a mesh without area is refused on the host
+    points = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    face_idx = torch.empty((m,), dtype=torch.int32, device=dev)
+    lib = _hip.load()
+    with torch.cuda.device(dev):
+        rc = lib.fpsg_mesh_sample(_hip.ptr(verts), V, _hip.ptr(faces), F, _hip.ptr(cdf), total, _hip.ptr(u), m,
+                                  _hip.ptr(points), _hip.ptr(face_idx), _hip.stream_of(verts))
+    _hip.check(rc, "fpsg_mesh_sample")
+    face_idx = face_idx.long()
+    if oversample > 1:
+        from .sampling import farthest_point_sample
+        keep = farthest_point_sample(points.unsqueeze(0), n)[0]
+        points, face_idx = points[keep].contiguous(), face_idx[keep].contiguous()
+    return points, face_idx
+
+
+# -------------------------------------------------------------------------------------------- K27
+@dataclasses.dataclass(frozen=True)
+class PhongMaterial:
+    """Flat Phong shading of K27: ``ambient * color + diffuse * color * max(n.l, 0) + specular * max(r.v, 0)^shininess``
+    with one directional light fixed in the camera frame (x right, y up, z along the view; ``light`` points from the
+    surface towards the light and is normalised here).  The defaults are a light grey object lit from the upper left
+    behind the camera; their largest radiance is 0.8 (0.15 + 0.75) + 0.25 = 0.97, so nothing clips.  ``shininess`` is a
+    power of two (the kernel squares log2(shininess) times, no ``powf``)."""
+    color: tuple = (0.8, 0.8, 0.8)
+    ambient: float = 0.15
+    diffuse: float = 0.75
+    specular: float = 0.25
+    shininess: int = 32
+    light: tuple = (-0.35, 0.5, -0.8)
+
+    def log2_shininess(self) -> int:
+        s = int(self.shininess)
+        if s != self.shininess or s < 1 or s & (s - 1) or s > 1024:
+            raise ValueError(f"shininess must be a power of two from 1 to 1024, got {self.shininess}")
+        return s.bit_length() - 1
+
+    def params(self, background=(1.0, 1.0, 1.0)) -> np.ndarray:
+        """The 15 floats of ``fpsg_mesh_render``: ka[3], kd[3], ks[3], l[3], bg[3]; products formed in float64."""
+        c = np.asarray(self.color, dtype=np.float64).reshape(3)
+        l = np.asarray(self.light, dtype=np.float64).reshape(3)
+        norm = float(np.sqrt((l * l).sum()))
+        if not norm > 0:
+            raise ValueError("light must not be the zero vector")
+        return np.concatenate([self.ambient * c, self.diffuse * c, np.full(3, float(self.specular)), l / norm,
+                               np.asarray(background, dtype=np.float64).reshape(3)]).astype(np.float32)
+
+
+def camera_views(elevations_deg=60.0, azimuths_deg=range(0, 360, 30), radius: float = 3.0, up: str = "z") -> np.ndarray:
+    """View matrices ``[n_views, 12]`` float32 (right, up, forward, position), one per (elevation, azimuth), elevation
+    outermost.  ``phong.py``'s camera: at ``c = radius (sin t cos p, sin t sin p, cos t)``, ``t`` measured from the pole,
+    looking at the origin (its TRACK_TO constraint): forward ``f = -c / |c|``, right ``normalize(f x up)`` (``+x`` when
+    ``f`` is parallel to ``up``: the top view ``t = 0``), camera up ``right x f``.  ``up="y"``: the same camera for a
+    y-up mesh, the axes permuted cyclically (z -> y, y -> x, x -> z).  Built in float64, rounded once."""
+    if up not in ("z", "y"):
+        raise ValueError(f"up must be 'z' or 'y', got {up!r}")
+    if not radius > 0:
+        raise ValueError(f"radius must be positive, got {radius}")
+    els = np.atleast_1d(np.asarray(elevations_deg, dtype=np.float64))
+    azs = np.atleast_1d(np.asarray(list(azimuths_deg) if not np.isscalar(azimuths_deg) else azimuths_deg,
+                                   dtype=np.float64))
+    pole = np.array([0.0, 0.0, 1.0])
+    rows = []
+    for t in np.deg2rad(els):
+        for p in np.deg2rad(azs):
+            c = radius * np.array([np.sin(t) * np.cos(p), np.sin(t) * np.sin(p), np.cos(t)])
+            f = -c / np.linalg.norm(c)
+            r = np.cross(f, pole)
+            r = r / np.linalg.norm(r) if np.linalg.norm(r) > 1e-12 else np.array([1.0, 0.0, 0.0])
+            cu = np.cross(r, f)
+            vecs = [r, cu, f, c]
+            if up == "y":
+                vecs = [np.array([v[1], v[2], v[0]]) for v in vecs]
+            rows.append(np.concatenate(vecs))
+    return np.asarray(rows, dtype=np.float64).astype(np.float32)
+
+
+def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevations_deg=60.0,
+                 azimuths_deg=range(0, 360, 30), radius: float = 3.0, ortho_scale: float = 2.0, up: str = "z",
+                 ssaa: int = 2, background=(1.0, 1.0, 1.0), material: PhongMaterial = PhongMaterial(),
+                 return_buffers: bool = False, views=None):
+    """Orthographic, flat-shaded Phong views of a mesh (K27) -> uint8 ``[n_views, H, W, 3]`` on the mesh's device.
+
+    ``size``: an int (square) or ``(H, W)``; the mesh is rasterised at ``size * ssaa`` and every output pixel is the
+    mean of its ``ssaa^2`` samples over ``background``, an ``(r, g, b)`` in [0, 1] or a uint8 image ``[H, W, 3]`` (array
+    or tensor) shared by the views.  The camera is ``camera_views(elevations_deg, azimuths_deg, radius, up)`` unless
+    ``views [n,12]`` gives the matrices; ``ortho_scale`` world units span the image's larger side.  Both windings of
+    a face are drawn and lit (ModelNet's are inconsistent).  With ``return_buffers`` also a dict: ``face_id`` int32 and
+    ``depth`` float32 ``[n_views, H ssaa, W ssaa]`` (-1 / +inf where empty) and ``radiance`` float32 ``[n_views,H,W,3]``,
+    of which the image is ``rint(clamp(radiance, 0, 1) * 255)``.  Bitwise the same on every run.
+
+    ``ValueError`` for bad shapes and options, ``FpsgHipError`` for CPU tensors."""
+    H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+    if isinstance(ssaa, bool) or int(ssaa) != ssaa or not 1 <= int(ssaa) <= RENDER_MAX_SSAA:
+        raise ValueError(f"ssaa must be an integer from 1 to {RENDER_MAX_SSAA}, got {ssaa}")
+    ssaa = int(ssaa)
+    if H < 1 or W < 1 or H * ssaa > RENDER_MAX_SIZE or W * ssaa > RENDER_MAX_SIZE:
+        raise ValueError(f"size * ssaa must be from 1 to {RENDER_MAX_SIZE}, got {(H, W)} * {ssaa}")
+    if not (ortho_scale > 0 and math.isfinite(ortho_scale)):
+        raise ValueError(f"ortho_scale must be positive and finite, got {ortho_scale}")
+    log2s = material.log2_shininess()
+    mats = camera_views(elevations_deg, azimuths_deg, radius, up) if views is None else \
+        np.ascontiguousarray(np.asarray(views, dtype=np.float32).reshape(-1, 12))
+    n_views = mats.shape[0]
+    if n_views < 1:
+        raise ValueError("no views")
+    bg_img = None
+    if isinstance(background, (np.ndarray, torch.Tensor)) and background.ndim == 3:
+        bg_img = torch.as_tensor(background)
+        if bg_img.dtype != torch.uint8 or tuple(bg_img.shape) != (H, W, 3):
+            raise ValueError(f"a background image must be uint8 [{H},{W},3], got {bg_img.dtype} {tuple(bg_img.shape)}")
+        params = material.params()
+    else:
+        params = material.params(background)
+    verts, faces = _mesh_tensors(verts, faces)
+    dev = verts.device
+    V, F = verts.size(0), faces.size(0)
+    RW, RH = W * ssaa, H * ssaa
+    lib = _hip.load()
+    ws_bytes = lib.fpsg_mesh_render_workspace_bytes(V, F, n_views, RW, RH)
+    if ws_bytes == 0:
+        raise ValueError(f"unsupported render shape (V={V}, F={F}, views={n_views}, {RW}x{RH})")
+    ws = torch.empty((ws_bytes // 16 + 1, 2), dtype=torch.int64, device=dev)
+    d_views = torch.from_numpy(mats).to(dev)
+    if bg_img is not None:
+        bg_img = bg_img.to(dev).contiguous()
+    image = torch.empty((n_views, H, W, 3), dtype=torch.uint8, device=dev)
+    radiance = face_id = depth = None
+    if return_buffers:
+        radiance = torch.empty((n_views, H, W, 3), dtype=torch.float32, device=dev)
+        face_id = torch.empty((n_views, RH, RW), dtype=torch.int32, device=dev)
+        depth = torch.empty((n_views, RH, RW), dtype=torch.float32, device=dev)
+    c_params = (ctypes.c_float * 15)(*params.tolist())
+
+    def opt(t):
+        return None if t is None else _hip.ptr(t)
+
+    with torch.cuda.device(dev):
+        rc = lib.fpsg_mesh_render(_hip.ptr(verts), V, _hip.ptr(faces), F, _hip.ptr(d_views), n_views, RW, RH, ssaa,
+                                  float(ortho_scale), c_params, log2s, opt(bg_img), _hip.ptr(image), opt(radiance),
+                                  opt(face_id), opt(depth), _hip.ptr(ws), ws.numel() * 8, _hip.stream_of(verts))
+    _hip.check(rc, "fpsg_mesh_render")
+    if return_buffers:
+        return image, {"face_id": face_id, "depth": depth, "radiance": radiance}
+    return image
+
+
+# ------------------------------------------------------------------------------------- list files
+def _write_pairs(path, pairs):
+    with open(path, "w") as f:
+        f.write("\n".join(f"{img}\t{pc}" for img, pc in pairs))     # no trailing newline, as the reference writes
+
+
+def write_modelnet_lists(img_root: str, pc_root: str, output: str, train_classes=None, test_classes=None) -> dict:
+    """The list files of the reference's ``generate_dataset.py`` (``--dataset modelnet``) for an existing tree
+    ``<img_root>/<label>/<train|test>/<item>/<view>.png`` + ``<pc_root>/<label>/<split>/<item>.ply``:
+    ``<output>/modelnet_train.txt`` (items of the base classes), ``<output>/modelnet_test.txt`` (novel classes) and
+    ``<output>/modelnet_files/modelnet+<label>.txt`` for every class of either kind, every line
+    ``<first view>\\t<item>.ply``, no newline after the last.  A novel class wins over a base class of the same name,
+    other classes appear nowhere, items without views are left out -- all as there.  Unlike there, labels, items and
+    views are taken in sorted order, so the files do not depend on the file system, and the view listed is the first
+    of the sorted ones.  No GPU.  -> ``{"train": n, "test": n, "classes": [labels written]}``."""
+    train_classes = MODELNET_TRAIN_CLASSES if train_classes is None else tuple(train_classes)
+    test_classes = MODELNET_TEST_CLASSES if test_classes is None else tuple(test_classes)
+    train, test, written = [], [], []
+    os.makedirs(os.path.join(output, "modelnet_files"), exist_ok=True)
+    for label in sorted(os.listdir(img_root)):
+        if not os.path.isdir(os.path.join(img_root, label)):
+            continue
+        pairs = []
+        for split in ("train", "test"):
+            c_path = os.path.join(img_root, label, split)
+            if not os.path.isdir(c_path):
+                continue
+            for item in sorted(os.listdir(c_path)):
+                item_dir = os.path.join(c_path, item)
+                if not os.path.isdir(item_dir):
+                    continue
+                views = sorted(os.listdir(item_dir))
+                if views:
+                    pairs.append((os.path.join(item_dir, views[0]), os.path.join(pc_root, label, split, f"{item}.ply")))
+        if label in test_classes:
+            test += pairs
+        elif label in train_classes:
+            train += pairs
+        else:
+            continue
+        _write_pairs(os.path.join(output, "modelnet_files", f"modelnet+{label}.txt"), pairs)
+        written.append(label)
+    _write_pairs(os.path.join(output, "modelnet_train.txt"), train)
+    _write_pairs(os.path.join(output, "modelnet_test.txt"), test)
+    return {"train": len(train), "test": len(test), "classes": written}

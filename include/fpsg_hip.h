@@ -1168,6 +1168,86 @@ int fpsg_adam_step_segments_ema(float* param, const float* const* grad_ptrs, con
  * Errors before the launch: FPSG_E_SHAPE for n = 0 or a == b, FPSG_E_NULL, FPSG_E_ALIGN (both 16-byte aligned). */
 int fpsg_flat_swap(float* a, float* b, size_t n, fpsg_stream_t stream);
 
+/* ---- K26: area-weighted sampling of a triangle mesh's surface -----------------------------------
+ * Makes the point clouds the reference took from pcl_mesh_sampling.  PCL is not pinned; the definition below is the
+ * specification.  Two entry points: the mesh's integer CDF, then any number of sample sets from it.
+ * verts [V,3] fp32; faces [F,3] int32; cdf [F] uint64; u [m,3] fp32; points [m,3] fp32; face_idx [m] int32.
+ * Areas, fp32, every operation rounded on its own (no fused multiply-add), a, b, c the face's vertices:
+ *   e1 = b - a, e2 = c - a;  n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x);
+ *   area = 0.5 sqrt((nx nx + ny ny) + nz nz), sqrt correctly rounded.
+ *   A face with a NaN or infinite area, or with a vertex index outside [0, V), has area 0.
+ * Weights: q_f = (uint64) rint((double) area_f / (double) area_max 2^32) (round half to even), 0 for area 0; area_max
+ * is the largest area (an integer maximum over the bits: no order of arrival enters).  C_f = q_0 + ... + q_f in
+ * uint64: integers, so every scan order gives the same C, and nothing depends on the launch shape.  F <=
+ * FPSG_MESH_MAX_FACES keeps C below 2^57.  T = C_{F-1}; T = 0 iff every face has area 0.
+ * Samples, one per row of u, each component first clamped to [0, 1 - 2^-24] (NaN -> 0):
+ *   t = min((uint64) ((double) u0 (double) T), T - 1)  (the product rounded to double, then truncated);
+ *   f = the first face with C_f > t -- a face with q = 0 is never chosen;
+ *   s = sqrt(u1); w0 = 1 - s, w1 = s (1 - u2), w2 = s u2;  p = (w0 a + w1 b) + w2 c per coordinate, fp32, no fma.
+ * fpsg_mesh_cdf writes cdf; its workspace (fpsg_mesh_cdf_workspace_bytes, 8-byte aligned) holds the areas and block
+ * sums.  fpsg_mesh_sample takes `total` = cdf[F-1], which the caller reads back from the device: total = 0 is refused
+ * with FPSG_E_SHAPE and a message that names the cause, before any launch.  The kernel clamps what it reads from cdf
+ * and faces into range, so a foreign cdf gives wrong samples and never an access outside the buffers.
+ * Errors, all before any launch: FPSG_E_SHAPE for V, F or m < 1, total = 0 or > F 2^32, a workspace too small;
+ * FPSG_E_LIMIT for F > FPSG_MESH_MAX_FACES; FPSG_E_NULL for a null pointer; FPSG_E_ALIGN for a misaligned one (cdf
+ * and ws: 8 bytes).  fpsg_mesh_cdf_workspace_bytes returns 0 for a shape the entry refuses.
+ */
+#define FPSG_MESH_MAX_FACES (1 << 24)
+size_t fpsg_mesh_cdf_workspace_bytes(int V, int F);
+int fpsg_mesh_cdf(const float* verts, int V, const int32_t* faces, int F, uint64_t* cdf, void* ws, size_t ws_bytes,
+                  fpsg_stream_t stream);
+int fpsg_mesh_sample(const float* verts, int V, const int32_t* faces, int F, const uint64_t* cdf, uint64_t total,
+                     const float* u, int m, float* points, int32_t* face_idx, fpsg_stream_t stream);
+
+/* ---- K27: orthographic Phong views of a triangle mesh -------------------------------------------
+ * Makes the view images the reference rendered with Blender (src/preprocess/phong.py, view_generator.py).  The
+ * scene file is not pinned; the definition below is the specification.
+ * verts [V,3] fp32; faces [F,3] int32; views [n_views,12] fp32: per view the camera's right, up and forward unit
+ * vectors and its position c (built by the caller in double, rounded once).  W x H is the SAMPLE resolution, ssaa
+ * a divisor of both; the outputs image (uint8) and radiance (fp32) are [n_views, H/ssaa, W/ssaa, 3], face_id (int32,
+ * -1 = empty) and depth (fp32, +inf = empty) are [n_views, H, W].  Any output may be NULL, not all.
+ * All of the following in fp32 with every operation rounded on its own (no fma), divisions and sqrt correctly rounded.
+ * Project, per vertex p and view:  d = p - c;  x = (dx rx + dy ry) + dz rz, y likewise with up, z with forward;
+ *   S = max(W, H);  px = (x / ortho_scale) S + W/2;  py = H/2 - (y / ortho_scale) S;
+ *   X = (int) rint(clamp(256 px, -2^28, 2^28)), Y likewise.  A vertex whose px, py or z is not finite is invalid, and
+ *   so is every face that uses it or an index outside [0, V).
+ * Rasterise, per face and view, integers: A2 = (X1-X0)(Y2-Y0) - (Y1-Y0)(X2-X0) in int64; A2 = 0: skipped; A2 < 0:
+ *   vertices 1 and 2 swap (both windings are drawn).  For the pixel centre P = (256 i + 128, 256 j + 128):
+ *   E0 = edge(1,2), E1 = edge(2,0), E2 = edge(0,1), edge(a,b) = (Xb-Xa)(Py-Ya) - (Yb-Ya)(Px-Xa).  The pixel is covered
+ *   iff for every edge E > 0, or E = 0 and the edge is a top or left one: Yb - Ya < 0, or Yb = Ya and Xb - Xa > 0.
+ *   Depth: l_k = (float) E_k / (float) A2;  z = (l0 z0 + l1 z1) + l2 z2; a sample with z not finite is dropped.
+ *   Z-buffer: per sample the minimum of (key(z) << 32) | face, key = the float's bits mapped to an unsigned integer
+ *   of the same order (negative: all bits inverted; otherwise: sign bit set): the nearest face wins, the lowest face
+ *   index on equal depth, whatever the order of the launches (64-bit integer atomicMin).
+ * Shade, per covered sample, from the face's vertices a, b, c in world space (in the faces' own order): the edges
+ *   b - a and c - a, each turned into the camera frame as e = ((wx rx + wy ry) + wz rz, likewise with up, likewise
+ *   with forward) -- the camera's distance never enters, so a normal's error depends on the triangle's shape alone;
+ *   n = e1 x e2 (components as in K26), len = sqrt((nx nx + ny ny) + nz nz), n = n / len, or (0,0,-1) when
+ *   len is 0 or not finite; n = -n when nz > 0 (two-sided).  With the light direction l (unit, camera frame, towards
+ *   the light): ndl = (nx lx + ny ly) + nz lz; diff = max(ndl, 0); spec = ndl > 0 ? max(lz - (2 ndl) nz, 0) : 0,
+ *   squared log2_shininess times;  colour_c = (ka_c + kd_c diff) + ks_c spec.
+ * Resolve, per output pixel: acc = the sum of its covered samples' colours in row-major sample order, k their number,
+ *   inv = 1 / ssaa^2, out_c = acc_c inv + bg_c (1 - k inv); bg = the colour params[12..14], or with bg_image (uint8
+ *   [H/ssaa, W/ssaa, 3], shared by the views) (float) byte / 255.  radiance = out; image = (uint8) rint(clamp(out,0,1) 255).
+ * params (HOST pointer, 15 floats): ka[3], kd[3], ks[3], l[3], bg[3].
+ * Workspace: fpsg_mesh_render_workspace_bytes (16-byte aligned): projected vertices, the z-buffer, the list of
+ * triangles too large for one thread.
+ * Errors, all before any launch: FPSG_E_SHAPE for V, F, n_views, W or H < 1, ssaa outside 1..FPSG_RENDER_MAX_SSAA or
+ * not a divisor of W and H, an ortho_scale not positive and finite, log2_shininess outside
+ * 0..FPSG_RENDER_MAX_LOG2_SHININESS, a workspace too small; FPSG_E_LIMIT for W or H > FPSG_RENDER_MAX_SIZE, n_views >
+ * FPSG_RENDER_MAX_VIEWS or F n_views >= 2^31; FPSG_E_NULL for a null verts, faces, views, params or ws, or no output
+ * at all; FPSG_E_ALIGN for a misaligned pointer.  fpsg_mesh_render_workspace_bytes returns 0 for a refused shape.
+ */
+#define FPSG_RENDER_MAX_SIZE 8192
+#define FPSG_RENDER_MAX_VIEWS 1024
+#define FPSG_RENDER_MAX_SSAA 4
+#define FPSG_RENDER_MAX_LOG2_SHININESS 10
+size_t fpsg_mesh_render_workspace_bytes(int V, int F, int n_views, int W, int H);
+int fpsg_mesh_render(const float* verts, int V, const int32_t* faces, int F, const float* views, int n_views, int W,
+                     int H, int ssaa, float ortho_scale, const float* params, int log2_shininess,
+                     const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* face_id, float* depth, void* ws,
+                     size_t ws_bytes, fpsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
