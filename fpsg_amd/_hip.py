@@ -241,6 +241,12 @@ SIGNATURES = {
     "fpsg_mesh_render": [_c_f32p, _c_int, _c_i32p, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_int, ctypes.c_float,
                          ctypes.POINTER(ctypes.c_float), _c_int, ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _c_i32p,
                          _c_f32p, ctypes.c_void_p, ctypes.c_size_t, _c_stream],
+    "fpsg_mesh_render_materials_workspace_bytes": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int],
+    "fpsg_mesh_render_materials": [_c_f32p, _c_int, _c_i32p, _c_int, _c_i32p, _c_f32p, ctypes.POINTER(ctypes.c_float),
+                                   _c_int, ctypes.POINTER(ctypes.c_int32), _c_int, ctypes.c_void_p, ctypes.c_longlong,
+                                   _c_f32p, _c_int, _c_int, _c_int, _c_int, ctypes.c_float,
+                                   ctypes.POINTER(ctypes.c_float), _c_int, ctypes.c_void_p, ctypes.c_void_p, _c_f32p,
+                                   _c_i32p, _c_f32p, ctypes.c_void_p, ctypes.c_size_t, _c_stream],
 }
 _RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_grad_norm_workspace_bytes": ctypes.c_size_t,
 "fpsg_chamfer_workspace_bytes": ctypes.c_size_t,
@@ -254,7 +260,8 @@ _RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_grad_norm_workspace_bytes
              "fpsg_uniform_workspace_bytes": ctypes.c_size_t,
              "fpsg_swd_workspace_bytes": ctypes.c_size_t,
              "fpsg_mesh_cdf_workspace_bytes": ctypes.c_size_t,
-             "fpsg_mesh_render_workspace_bytes": ctypes.c_size_t}
+             "fpsg_mesh_render_workspace_bytes": ctypes.c_size_t,
+             "fpsg_mesh_render_materials_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 _lock = threading.Lock()

@@ -9,6 +9,8 @@
 //   * render_raster_large_kernel: a fixed grid strides over the list's entries, kChunks waves each, lanes over the
 //     bounding box's pixels;
 //   * render_shade_kernel: one output pixel per thread: its ssaa^2 samples shaded and composited over the background.
+// K28 (fpsg_mesh_render_materials) runs the same three kernels and then render_shade_materials_kernel, K27's shade
+// pass with a base colour per face: a material's Kd, or its texture looked up at the sample's interpolated uv.
 #include "fpsg_common.h"
 
 namespace fpsg {
@@ -242,6 +244,160 @@ __global__ __launch_bounds__(256) void render_shade_kernel(const float* __restri
   }
 }
 
+// ---- K28: the shade pass with materials and textures ------------------------------------------------------------
+struct MaterialParams {
+  RenderParams base;
+  float ambient, diffuse;
+};
+
+struct MaterialTables {
+  const int* face_material;              // [F], outside [0, M): no material
+  const v4f* materials;                  // [M]: Kd and the texture index (validated by the entry: -1 or in [0, T))
+  const float* face_uv;                  // [F, 3, 2]
+  const int* tex_table;                  // [T, 3]: texel offset, width, height (validated: inside texels)
+  const unsigned char* texels;
+  int M;
+};
+
+// t in [0, 1); anything else (1 after rounding, NaN from an overflowed uv) becomes 0
+__device__ __forceinline__ float repeat_unit(float u) {
+  const float t = u - __builtin_floorf(u);
+  return (t >= 0.0f && t < 1.0f) ? t : 0.0f;
+}
+
+__device__ __forceinline__ int wrap_index(int i, int n) {
+  const int r = i % n;
+  return r < 0 ? r + n : r;
+}
+
+// Bilinear lookup with repeat; w, h >= 1 and the texture inside texels by the entry's checks, indices wrapped here.
+__device__ __forceinline__ void texel_lookup(const unsigned char* __restrict__ tex, int w, int h, float u, float v,
+                                             float& r, float& g, float& b) {
+  const float tu = repeat_unit(u), tv = repeat_unit(v);
+  const float x = tu * (float)w - 0.5f, y = (1.0f - tv) * (float)h - 0.5f;
+  const float xf = __builtin_floorf(x), yf = __builtin_floorf(y);
+  const float fx = x - xf, fy = y - yf;
+  const int ix0 = wrap_index((int)xf, w), ix1 = wrap_index((int)xf + 1, w);
+  const int iy0 = wrap_index((int)yf, h), iy1 = wrap_index((int)yf + 1, h);
+  const float gx = 1.0f - fx, gy = 1.0f - fy;
+  const float w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
+  const unsigned char* p00 = tex + ((size_t)iy0 * w + ix0) * 3;
+  const unsigned char* p10 = tex + ((size_t)iy0 * w + ix1) * 3;
+  const unsigned char* p01 = tex + ((size_t)iy1 * w + ix0) * 3;
+  const unsigned char* p11 = tex + ((size_t)iy1 * w + ix1) * 3;
+  float c[3];
+  for (int k = 0; k < 3; ++k)
+    c[k] = ((w00 * ((float)p00[k] / 255.0f) + w10 * ((float)p10[k] / 255.0f)) + w01 * ((float)p01[k] / 255.0f)) +
+           w11 * ((float)p11[k] / 255.0f);
+  r = c[0]; g = c[1]; b = c[2];
+}
+
+__global__ __launch_bounds__(256) void render_shade_materials_kernel(
+    const float* __restrict__ verts, const int* __restrict__ faces, int V, const float* __restrict__ views,
+    const v4i* __restrict__ snapped, const u64* __restrict__ zbuf, int W, int H, int ssaa, MaterialParams Q,
+    MaterialTables T, const unsigned char* __restrict__ bg_img, unsigned char* __restrict__ image,
+    float* __restrict__ radiance, int* __restrict__ face_id, float* __restrict__ depth) {
+  const RenderParams& P = Q.base;
+  const int ow = W / ssaa, oh = H / ssaa;
+  const int ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (ox >= ow || oy >= oh) return;
+  const int view = blockIdx.z;
+  const float* M = views + (size_t)view * 12;
+  const u64* z0 = zbuf + (size_t)view * W * H;
+  const v4i* snap_v = snapped + (size_t)view * V;
+  float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f;
+  int covered = 0;
+  for (int sy = 0; sy < ssaa; ++sy) {
+    for (int sx = 0; sx < ssaa; ++sx) {
+      const int i = ox * ssaa + sx, j = oy * ssaa + sy;
+      const size_t pix = (size_t)j * W + i;
+      const u64 key = z0[pix];
+      const bool hit = key != kEmpty;
+      if (face_id) face_id[(size_t)view * W * H + pix] = hit ? (int)(unsigned)key : -1;
+      if (depth) depth[(size_t)view * W * H + pix] = hit ? key_depth((unsigned)(key >> 32)) : __builtin_inff();
+      if (!hit) continue;
+      const unsigned f = (unsigned)key;                // written by the rasteriser: a face with indices in range
+      const int ia = faces[(size_t)f * 3], ib = faces[(size_t)f * 3 + 1], ic = faces[(size_t)f * 3 + 2];
+      const float* a = verts + (size_t)ia * 3;
+      const float* b = verts + (size_t)ib * 3;
+      const float* c = verts + (size_t)ic * 3;
+      // the light's terms: K27's, operation for operation
+      const float w1x = b[0] - a[0], w1y = b[1] - a[1], w1z = b[2] - a[2];
+      const float w2x = c[0] - a[0], w2y = c[1] - a[1], w2z = c[2] - a[2];
+      const float e1x = (w1x * M[0] + w1y * M[1]) + w1z * M[2], e1y = (w1x * M[3] + w1y * M[4]) + w1z * M[5],
+                  e1z = (w1x * M[6] + w1y * M[7]) + w1z * M[8];
+      const float e2x = (w2x * M[0] + w2y * M[1]) + w2z * M[2], e2y = (w2x * M[3] + w2y * M[4]) + w2z * M[5],
+                  e2z = (w2x * M[6] + w2y * M[7]) + w2z * M[8];
+      float nx = e1y * e2z - e1z * e2y;
+      float ny = e1z * e2x - e1x * e2z;
+      float nz = e1x * e2y - e1y * e2x;
+      const float len = __builtin_sqrtf((nx * nx + ny * ny) + nz * nz);
+      if (len > 0.0f && finite_f(len)) { nx = nx / len; ny = ny / len; nz = nz / len; }
+      else { nx = 0.0f; ny = 0.0f; nz = -1.0f; }
+      if (nz > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
+      const float ndl = (nx * P.light[0] + ny * P.light[1]) + nz * P.light[2];
+      const float diff = __builtin_fmaxf(ndl, 0.0f);
+      float spec = ndl > 0.0f ? __builtin_fmaxf(P.light[2] - (2.0f * ndl) * nz, 0.0f) : 0.0f;
+      for (int k = 0; k < P.log2_shininess; ++k) spec = spec * spec;
+      ++covered;
+      const int m = T.M > 0 ? T.face_material[f] : -1;
+      if ((unsigned)m >= (unsigned)T.M) {              // no material: K27's colour
+        acc0 += (P.ka[0] + P.kd[0] * diff) + P.ks[0] * spec;
+        acc1 += (P.ka[1] + P.kd[1] * diff) + P.ks[1] * spec;
+        acc2 += (P.ka[2] + P.kd[2] * diff) + P.ks[2] * spec;
+        continue;
+      }
+      const v4f mat = T.materials[m];
+      float b0 = mat.x, b1 = mat.y, b2 = mat.z;
+      const int tex = (int)mat.w;
+      if (tex >= 0) {
+        const float* q = T.face_uv + (size_t)f * 6;
+        float u0 = q[0], v0 = q[1], u1 = q[2], v1 = q[3], u2 = q[4], v2 = q[5];
+        if (finite_f(u0) && finite_f(v0) && finite_f(u1) && finite_f(v1) && finite_f(u2) && finite_f(v2)) {
+          const v4i s0 = snap_v[ia];
+          v4i s1 = snap_v[ib], s2 = snap_v[ic];
+          i64 A2 = (i64)(s1.x - s0.x) * (i64)(s2.y - s0.y) - (i64)(s1.y - s0.y) * (i64)(s2.x - s0.x);
+          if (A2 < 0) {                                // the rasteriser's swap, and the uv with the corners
+            const v4i s = s1; s1 = s2; s2 = s;
+            float t = u1; u1 = u2; u2 = t;
+            t = v1; v1 = v2; v2 = t;
+            A2 = -A2;
+          }
+          const int px = 256 * i + 128, py = 256 * j + 128;
+          const float A = (float)A2;                   // not 0: the face was drawn
+          const float l0 = (float)edge_fn(s1.x, s1.y, s2.x, s2.y, px, py) / A;
+          const float l1 = (float)edge_fn(s2.x, s2.y, s0.x, s0.y, px, py) / A;
+          const float l2 = (float)edge_fn(s0.x, s0.y, s1.x, s1.y, px, py) / A;
+          const float u = (l0 * u0 + l1 * u1) + l2 * u2;
+          const float v = (l0 * v0 + l1 * v1) + l2 * v2;
+          const int* e = T.tex_table + (size_t)tex * 3;
+          texel_lookup(T.texels + (size_t)e[0] * 3, e[1], e[2], u, v, b0, b1, b2);
+        }
+      }
+      const float a0 = Q.ambient * b0, a1 = Q.ambient * b1, a2 = Q.ambient * b2;
+      const float d0 = Q.diffuse * b0, d1 = Q.diffuse * b1, d2 = Q.diffuse * b2;
+      acc0 += (a0 + d0 * diff) + P.ks[0] * spec;
+      acc1 += (a1 + d1 * diff) + P.ks[1] * spec;
+      acc2 += (a2 + d2 * diff) + P.ks[2] * spec;
+    }
+  }
+  const float inv = 1.0f / (float)(ssaa * ssaa);
+  const float rest = 1.0f - (float)covered * inv;
+  const size_t o = (((size_t)view * oh + oy) * ow + ox) * 3;
+  float bg0 = P.bg[0], bg1 = P.bg[1], bg2 = P.bg[2];
+  if (bg_img) {
+    const unsigned char* q = bg_img + ((size_t)oy * ow + ox) * 3;
+    bg0 = (float)q[0] / 255.0f; bg1 = (float)q[1] / 255.0f; bg2 = (float)q[2] / 255.0f;
+  }
+  const float r0 = acc0 * inv + bg0 * rest, r1 = acc1 * inv + bg1 * rest, r2 = acc2 * inv + bg2 * rest;
+  if (radiance) { radiance[o] = r0; radiance[o + 1] = r1; radiance[o + 2] = r2; }
+  if (image) {
+    image[o] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r0, 0.0f), 1.0f) * 255.0f);
+    image[o + 1] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r1, 0.0f), 1.0f) * 255.0f);
+    image[o + 2] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r2, 0.0f), 1.0f) * 255.0f);
+  }
+}
+
 struct RenderWs {
   size_t cam, snapped, zbuf, list, counter, total;
 };
@@ -256,6 +412,24 @@ inline RenderWs render_ws(int V, int F, int NV, int W, int H) {
   w.counter = o; o += 16;
   w.total = o;
   return w;
+}
+
+// K28's workspace: K27's, then the material and texture tables copied from the host
+struct MaterialWs {
+  size_t materials, tex_table, total;
+};
+
+inline MaterialWs material_ws(const RenderWs& L, int M, int T) {
+  MaterialWs w;
+  size_t o = L.total;
+  w.materials = o; o += (size_t)M * 16;
+  w.tex_table = o; o += (((size_t)T * 12) + 15) & ~(size_t)15;
+  w.total = o;
+  return w;
+}
+
+inline bool material_limit_ok(int M, int T, long long n_texels) {
+  return M <= FPSG_RENDER_MAX_MATERIALS && T <= FPSG_RENDER_MAX_TEXTURES && n_texels <= FPSG_RENDER_MAX_TEXELS;
 }
 
 inline bool render_shape_ok(int V, int F, int NV, int W, int H, int ssaa) {
@@ -328,4 +502,105 @@ extern "C" int fpsg_mesh_render(const float* verts, int V, const int32_t* faces,
   hipLaunchKernelGGL(render_shade_kernel, dim3((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4), (unsigned)n_views),
                      dim3(256), 0, st, verts, faces, views, zbuf, W, H, ssaa, P, bg_image, image, radiance, face_id, depth);
   return launch_status("fpsg_mesh_render");
+}
+
+extern "C" size_t fpsg_mesh_render_materials_workspace_bytes(int V, int F, int n_views, int W, int H, int M, int T) {
+  using namespace fpsg;
+  if (!render_shape_ok(V, F, n_views, W, H, 1) || !render_limit_ok(F, n_views, W, H) || M < 0 || T < 0 ||
+      !material_limit_ok(M, T, 0))
+    return 0;
+  return material_ws(render_ws(V, F, n_views, W, H), M, T).total;
+}
+
+extern "C" int fpsg_mesh_render_materials(const float* verts, int V, const int32_t* faces, int F,
+                                          const int32_t* face_material, const float* face_uv, const float* materials,
+                                          int M, const int32_t* tex_table, int T, const uint8_t* texels,
+                                          long long n_texels, const float* views, int n_views, int W, int H, int ssaa,
+                                          float ortho_scale, const float* params, int log2_shininess,
+                                          const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* face_id,
+                                          float* depth, void* ws, size_t ws_bytes, fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_REQUIRE(render_shape_ok(V, F, n_views, W, H, ssaa), FPSG_E_SHAPE,
+               "fpsg_mesh_render_materials: V,F,n_views,W,H must be positive, ssaa from 1 to %d and a divisor of W "
+               "and H (got %d,%d,%d,%d,%d,%d)", FPSG_RENDER_MAX_SSAA, V, F, n_views, W, H, ssaa);
+  FPSG_REQUIRE(M >= 0 && T >= 0 && n_texels >= 0, FPSG_E_SHAPE,
+               "fpsg_mesh_render_materials: M, T and n_texels must not be negative (got %d,%d,%lld)", M, T, n_texels);
+  FPSG_REQUIRE(ortho_scale > 0.0f && ortho_scale <= 3.0e38f, FPSG_E_SHAPE,
+               "fpsg_mesh_render_materials: ortho_scale must be positive and finite");
+  FPSG_REQUIRE(log2_shininess >= 0 && log2_shininess <= FPSG_RENDER_MAX_LOG2_SHININESS, FPSG_E_SHAPE,
+               "fpsg_mesh_render_materials: log2_shininess must be from 0 to %d (got %d)",
+               FPSG_RENDER_MAX_LOG2_SHININESS, log2_shininess);
+  FPSG_REQUIRE(render_limit_ok(F, n_views, W, H), FPSG_E_LIMIT,
+               "fpsg_mesh_render_materials: W,H <= %d, n_views <= %d and F n_views < 2^31 are supported (got "
+               "%d,%d,%d,%d)", FPSG_RENDER_MAX_SIZE, FPSG_RENDER_MAX_VIEWS, W, H, n_views, F);
+  FPSG_REQUIRE(material_limit_ok(M, T, n_texels), FPSG_E_LIMIT,
+               "fpsg_mesh_render_materials: M <= %d, T <= %d and n_texels <= %d are supported (got %d,%d,%lld)",
+               FPSG_RENDER_MAX_MATERIALS, FPSG_RENDER_MAX_TEXTURES, FPSG_RENDER_MAX_TEXELS, M, T, n_texels);
+  FPSG_REQUIRE_PTR(verts); FPSG_REQUIRE_PTR(faces); FPSG_REQUIRE_PTR(views); FPSG_REQUIRE_PTR(ws);
+  FPSG_REQUIRE(params != nullptr, FPSG_E_NULL, "fpsg_mesh_render_materials: null pointer 'params'");
+  if (M > 0) { FPSG_REQUIRE_PTR(face_material); FPSG_REQUIRE_PTR(materials); }
+  if (T > 0) { FPSG_REQUIRE_PTR(face_uv); FPSG_REQUIRE_PTR(tex_table); }
+  FPSG_REQUIRE(T == 0 || texels != nullptr, FPSG_E_NULL, "fpsg_mesh_render_materials: null pointer 'texels'");
+  FPSG_REQUIRE(image || radiance || face_id || depth, FPSG_E_NULL, "fpsg_mesh_render_materials: no output requested");
+  FPSG_REQUIRE(!misaligned4(radiance) && !misaligned4(face_id) && !misaligned4(depth), FPSG_E_ALIGN,
+               "fpsg_mesh_render_materials: an output is not 4-byte aligned");
+  FPSG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15u) == 0, FPSG_E_ALIGN,
+               "fpsg_mesh_render_materials: 'ws' must be 16-byte aligned");
+  for (int t = 0; t < T; ++t) {                        // tex_table and materials are host memory
+    const long long off = tex_table[3 * t], tw = tex_table[3 * t + 1], th = tex_table[3 * t + 2];
+    FPSG_REQUIRE(off >= 0 && tw >= 1 && th >= 1 && off + tw * th <= n_texels, FPSG_E_SHAPE,
+                 "fpsg_mesh_render_materials: texture %d (offset %lld, %lld x %lld) reaches outside the %lld texels", t,
+                 off, tw, th, n_texels);
+  }
+  for (int m = 0; m < M; ++m) {
+    const float ti = materials[4 * m + 3];
+    FPSG_REQUIRE(ti >= -1.0f && ti < (float)T && ti == __builtin_floorf(ti), FPSG_E_SHAPE,
+                 "fpsg_mesh_render_materials: material %d has texture index %g, outside [-1, %d)", m, (double)ti, T);
+  }
+  const RenderWs L = render_ws(V, F, n_views, W, H);
+  const MaterialWs LM = material_ws(L, M, T);
+  FPSG_REQUIRE(ws_bytes >= LM.total, FPSG_E_SHAPE, "fpsg_mesh_render_materials: workspace of %zu bytes, %zu needed",
+               ws_bytes, LM.total);
+  MaterialParams Q;
+  RenderParams& P = Q.base;
+  for (int k = 0; k < 3; ++k) {
+    P.ka[k] = params[k]; P.kd[k] = params[3 + k]; P.ks[k] = params[6 + k];
+    P.light[k] = params[9 + k]; P.bg[k] = params[12 + k];
+  }
+  P.log2_shininess = log2_shininess;
+  Q.ambient = params[15]; Q.diffuse = params[16];
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  v4f* cam = reinterpret_cast<v4f*>(base + L.cam);
+  v4i* snapped = reinterpret_cast<v4i*>(base + L.snapped);
+  u64* zbuf = reinterpret_cast<u64*>(base + L.zbuf);
+  unsigned* list = reinterpret_cast<unsigned*>(base + L.list);
+  unsigned* counter = reinterpret_cast<unsigned*>(base + L.counter);
+  MaterialTables TB;
+  TB.face_material = face_material;
+  TB.materials = reinterpret_cast<const v4f*>(base + LM.materials);
+  TB.face_uv = face_uv;
+  TB.tex_table = reinterpret_cast<const int*>(base + LM.tex_table);
+  TB.texels = texels;
+  TB.M = M;
+  hipError_t e = hipMemsetAsync(zbuf, 0xff, (size_t)n_views * W * H * 8, st);
+  if (e == hipSuccess) e = hipMemsetAsync(counter, 0, 16, st);
+  // the two host tables: pageable memory is staged before hipMemcpyAsync returns (pinned: see the header)
+  if (e == hipSuccess && M > 0)
+    e = hipMemcpyAsync(base + LM.materials, materials, (size_t)M * 16, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && T > 0)
+    e = hipMemcpyAsync(base + LM.tex_table, tex_table, (size_t)T * 12, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) { set_error("fpsg_mesh_render_materials: %s", hipGetErrorString(e)); return (int)e; }
+  hipLaunchKernelGGL(render_project_kernel, dim3((unsigned)((V + 255) / 256), (unsigned)n_views), dim3(256), 0, st,
+                     verts, V, views, ortho_scale, W, H, cam, snapped);
+  hipLaunchKernelGGL(render_raster_kernel, dim3((unsigned)((F + 255) / 256), (unsigned)n_views), dim3(256), 0, st,
+                     faces, F, V, cam, snapped, W, H, zbuf, list, counter);
+  hipLaunchKernelGGL(render_raster_large_kernel, dim3(1024), dim3(256), 0, st, faces, F, V, cam, snapped, W, H, zbuf,
+                     list, counter, (unsigned)n_views);
+  const int ow = W / ssaa, oh = H / ssaa;
+  hipLaunchKernelGGL(render_shade_materials_kernel,
+                     dim3((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4), (unsigned)n_views), dim3(256), 0, st,
+                     verts, faces, V, views, snapped, zbuf, W, H, ssaa, Q, TB, bg_image, image, radiance, face_id,
+                     depth);
+  return launch_status("fpsg_mesh_render_materials");
 }

@@ -1,8 +1,9 @@
-"""Datasets from meshes: mesh files in, sampled clouds (K26) and rendered views (K27) out, plus the list files that
-``fpsg_amd.datasets`` reads.  The definitions of both kernels are in ``include/fpsg_hip.h``.
+"""Datasets from meshes: mesh files in, sampled clouds (K26) and rendered views (K27, with materials and textures K28)
+out, plus the list files that ``fpsg_amd.datasets`` reads.  The definitions of the kernels are in ``include/fpsg_hip.h``.
 
-The host part (``load_mesh``, ``normalize_mesh``, ``write_ply_points``, ``camera_views``, ``write_modelnet_lists``)
-needs no GPU.  ``sample_surface`` and ``render_views`` run on the GPU only: a CPU tensor raises ``FpsgHipError``.
+The host part (``load_mesh``, ``load_obj_scene``, ``pack_textures``, ``normalize_mesh``, ``write_ply_points``,
+``camera_views``, ``write_modelnet_lists``, ``write_shapenet_lists``) needs no GPU.  ``sample_surface`` and
+``render_views`` run on the GPU only: a CPU tensor raises ``FpsgHipError``.
 """
 from __future__ import annotations
 
@@ -25,6 +26,12 @@ RENDER_MAX_SSAA = 4             # FPSG_RENDER_MAX_SSAA
 MODELNET_TRAIN_CLASSES = ("airplane", "bathtub", "bed", "chair", "desk", "dresser", "monitor", "sofa", "table",
                           "toilet")
 MODELNET_TEST_CLASSES = ("cup", "keyboard", "door", "laptop", "bowl")
+# TRAIN_SET_DIC['shapenet'] / TEST_SET_DIC['shapenet'] there, as synset ids (datasets.SHAPENET_ID2NAME)
+SHAPENET_TRAIN_CLASSES = ("02691156", "02942699", "02958343", "03046257", "03001627", "03325088", "04004475", "04099429")
+SHAPENET_TEST_CLASSES = ("02880940", "02992529", "03593526", "03797390", "03211117")
+RENDER_MAX_MATERIALS = 65536    # FPSG_RENDER_MAX_MATERIALS
+RENDER_MAX_TEXTURES = 4096      # FPSG_RENDER_MAX_TEXTURES
+RENDER_MAX_TEXELS = 1 << 28     # FPSG_RENDER_MAX_TEXELS
 
 
 # ------------------------------------------------------------------------------------------ files
@@ -133,6 +140,234 @@ def _load_obj(path):
     tri, tri_line = _fan(flat, starts, ntok, fno)
     _check_range(tri, tri_line, nv, path)
     return np.ascontiguousarray(verts), tri.astype(np.int32)
+
+
+# ------------------------------------------------------------------------ .obj with materials (K28)
+@dataclasses.dataclass
+class ObjMaterial:
+    name: str
+    kd: tuple = (0.8, 0.8, 0.8)          # the value a .mtl record without Kd gets from common importers
+    texture: str | None = None           # map_Kd, resolved relative to the .mtl; None when absent or not found
+
+
+@dataclasses.dataclass
+class ObjScene:
+    """A ``.obj`` with what its ``.mtl`` says about colour.  ``face_material [F]`` int32 indexes ``materials`` (-1: none);
+    ``face_uv [F,3,2]`` float32 holds the corners' ``vt`` in the faces' vertex order, NaN where a corner has none."""
+    verts: np.ndarray
+    faces: np.ndarray
+    face_material: np.ndarray
+    face_uv: np.ndarray
+    materials: list
+    warnings: list
+
+
+# options of a map_Kd statement and how many numbers may follow each (o, s, t: one to three)
+_MAP_OPTIONS = {"-blendu": 1, "-blendv": 1, "-cc": 1, "-clamp": 1, "-imfchan": 1, "-texres": 1, "-bm": 1, "-boost": 1,
+                "-type": 1, "-mm": 2, "-o": 3, "-s": 3, "-t": 3}
+
+
+def _is_number(tok):
+    try:
+        float(tok)
+        return True
+    except ValueError:
+        return False
+
+
+def _map_file(rest: str) -> str:
+    """The file name of a ``map_Kd`` statement: options in front skipped, blanks inside kept, backslashes turned."""
+    toks = rest.split()
+    i = 0
+    while i < len(toks) and toks[i] in _MAP_OPTIONS:
+        n, opt = _MAP_OPTIONS[toks[i]], toks[i]
+        i += 1
+        if opt in ("-o", "-s", "-t"):
+            k = 0
+            while k < n and i < len(toks) - 1 and _is_number(toks[i]):   # the last token is the name, number or not
+                i, k = i + 1, k + 1
+        else:
+            i += n
+    return " ".join(toks[i:]).strip().replace("\\", "/")
+
+
+def _load_mtl(path, warnings):
+    """-> [ObjMaterial] in the file's order.  Only ``newmtl``, ``Kd`` and ``map_Kd`` are read."""
+    out = []
+    with open(path, "r", errors="replace") as f:
+        for raw in f:
+            line = raw.split("#", 1)[0].strip()
+            key, _, rest = line.partition(" ")
+            rest = rest.strip()
+            if key == "newmtl":
+                out.append(ObjMaterial(rest))
+            elif not out:
+                continue
+            elif key == "Kd":
+                try:
+                    kd = [float(t) for t in rest.split()[:3]]
+                    out[-1].kd = tuple(kd) if len(kd) == 3 else (kd[0],) * 3
+                except (ValueError, IndexError):
+                    warnings.append(f"{path}: bad Kd {rest!r} in material {out[-1].name!r}")
+            elif key == "map_Kd":
+                name = _map_file(rest)
+                tex = os.path.normpath(os.path.join(os.path.dirname(path), name))
+                if name and os.path.isfile(tex):
+                    out[-1].texture = tex
+                else:
+                    warnings.append(f"{path}: texture {name!r} of material {out[-1].name!r} not found")
+    return out
+
+
+def _obj_verts(vrecords, path):
+    """The ``v`` records of an ``.obj`` -> float32 [V,3], with ``_load_obj``'s checks."""
+    nv = len(vrecords)
+    if nv == 0:
+        return np.zeros((0, 3), np.float32)
+    vlines = np.char.partition(vrecords, " ")[:, 2]
+    per = np.char.count(vlines, " ") + 1
+    if (per < 3).any():
+        raise ValueError(f"{path}: a 'v' record with fewer than 3 numbers")
+    if not (per == per[0]).all():
+        raise ValueError(f"{path}: 'v' records of different lengths")
+    return np.ascontiguousarray(_numbers(vlines, np.float32, path, "vertex").reshape(nv, -1)[:, :3])
+
+
+def load_obj_scene(path: str) -> ObjScene:
+    """``.obj`` -> ``ObjScene``: what ``load_mesh`` reads, plus ``vt``, ``usemtl`` and the ``mtllib`` files beside it.
+
+    Polygons are fan-triangulated with their ``uv`` and material.  ``v/vt`` and ``v/vt/vn`` corners, negative indices
+    for both.  A ``usemtl`` counts from its line on, wherever the ``mtllib`` stands.  In a ``.mtl`` only ``newmtl``,
+    ``Kd`` and ``map_Kd`` are read (``d``, ``illum``, ``Ka``, ``Ks``, ``Ns`` and unknown keys are ignored); options in
+    front of a texture's name are skipped, the name may hold blanks and backslashes and is resolved relative to the
+    ``.mtl``.  A missing ``.mtl``, a missing texture, an unknown material and a ``vt`` index out of range are entries in
+    ``warnings``, not errors: the faces fall back to no material, to ``Kd``, or to NaN ``uv`` (which K28 shades with
+    ``Kd``).  Face indices outside the vertices raise ``ValueError`` as in ``load_mesh``."""
+    lines, lineno = _lines(path)
+    warnings = []
+    is_v, is_vt, is_f = (np.char.startswith(lines, k) for k in ("v ", "vt ", "f "))
+    is_use = np.char.startswith(lines, "usemtl")
+    verts = _obj_verts(lines[is_v], path)
+    nv = len(verts)
+    vt_rows = [(t.split() + ["0", "0"])[1:3] for t in lines[is_vt].tolist()]   # u, v; a third number is ignored
+    try:
+        vts = np.array(vt_rows, dtype=np.float64).astype(np.float32).reshape(-1, 2)
+    except ValueError as e:
+        raise ValueError(f"{path}: bad 'vt' record: {e}") from None
+    materials = []
+    for lib in lines[np.char.startswith(lines, "mtllib ")].tolist():
+        name = lib.partition(" ")[2].strip().replace("\\", "/")
+        mtl = os.path.join(os.path.dirname(path), name)
+        if os.path.isfile(mtl):
+            materials += _load_mtl(mtl, warnings)
+        else:
+            warnings.append(f"{path}: material library {name!r} not found")
+    index = {}
+    for k, m in enumerate(materials):
+        index.setdefault(m.name, k)
+    flines, fno = lines[is_f], lineno[is_f]
+    if len(flines) == 0:
+        return ObjScene(verts, np.zeros((0, 3), np.int32), np.zeros((0,), np.int32), np.zeros((0, 3, 2), np.float32),
+                        materials, warnings)
+    ftext = np.char.partition(flines, " ")[:, 2]
+    ntok = np.char.count(ftext, " ") + 1
+    tokens = np.array(" ".join(ftext.tolist()).split(), dtype=np.str_)
+    parts = np.char.partition(tokens, "/")
+    vt_text = np.char.partition(parts[:, 2], "/")[:, 0]
+    try:
+        vi = parts[:, 0].astype(np.int64)
+        ti = np.where(vt_text == "", "0", vt_text).astype(np.int64)             # 0 is no index in OBJ
+    except ValueError as e:
+        raise ValueError(f"{path}: bad face record: {e}") from None
+    seen_v = np.repeat(np.cumsum(is_v)[is_f], ntok)
+    seen_t = np.repeat(np.cumsum(is_vt)[is_f], ntok)
+    vi = np.where(vi < 0, vi + seen_v, np.where(vi > 0, vi - 1, -1))
+    ti = np.where(ti < 0, ti + seen_t, np.where(ti > 0, ti - 1, -1))
+    starts = np.cumsum(ntok) - ntok
+    pos, tri_line = _fan(np.arange(len(tokens)), starts, ntok, fno)           # token positions of every triangle
+    tri = vi[pos]
+    _check_range(tri, tri_line, nv, path)
+    tri_t = ti[pos]
+    has = (tri_t >= 0) & (tri_t < len(vts))
+    if ((tri_t >= len(vts)) | ((tri_t < 0) & (vt_text[pos] != ""))).any():
+        warnings.append(f"{path}: 'vt' index out of range; those corners have no uv")
+    uv = np.full(tri.shape + (2,), np.nan, np.float32)
+    if len(vts):
+        uv[has] = vts[tri_t[has]]
+    # the usemtl in force at each face line
+    use_names = [t.partition(" ")[2].strip() for t in lines[is_use].tolist()]
+    use_idx = np.array([index.get(n, -1) for n in use_names] + [-1], dtype=np.int32)   # the last slot: no usemtl yet
+    for n in sorted({n for n in use_names if n not in index}):
+        warnings.append(f"{path}: unknown material {n!r}")
+    which = np.cumsum(is_use)[is_f] - 1                                        # -1 picks the last slot
+    owner = np.repeat(np.arange(len(flines)), ntok)[pos[:, 0]] if len(pos) else np.zeros((0,), np.int64)
+    return ObjScene(verts, tri.astype(np.int32), use_idx[which][owner].astype(np.int32), uv, materials, warnings)
+
+
+@dataclasses.dataclass
+class PackedTextures:
+    """What K28 reads: ``texels`` uint8 ``[n,3]`` (every texture's rows from the top, back to back), ``tex_table`` int32
+    ``[T,3]`` (texel offset, width, height) and ``materials`` float32 ``[M,4]`` (``Kd``, texture index or -1)."""
+    texels: np.ndarray
+    tex_table: np.ndarray
+    materials: np.ndarray
+    warnings: list
+
+
+def pack_textures(materials, max_size: int = 1024) -> PackedTextures:
+    """Decodes the materials' texture files with PIL, each file once however many materials name it; one larger than
+    ``max_size`` on a side is scaled down to it, keeping its aspect.  A file that does not decode is a warning and its
+    materials fall back to ``Kd``."""
+    from PIL import Image
+    if max_size < 1:
+        raise ValueError(f"max_size must be positive, got {max_size}")
+    slot, blocks, table, warnings = {}, [], [], []
+    mats = np.full((len(materials), 4), -1.0, np.float32)
+    offset = 0
+    for k, m in enumerate(materials):
+        mats[k, :3] = m.kd
+        if m.texture is None:
+            continue
+        if m.texture not in slot:
+            try:
+                with Image.open(m.texture) as im:
+                    im = im.convert("RGB")
+                    w, h = im.size
+                    if max(w, h) > max_size:
+                        scale = max_size / max(w, h)
+                        im = im.resize((max(1, round(w * scale)), max(1, round(h * scale))), Image.BILINEAR)
+                    arr = np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
+            except (OSError, ValueError, SyntaxError) as e:
+                warnings.append(f"{m.texture}: not decoded ({e})")
+                slot[m.texture] = -1
+            else:
+                slot[m.texture] = len(table)
+                table.append((offset, arr.shape[1], arr.shape[0]))
+                blocks.append(arr.reshape(-1, 3))
+                offset += arr.shape[0] * arr.shape[1]
+        mats[k, 3] = slot[m.texture]
+    texels = np.concatenate(blocks) if blocks else np.zeros((0, 3), np.uint8)
+    return PackedTextures(texels, np.asarray(table, dtype=np.int32).reshape(-1, 3), mats, warnings)
+
+
+@dataclasses.dataclass
+class RenderScene:
+    """The per-face colour inputs of K28 for ``render_views(scene=...)``: ``face_material`` int32 ``[F]`` and ``face_uv``
+    float32 ``[F,3,2]`` on the mesh's device (either may be None without materials / textures), the host tables
+    ``materials [M,4]`` and ``tex_table [T,3]``, and ``texels`` uint8 ``[n,3]`` on the device."""
+    face_material: torch.Tensor | None
+    face_uv: torch.Tensor | None
+    materials: np.ndarray
+    tex_table: np.ndarray
+    texels: torch.Tensor | None
+
+
+def scene_tensors(scene: ObjScene, packed: PackedTextures, device) -> RenderScene:
+    """An ``ObjScene`` and its packed textures moved to ``device`` for ``render_views``."""
+    T = len(packed.tex_table)
+    return RenderScene(torch.from_numpy(scene.face_material).to(device) if len(packed.materials) else None,
+                       torch.from_numpy(scene.face_uv).to(device) if T else None, packed.materials, packed.tex_table,
+                       torch.from_numpy(packed.texels).to(device) if T else None)
 
 
 def load_mesh(path: str):
@@ -326,10 +561,34 @@ def camera_views(elevations_deg=60.0, azimuths_deg=range(0, 360, 30), radius: fl
     return np.asarray(rows, dtype=np.float64).astype(np.float32)
 
 
+def _scene_arguments(scene, F, dev):
+    """Shapes, types and devices of a ``RenderScene``; what the values must satisfy is the C entry's to refuse."""
+    mat_table = np.ascontiguousarray(np.asarray(scene.materials, dtype=np.float32).reshape(-1, 4))
+    tex_table = np.ascontiguousarray(np.asarray(scene.tex_table, dtype=np.int32).reshape(-1, 3))
+
+    def dev_input(t, shape, dtype, name, needed):
+        if t is None:
+            if needed:
+                raise ValueError(f"scene.{name} is needed")
+            return None
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dim() != len(shape) or \
+                any(want not in (-1, have) for want, have in zip(shape, t.shape)):
+            raise ValueError(f"scene.{name} must be a tensor {shape} on {dev}, got {tuple(getattr(t, 'shape', ()))} "
+                             f"on {getattr(t, 'device', None)}")
+        t = t.detach().contiguous()
+        _hip.dev_tensor(t, dtype, f"scene.{name}")
+        return t
+
+    face_material = dev_input(scene.face_material, (F,), torch.int32, "face_material", len(mat_table) > 0)
+    face_uv = dev_input(scene.face_uv, (F, 3, 2), torch.float32, "face_uv", len(tex_table) > 0)
+    texels = dev_input(scene.texels, (-1, 3), torch.uint8, "texels", len(tex_table) > 0)
+    return mat_table, tex_table, face_material, face_uv, texels
+
+
 def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevations_deg=60.0,
                  azimuths_deg=range(0, 360, 30), radius: float = 3.0, ortho_scale: float = 2.0, up: str = "z",
                  ssaa: int = 2, background=(1.0, 1.0, 1.0), material: PhongMaterial = PhongMaterial(),
-                 return_buffers: bool = False, views=None):
+                 return_buffers: bool = False, views=None, scene: RenderScene | None = None):
     """Orthographic, flat-shaded Phong views of a mesh (K27) -> uint8 ``[n_views, H, W, 3]`` on the mesh's device.
 
     ``size``: an int (square) or ``(H, W)``; the mesh is rasterised at ``size * ssaa`` and every output pixel is the
@@ -339,6 +598,10 @@ def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevatio
     a face are drawn and lit (ModelNet's are inconsistent).  With ``return_buffers`` also a dict: ``face_id`` int32 and
     ``depth`` float32 ``[n_views, H ssaa, W ssaa]`` (-1 / +inf where empty) and ``radiance`` float32 ``[n_views,H,W,3]``,
     of which the image is ``rint(clamp(radiance, 0, 1) * 255)``.  Bitwise the same on every run.
+
+    With ``scene`` (a ``RenderScene``, see ``scene_tensors``) the shade pass is K28's: a face with a material takes its
+    base colour from the material's ``Kd`` or texture in place of ``material.color``, scaled by ``material.ambient`` and
+    ``material.diffuse``; a face without one is shaded as without ``scene``, and so are ``face_id`` and ``depth``.
 
     ``ValueError`` for bad shapes and options, ``FpsgHipError`` for CPU tensors."""
     H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
@@ -368,7 +631,12 @@ def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevatio
     V, F = verts.size(0), faces.size(0)
     RW, RH = W * ssaa, H * ssaa
     lib = _hip.load()
-    ws_bytes = lib.fpsg_mesh_render_workspace_bytes(V, F, n_views, RW, RH)
+    if scene is not None:
+        mat_table, tex_table, face_material, face_uv, texels = _scene_arguments(scene, F, dev)
+        M, T = len(mat_table), len(tex_table)
+        ws_bytes = lib.fpsg_mesh_render_materials_workspace_bytes(V, F, n_views, RW, RH, M, T)
+    else:
+        ws_bytes = lib.fpsg_mesh_render_workspace_bytes(V, F, n_views, RW, RH)
     if ws_bytes == 0:
         raise ValueError(f"unsupported render shape (V={V}, F={F}, views={n_views}, {RW}x{RH})")
     ws = torch.empty((ws_bytes // 16 + 1, 2), dtype=torch.int64, device=dev)
@@ -386,11 +654,23 @@ def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevatio
     def opt(t):
         return None if t is None else _hip.ptr(t)
 
-    with torch.cuda.device(dev):
-        rc = lib.fpsg_mesh_render(_hip.ptr(verts), V, _hip.ptr(faces), F, _hip.ptr(d_views), n_views, RW, RH, ssaa,
-                                  float(ortho_scale), c_params, log2s, opt(bg_img), _hip.ptr(image), opt(radiance),
-                                  opt(face_id), opt(depth), _hip.ptr(ws), ws.numel() * 8, _hip.stream_of(verts))
-    _hip.check(rc, "fpsg_mesh_render")
+    if scene is not None:
+        c_params = (ctypes.c_float * 17)(*params.tolist(), float(material.ambient), float(material.diffuse))
+        c_mats = mat_table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if M else None
+        c_table = tex_table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if T else None
+        with torch.cuda.device(dev):
+            rc = lib.fpsg_mesh_render_materials(
+                _hip.ptr(verts), V, _hip.ptr(faces), F, opt(face_material), opt(face_uv), c_mats, M, c_table, T,
+                opt(texels), 0 if texels is None else texels.size(0), _hip.ptr(d_views), n_views, RW, RH, ssaa,
+                float(ortho_scale), c_params, log2s, opt(bg_img), _hip.ptr(image), opt(radiance), opt(face_id),
+                opt(depth), _hip.ptr(ws), ws.numel() * 8, _hip.stream_of(verts))
+        _hip.check(rc, "fpsg_mesh_render_materials")
+    else:
+        with torch.cuda.device(dev):
+            rc = lib.fpsg_mesh_render(_hip.ptr(verts), V, _hip.ptr(faces), F, _hip.ptr(d_views), n_views, RW, RH, ssaa,
+                                      float(ortho_scale), c_params, log2s, opt(bg_img), _hip.ptr(image), opt(radiance),
+                                      opt(face_id), opt(depth), _hip.ptr(ws), ws.numel() * 8, _hip.stream_of(verts))
+        _hip.check(rc, "fpsg_mesh_render")
     if return_buffers:
         return image, {"face_id": face_id, "depth": depth, "radiance": radiance}
     return image
@@ -440,4 +720,47 @@ def write_modelnet_lists(img_root: str, pc_root: str, output: str, train_classes
         written.append(label)
     _write_pairs(os.path.join(output, "modelnet_train.txt"), train)
     _write_pairs(os.path.join(output, "modelnet_test.txt"), test)
+    return {"train": len(train), "test": len(test), "classes": written}
+
+
+def write_shapenet_lists(root: str, output: str, train_classes=None, test_classes=None) -> dict:
+    """The list files of the reference's ``generate_dataset.py`` (``--dataset shapenet``) for an existing tree
+    ``<root>/<synset>/<item>/models/{npy_file.npy, images/*}`` with its split files ``<root>/<synset>_train.txt`` and
+    ``<root>/<synset>_test.txt`` (one item per line): ``<output>/shapenet_train.txt`` (every item of the base classes,
+    of both splits, as there), ``<output>/shapenet_test.txt`` (novel classes) and
+    ``<output>/shapenet_files/shapenet+<synset>.txt``, every line ``<root>/<synset>/<item>/models``, no newline after
+    the last.  A synset of both kinds is listed in both files, as there.  Unlike there, items are taken in sorted order,
+    only items that have ``npy_file.npy`` and at least one view are listed, and a class file is written only for a class
+    that has a split file (the reference wrote one for each of the 55 synsets, mostly empty).  No GPU.
+    -> ``{"train": n, "test": n, "classes": [synsets written]}``."""
+    train_classes = SHAPENET_TRAIN_CLASSES if train_classes is None else tuple(train_classes)
+    test_classes = SHAPENET_TEST_CLASSES if test_classes is None else tuple(test_classes)
+    train, test, written = [], [], []
+    os.makedirs(os.path.join(output, "shapenet_files"), exist_ok=True)
+    for synset in sorted(set(train_classes) | set(test_classes)):
+        names, found = set(), False
+        for split in ("train", "test"):
+            path = os.path.join(root, f"{synset}_{split}.txt")
+            if os.path.isfile(path):
+                found = True
+                with open(path, "r") as f:
+                    names |= {line.strip() for line in f if line.strip()}
+        if not found:
+            continue
+        items = []
+        for name in sorted(names):
+            models = os.path.join(root, synset, name, "models")
+            views = os.path.join(models, "images")
+            if os.path.isfile(os.path.join(models, "npy_file.npy")) and os.path.isdir(views) and os.listdir(views):
+                items.append(models)
+        if synset in train_classes:
+            train += items
+        if synset in test_classes:
+            test += items
+        with open(os.path.join(output, "shapenet_files", f"shapenet+{synset}.txt"), "w") as f:
+            f.write("\n".join(items))
+        written.append(synset)
+    for name, rows in (("shapenet_train.txt", train), ("shapenet_test.txt", test)):
+        with open(os.path.join(output, name), "w") as f:
+            f.write("\n".join(rows))
     return {"train": len(train), "test": len(test), "classes": written}

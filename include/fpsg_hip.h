@@ -1248,6 +1248,56 @@ int fpsg_mesh_render(const float* verts, int V, const int32_t* faces, int F, con
                      const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* face_id, float* depth, void* ws,
                      size_t ws_bytes, fpsg_stream_t stream);
 
+/* ---- K28: K27's views with a base colour per face: materials and textures -------------------------
+ * For meshes that carry materials (ShapeNet's model_normalized.obj with its .mtl: Kd per part, map_Kd textures).
+ * fpsg_mesh_render_materials projects, rasterises and fills the z-buffer with K27's kernels, so face_id and depth are
+ * K27's; only the shade pass differs.  Every argument it shares with fpsg_mesh_render means what it means there.
+ * All of the following in fp32 with every operation rounded on its own (no fma), divisions correctly rounded.
+ * Extra inputs: face_material [F] int32 (device), a value outside [0, M) = no material; face_uv [F,3,2] fp32 (device),
+ *   the corners' (u, v) in the face's own vertex order; materials [M,4] fp32 (HOST): Kd r, g, b and the texture index
+ *   as an integer value, -1 = none; tex_table [T,3] int32 (HOST): texel offset, width w, height h; texels (device)
+ *   uint8 [n_texels, 3], RGB, every texture row-major from its TOP row, all textures back to back.
+ *   params (HOST pointer, 17 floats): K27's 15, then ambient and diffuse.
+ *   M = 0: face_material and materials may be NULL.  T = 0: face_uv, tex_table and texels may be NULL.
+ * Shade, per covered sample of face f: diff and spec are K27's.
+ *   No material: colour_c = (ka_c + kd_c diff) + ks_c spec -- K27's colour, so a call in which no face has a material
+ *   gives fpsg_mesh_render's image, radiance, face_id and depth bit for bit.
+ *   Material with base colour b:  a_c = ambient b_c;  d_c = diffuse b_c;  colour_c = (a_c + d_c diff) + ks_c spec.
+ * Base colour: b = Kd when the material has no texture, or when any of the face's six uv numbers is not finite.
+ *   Otherwise b is the texel colour alone (Kd is not multiplied in: many materials carry a black Kd beside a map_Kd).
+ * uv at the sample: from the snapped vertices of the face's corners 0, 1, 2 and the sample's centre P, as K27
+ *   rasterises: A2 in int64; A2 < 0: corners 1 and 2 swap, and their uv with them, A2 = -A2.  E0 = edge(1,2),
+ *   E1 = edge(2,0), E2 = edge(0,1) in int64;  l_k = (float) E_k / (float) A2;
+ *   u = (l0 u0 + l1 u1) + l2 u2;  v = (l0 v0 + l1 v1) + l2 v2.  (Orthographic: affine interpolation is the correct one.)
+ * Lookup in the texture (w, h), which repeats: tu = u - floor(u), and tu = 0 unless 0 <= tu < 1 (a tu rounded up to
+ *   1, a NaN from an overflow); tv likewise.  x = tu w - 0.5;  y = (1 - tv) h - 0.5 (v = 0 is the bottom row, as in OBJ).
+ *   x0 = floor(x), fx = x - x0, gx = 1 - fx; y0, fy, gy likewise.  The four neighbours are the texels
+ *   (x0 mod w, y0 mod h), (x0+1 mod w, y0 mod h), (x0 mod w, y0+1 mod h), (x0+1 mod w, y0+1 mod h) with values
+ *   c00, c10, c01, c11, each channel (float) byte / 255, and weights w00 = gx gy, w10 = fx gy, w01 = gx fy, w11 = fx fy:
+ *   b_c = ((w00 c00 + w10 c10) + w01 c01) + w11 c11.
+ *   Wrapped neighbours make b a continuous function of (u, v), also across the texture's seam: a last-bit difference
+ *   in u moves b by a last bit's worth and never to the texture's far side.  No mipmaps, no gamma: bytes are values.
+ * Resolve and outputs: K27's.
+ * Workspace: fpsg_mesh_render_materials_workspace_bytes (16-byte aligned): K27's, then the two host tables, which the
+ * entry copies there with hipMemcpyAsync on the stream: pageable arrays (malloc, numpy) are read before it returns,
+ * pinned ones must stay unchanged until the stream has passed the call.
+ * Errors, all before any launch or copy: those of fpsg_mesh_render; FPSG_E_SHAPE for a negative M, T or n_texels, a
+ * texture index that is not an integer in [-1, T), a tex_table entry with offset < 0, w < 1, h < 1 or
+ * offset + w h > n_texels; FPSG_E_LIMIT for M > FPSG_RENDER_MAX_MATERIALS, T > FPSG_RENDER_MAX_TEXTURES or n_texels >
+ * FPSG_RENDER_MAX_TEXELS; FPSG_E_NULL for a null face_material or materials with M > 0, a null face_uv, tex_table
+ * or texels with T > 0; FPSG_E_ALIGN for a misaligned pointer.  The workspace function returns 0 for a refused shape.
+ */
+#define FPSG_RENDER_MAX_MATERIALS 65536
+#define FPSG_RENDER_MAX_TEXTURES 4096
+#define FPSG_RENDER_MAX_TEXELS (1 << 28)
+size_t fpsg_mesh_render_materials_workspace_bytes(int V, int F, int n_views, int W, int H, int M, int T);
+int fpsg_mesh_render_materials(const float* verts, int V, const int32_t* faces, int F, const int32_t* face_material,
+                               const float* face_uv, const float* materials, int M, const int32_t* tex_table, int T,
+                               const uint8_t* texels, long long n_texels, const float* views, int n_views, int W, int H,
+                               int ssaa, float ortho_scale, const float* params, int log2_shininess,
+                               const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* face_id, float* depth,
+                               void* ws, size_t ws_bytes, fpsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
