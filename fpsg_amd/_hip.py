@@ -81,6 +81,7 @@ SIGNATURES = {
     "fpsg_sinkhorn_divergence_grad": [_c_f32p, _c_f32p, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_int, _c_f32p, _c_f32p,
                                       _c_f32p, _c_f32p, _c_stream],
     "fpsg_dec1_tiles": [_c_int],
+    "fpsg_dec1_fits": [_c_int, _c_int, _c_int],
     "fpsg_dec1_fwd": [_c_f32p, _c_f32p, _c_int, _c_int, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_int, _c_int,
                       _c_int, _c_int, _c_int, ctypes.c_float, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_stream],
     "fpsg_dec1_bwd": [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int,

@@ -33,6 +33,11 @@ constexpr int kD1Threads = 64 * kD1Waves;
 constexpr int kD1ChPerWave = 4;
 constexpr int kD1Tile = kD1Waves * kD1ChPerWave;       // channels per workgroup
 constexpr int kD1MaxBP = 8192;                         // points of a patch over the batch that fit LDS (96 KB)
+constexpr size_t kD1MaxLds = 160 * 1024;               // LDS of a CU: what one workgroup can be given
+
+inline size_t dec1_lds_bytes(int B, int P, bool bwd) {
+  return ((size_t)3 * B * P + (size_t)kD1Tile * B + (bwd ? (size_t)kD1Waves * 64 * 12 : 0)) * sizeof(float);
+}
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
@@ -354,17 +359,17 @@ __global__ __launch_bounds__(kD1Threads) void dec1_bwd_kernel(Dec1Args a, const 
   }
 }
 
-inline size_t dec1_lds_bytes(int B, int P, bool bwd) {
-  return ((size_t)3 * B * P + (size_t)kD1Tile * B + (bwd ? (size_t)kD1Waves * 64 * 12 : 0)) * sizeof(float);
-}
-
-inline int dec1_check(const char* fn, int G, int D, int B, int P, int ldw, int wofs) {
+inline int dec1_check(const char* fn, int G, int D, int B, int P, int ldw, int wofs, bool bwd) {
   FPSG_REQUIRE(G > 0 && D > 0 && B > 0 && P > 0, FPSG_E_SHAPE, "%s: G,D,B,P must be positive (got %d,%d,%d,%d)", fn, G,
                D, B, P);
   FPSG_REQUIRE(P % 4 == 0 && P <= 256 && ((P / 4) & (P / 4 - 1)) == 0, FPSG_E_SHAPE,
                "%s: P = %d must be 4 x a power of two, at most 256 (lanes of 4 points, a cloud = one lane group)", fn, P);
   FPSG_REQUIRE((long)B * P <= kD1MaxBP, FPSG_E_LIMIT, "%s: B*P = %ld exceeds %d (the patch's points live in LDS)", fn,
                (long)B * P, kD1MaxBP);
+  // many small clouds: the latent rows [32][B] (and the backward's reduction buffer) outgrow the CU before B*P does
+  FPSG_REQUIRE(dec1_lds_bytes(B, P, bwd) <= kD1MaxLds, FPSG_E_LIMIT,
+               "%s: B = %d, P = %d need %zu bytes of LDS, more than the %zu of a CU", fn, B, P, dec1_lds_bytes(B, P, bwd),
+               kD1MaxLds);
   FPSG_REQUIRE(G <= 65535 && wofs >= 0 && wofs + 3 <= ldw, FPSG_E_SHAPE, "%s: bad G / weight columns", fn);
   return 0;
 }
@@ -374,13 +379,17 @@ inline int dec1_check(const char* fn, int G, int D, int B, int P, int ldw, int w
 
 extern "C" int fpsg_dec1_tiles(int D) { return (D + fpsg::kD1Tile - 1) / fpsg::kD1Tile; }
 
+extern "C" int fpsg_dec1_fits(int B, int P, int bwd) {
+  return fpsg::dec1_check("fpsg_dec1_fits", 1, 1, B, P, 3, 0, bwd != 0) == 0;
+}
+
 extern "C" int fpsg_dec1_fwd_ld(const float* hlat, int ld_hlat, const float* w, int ldw, int wofs, const float* pts, int ld_pts,
                                 const float* gamma, const float* beta, const float* running_mean,
                                 const float* running_var, int G, int D, int B, int P, int training, float eps,
                                 float* out, int ld_out, float* chan, float* batch_mean, float* batch_var_unbiased,
                                 fpsg_stream_t stream) {
   using namespace fpsg;
-  int rc = dec1_check("fpsg_dec1_fwd", G, D, B, P, ldw, wofs);
+  int rc = dec1_check("fpsg_dec1_fwd", G, D, B, P, ldw, wofs, false);
   if (rc) return rc;
   FPSG_REQUIRE_PTR(hlat); FPSG_REQUIRE_PTR(w); FPSG_REQUIRE_PTR(pts); FPSG_REQUIRE_PTR(gamma); FPSG_REQUIRE_PTR(beta);
   FPSG_REQUIRE_PTR(out); FPSG_REQUIRE_PTR(chan);
@@ -420,7 +429,7 @@ extern "C" int fpsg_dec1_bwd_ld(const float* dout, int ld_dout, const float* hla
                                 int training, int accumulate, float* dhlat, float* dw, float* dpts_part, float* dgamma,
                                 float* dbeta, fpsg_stream_t stream) {
   using namespace fpsg;
-  int rc = dec1_check("fpsg_dec1_bwd", G, D, B, P, ldw, wofs);
+  int rc = dec1_check("fpsg_dec1_bwd", G, D, B, P, ldw, wofs, true);
   if (rc) return rc;
   FPSG_REQUIRE_PTR(dout); FPSG_REQUIRE_PTR(hlat); FPSG_REQUIRE_PTR(w); FPSG_REQUIRE_PTR(pts); FPSG_REQUIRE_PTR(chan);
   FPSG_REQUIRE_PTR(dhlat); FPSG_REQUIRE_PTR(dw); FPSG_REQUIRE_PTR(dpts_part); FPSG_REQUIRE_PTR(dgamma); FPSG_REQUIRE_PTR(dbeta);

@@ -262,13 +262,19 @@ def _update_running_calls(bns, r, stats):
         bn_counters.count_batch(b, n * r)
 
 
+def _layer1_sizes_ok(B, P) -> bool:
+    """The sizes K9 takes, asked of the library (``fpsg_dec1_fits``, the entry points' own check): P = 4 x a power of
+    two <= 256, B*P <= 8192, and the backward's LDS (the larger of the two) within a CU's."""
+    from . import _hip
+    return _hip.load().fpsg_dec1_fits(B, P, 1) != 0
+
+
 def _layer1_fused_ok(x, pts, B, P, act) -> bool:
-    """K9 applies: ROCm tensors, ReLU, patch sizes the kernel tiles (P = 4 x a power of two <= 256,
-    B*P <= 8192).  ``FPSG_DEC1=0`` selects the library chain (A/B measurements)."""
+    """K9 applies: ROCm tensors, ReLU, patch sizes the kernel takes (``_layer1_sizes_ok``); everything else runs the
+    library chain.  ``FPSG_DEC1=0`` selects the library chain (A/B measurements)."""
     import os
     return (x.is_cuda and pts.is_cuda and x.dtype == torch.float32 and act is F.relu
-            and os.environ.get("FPSG_DEC1", "1") != "0" and P % 4 == 0 and P <= 256
-            and ((P // 4) & (P // 4 - 1)) == 0 and B * P <= 8192)
+            and os.environ.get("FPSG_DEC1", "1") != "0" and _layer1_sizes_ok(B, P))
 
 
 class _DecoderLayer1(torch.autograd.Function):

@@ -707,8 +707,13 @@ int fpsg_sinkhorn_divergence_grad(const float* x, const float* y, int B, int N, 
  *   bwd: from dout [G,D,B*P]: dhlat [G,D,B] (gradient of the latent GEMM's output), the three point columns of
  *        dw (same layout / ldw / wofs as w; other columns untouched), dpts_part [G, fpsg_dec1_tiles(D), 3, B*P]
  *        (partial sums over channel tiles; the caller adds them up), dgamma, dbeta [G*D].
- * pts, out, dout 16-byte aligned.  Deterministic. */
+ * pts, out, dout 16-byte aligned.  Deterministic.
+ * A workgroup keeps the patch's points and its 32 latent rows in LDS: 4 (3 B P + 32 B) bytes, the backward 24576 more.
+ * Beyond the 163840 bytes of a CU (many small clouds: P = 16 from B = 436 in the backward, P = 4 from B = 931 in the
+ * forward) the entry points answer FPSG_E_LIMIT.  fpsg_dec1_fits(B, P, bwd) is that shape check alone (P, B*P and
+ * the LDS of the forward, bwd = 0, or the backward): 1 when a call of these sizes would pass it, else 0. */
 int fpsg_dec1_tiles(int D);
+int fpsg_dec1_fits(int B, int P, int bwd);
 int fpsg_dec1_fwd(const float* hlat, const float* w, int ldw, int wofs, const float* pts,
                   const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                   int G, int D, int B, int P, int training, float eps, float* out, float* chan,
