@@ -66,7 +66,9 @@ def main(opt):
             sample = to_device(sample, device)
             if getattr(opt, "npy_folder", ""):
                 os.makedirs(opt.npy_folder, exist_ok=True)
-                model.draw_reconstruction(sample, [item, opt.npy_folder])
+                model.draw_reconstruction(sample, [item, opt.npy_folder],
+                                          renderer=getattr(opt, "sample_renderer", "matplotlib"),
+                                          up=getattr(opt, "sample_up", "z"))
                 continue
             out = run_item(sample)
             name = sample["class"][0]

@@ -167,6 +167,12 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--eval_interval", type=int, default=20)
     g.add_argument("--eval_model", type=str, default="NONE")
     g.add_argument("--sequential_eval", action="store_true")
+    g.add_argument("--sample_renderer", type=str, default="matplotlib", choices=("matplotlib", "splat"),
+                   help="What draws the sample images (generated against ground-truth clouds): 'matplotlib', the "
+                        "reference's scatter panels on the host, or 'splat', shaded spheres on the GPU, generated "
+                        "clouds in the decoder's patch colours, both on one scale [default: matplotlib];")
+    g.add_argument("--sample_up", type=str, default="z", choices=("z", "y"),
+                   help="With --sample_renderer splat: the clouds' up axis, z for ModelNet, y for ShapeNet [default: z];")
     if evaluation:
         g.add_argument("--npy_folder", type=str, default="", help="Where draw_reconstruction dumps go;")
         eval_report.add_arguments(g)

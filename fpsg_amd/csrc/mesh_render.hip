@@ -11,7 +11,7 @@
 //   * render_shade_kernel: one output pixel per thread: its ssaa^2 samples shaded and composited over the background.
 // K28 (fpsg_mesh_render_materials) runs the same three kernels and then render_shade_materials_kernel, K27's shade
 // pass with a base colour per face: a material's Kd, or its texture looked up at the sample's interpolated uv.
-#include "fpsg_common.h"
+#include "render_common.h"
 
 namespace fpsg {
 namespace {
@@ -21,29 +21,7 @@ typedef long long i64;
 
 constexpr int kSmallBox = 64;            // pixel centres a single thread still draws
 constexpr int kChunks = 16;              // waves that share one large triangle
-constexpr float kSnapLimit = 268435456.0f;   // 2^28: snapped coordinates stay below it, edge functions below 2^60
 constexpr u64 kEmpty = ~0ull;
-
-struct RenderParams {
-  float ka[3], kd[3], ks[3], light[3], bg[3];
-  int log2_shininess;
-};
-
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// float -> unsigned with the same order (negative depths included)
-__device__ __forceinline__ unsigned depth_key(float z) {
-  const unsigned b = __float_as_uint(z);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_depth(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-__device__ __forceinline__ int snap(float p) {
-  const float v = p * 256.0f;
-  return (int)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(v, -kSnapLimit), kSnapLimit));
-}
 
 __global__ __launch_bounds__(256) void render_project_kernel(const float* __restrict__ verts, int V,
                                                              const float* __restrict__ views, float ortho_scale,
@@ -51,19 +29,12 @@ __global__ __launch_bounds__(256) void render_project_kernel(const float* __rest
                                                              v4i* __restrict__ snapped) {
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v >= V) return;
-  const float* M = views + (size_t)blockIdx.y * 12;    // right, up, forward, position
-  const float dx = verts[(size_t)v * 3] - M[9], dy = verts[(size_t)v * 3 + 1] - M[10],
-              dz = verts[(size_t)v * 3 + 2] - M[11];
-  const float x = (dx * M[0] + dy * M[1]) + dz * M[2];
-  const float y = (dx * M[3] + dy * M[4]) + dz * M[5];
-  const float d = (dx * M[6] + dy * M[7]) + dz * M[8];
-  const float S = (float)(W > H ? W : H);
-  const float px = (x / ortho_scale) * S + 0.5f * (float)W;
-  const float py = 0.5f * (float)H - (y / ortho_scale) * S;
-  const bool ok = finite_f(px) && finite_f(py) && finite_f(d);
+  float x, y, d;
+  int X, Y;
+  const bool ok = project_point(verts + (size_t)v * 3, views + (size_t)blockIdx.y * 12, ortho_scale, W, H, x, y, d, X, Y);
   const size_t o = (size_t)blockIdx.y * V + v;
   cam[o] = v4f{x, y, d, 0.0f};
-  snapped[o] = v4i{ok ? snap(px) : 0, ok ? snap(py) : 0, ok ? 1 : 0, 0};
+  snapped[o] = v4i{X, Y, ok ? 1 : 0, 0};
 }
 
 // A face of one view ready to draw: winding normalised (A2 > 0), bounding box clipped to the image.
@@ -245,11 +216,6 @@ __global__ __launch_bounds__(256) void render_shade_kernel(const float* __restri
 }
 
 // ---- K28: the shade pass with materials and textures ------------------------------------------------------------
-struct MaterialParams {
-  RenderParams base;
-  float ambient, diffuse;
-};
-
 struct MaterialTables {
   const int* face_material;              // [F], outside [0, M): no material
   const v4f* materials;                  // [M]: Kd and the texture index (validated by the entry: -1 or in [0, T))
@@ -476,11 +442,7 @@ extern "C" int fpsg_mesh_render(const float* verts, int V, const int32_t* faces,
   FPSG_REQUIRE(ws_bytes >= L.total, FPSG_E_SHAPE, "fpsg_mesh_render: workspace of %zu bytes, %zu needed", ws_bytes,
                L.total);
   RenderParams P;
-  for (int k = 0; k < 3; ++k) {
-    P.ka[k] = params[k]; P.kd[k] = params[3 + k]; P.ks[k] = params[6 + k];
-    P.light[k] = params[9 + k]; P.bg[k] = params[12 + k];
-  }
-  P.log2_shininess = log2_shininess;
+  unpack_render_params(params, log2_shininess, P);
   hipStream_t st = static_cast<hipStream_t>(stream);
   char* base = static_cast<char*>(ws);
   v4f* cam = reinterpret_cast<v4f*>(base + L.cam);
@@ -562,12 +524,7 @@ extern "C" int fpsg_mesh_render_materials(const float* verts, int V, const int32
   FPSG_REQUIRE(ws_bytes >= LM.total, FPSG_E_SHAPE, "fpsg_mesh_render_materials: workspace of %zu bytes, %zu needed",
                ws_bytes, LM.total);
   MaterialParams Q;
-  RenderParams& P = Q.base;
-  for (int k = 0; k < 3; ++k) {
-    P.ka[k] = params[k]; P.kd[k] = params[3 + k]; P.ks[k] = params[6 + k];
-    P.light[k] = params[9 + k]; P.bg[k] = params[12 + k];
-  }
-  P.log2_shininess = log2_shininess;
+  unpack_render_params(params, log2_shininess, Q.base);
   Q.ambient = params[15]; Q.diffuse = params[16];
   hipStream_t st = static_cast<hipStream_t>(stream);
   char* base = static_cast<char*>(ws);

@@ -32,7 +32,8 @@ def default_options(**overrides) -> argparse.Namespace:
         support_factor=1.0, query_factor=1.0, intra_recon=False, num_clusters=4, ori_dim=2,
         raw_dim=3, num_nodes=4, device="cuda", bottleneck_size=1536, template_type="SQUARE",
         activation="relu", aggregate="single", pc_dist="cd", lr=1e-3, lr_decay=350, SGD=False,
-        n_way=1, n_shot=20, n_query=0, clip_grad_norm=0.0, ema_decay=0.0, **LOSS_OPTION_DEFAULTS)
+        n_way=1, n_shot=20, n_query=0, clip_grad_norm=0.0, ema_decay=0.0, sample_renderer="matplotlib", sample_up="z",
+        **LOSS_OPTION_DEFAULTS)
     for k, v in overrides.items():
         setattr(opt, k, v)
     return opt

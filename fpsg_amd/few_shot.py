@@ -381,14 +381,23 @@ class ImgPCProtoNet(nn.Module):
         pc_z = self.pc_encoder(pcs.reshape(-1, *pcs.shape[2:]).transpose(2, 1))
         return self._decode_queries(img_z, pc_z)
 
-    def draw_reconstruction(self, sample, img_path):
+    def draw_reconstruction(self, sample, img_path, renderer="matplotlib", up="z"):
         """Writes ``<dir>/<stem>.png`` (generated vs ground truth, one column per query) and
         the clouds as ``<stem>_<code>.npy`` / ``<stem>_<code>_gt.npy``.
 
         ``img_path`` is ``[stem, directory]`` as ``evaluate_Network.py:111`` passes it; a plain
         path string (what ``trainNetwork.py:183,205`` passes, which makes the reference write
-        garbage names -- SURVEY.md F10) is split into directory and stem instead."""
-        from .visualization import visualize_point_clouds, write_png
+        garbage names -- SURVEY.md F10) is split into directory and stem instead.
+
+        ``renderer="matplotlib"``: the reference's scatter panels.  ``renderer="splat"``: the PNG is
+        ``visualization.render_reconstruction``'s (K29, on the GPU): one row per query, generated left in the decoder's
+        patch colours and ground truth right, on one scale, seen by the cameras of the conditioning views for clouds
+        whose ``up`` axis is ``"z"`` or ``"y"``.  The ``.npy`` files are the same either way."""
+        from .visualization import render_reconstruction, visualize_point_clouds, write_png
+        if renderer not in ("matplotlib", "splat"):
+            raise ValueError(f"renderer must be 'matplotlib' or 'splat', got {renderer!r}")
+        if up not in ("z", "y"):
+            raise ValueError(f"up must be 'z' or 'y', got {up!r}")
         if isinstance(img_path, (str, os.PathLike)):
             directory, stem = os.path.split(os.fspath(img_path))
             stem = os.path.splitext(stem)[0]
@@ -398,8 +407,13 @@ class ImgPCProtoNet(nn.Module):
         code = int(code.reshape(-1)[0]) if torch.is_tensor(code) else int(np.ravel(code)[0])
         syn_pc = self.reconstruct(sample)
         pcq = sample["pcq"].squeeze(0)
-        panels = [visualize_point_clouds(g, pcq[i], i) for i, g in enumerate(syn_pc)]
-        write_png(os.path.join(directory, f"{stem}.png"),
-                  np.concatenate(panels, axis=1).transpose(1, 2, 0))
+        if renderer == "splat":
+            gt = pcq.reshape(-1, *pcq.shape[-2:])
+            sheet = render_reconstruction(syn_pc, gt, getattr(self.pc_decoder, "pts_per_patch", None), up=up)
+            write_png(os.path.join(directory, f"{stem}.png"), sheet)
+        else:
+            panels = [visualize_point_clouds(g, pcq[i], i) for i, g in enumerate(syn_pc)]
+            write_png(os.path.join(directory, f"{stem}.png"),
+                      np.concatenate(panels, axis=1).transpose(1, 2, 0))
         np.save(os.path.join(directory, f"{stem}_{code}.npy"), syn_pc.squeeze(0).cpu().numpy())
         np.save(os.path.join(directory, f"{stem}_{code}_gt.npy"), pcq.squeeze(0).cpu().numpy())

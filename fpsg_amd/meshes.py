@@ -2,8 +2,9 @@
 out, plus the list files that ``fpsg_amd.datasets`` reads.  The definitions of the kernels are in ``include/fpsg_hip.h``.
 
 The host part (``load_mesh``, ``load_obj_scene``, ``pack_textures``, ``normalize_mesh``, ``write_ply_points``,
-``camera_views``, ``write_modelnet_lists``, ``write_shapenet_lists``) needs no GPU.  ``sample_surface`` and
-``render_views`` run on the GPU only: a CPU tensor raises ``FpsgHipError``.
+``camera_views``, ``write_modelnet_lists``, ``write_shapenet_lists``) needs no GPU.  ``sample_surface``,
+``render_views`` and ``render_points`` (K29: views of point clouds as shaded spheres) run on the GPU only: a CPU tensor
+raises ``FpsgHipError``.
 """
 from __future__ import annotations
 
@@ -32,6 +33,8 @@ SHAPENET_TEST_CLASSES = ("02880940", "02992529", "03593526", "03797390", "032111
 RENDER_MAX_MATERIALS = 65536    # FPSG_RENDER_MAX_MATERIALS
 RENDER_MAX_TEXTURES = 4096      # FPSG_RENDER_MAX_TEXTURES
 RENDER_MAX_TEXELS = 1 << 28     # FPSG_RENDER_MAX_TEXELS
+POINTS_MAX_N = 16384            # FPSG_POINTS_MAX_N
+POINTS_MAX_RADIUS_PX = 64       # FPSG_POINTS_MAX_RADIUS_PX
 
 
 # ------------------------------------------------------------------------------------------ files
@@ -673,6 +676,108 @@ def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevatio
         _hip.check(rc, "fpsg_mesh_render")
     if return_buffers:
         return image, {"face_id": face_id, "depth": depth, "radiance": radiance}
+    return image
+
+
+# -------------------------------------------------------------------------------------------- K29
+def render_points(points: torch.Tensor, *, colors=None, size=256, elevations_deg=60.0, azimuths_deg=(0, 120, 240),
+                  radius_cam: float = 3.0, ortho_scale: float = 2.0, up: str = "z", ssaa: int = 2,
+                  point_radius: float = 0.02, background=(1.0, 1.0, 1.0), material: PhongMaterial = PhongMaterial(),
+                  views=None, return_buffers: bool = False):
+    """Orthographic Phong views of point clouds, every point a sphere of ``point_radius`` world units (K29) -> uint8
+    ``[B, n_views, H, W, 3]`` on the clouds' device.
+
+    ``points``: ``[N,3]`` (one cloud, B = 1) or ``[B,N,3]`` float32; ``colors``: uint8 of the same shape, a base colour per
+    point in place of ``material.color`` (scaled by ``material.ambient`` and ``material.diffuse``, as ``render_views``
+    does with a ``scene``).  ``size``, ``ssaa``, ``background``, ``ortho_scale``, ``up``, ``material`` and ``views`` mean
+    what they mean in ``render_views``; the camera is ``camera_views(elevations_deg, azimuths_deg, radius_cam, up)``
+    unless ``views`` gives the matrices, and every cloud is seen by all of them.  The nearest sphere wins each sample,
+    the lowest point index on equal depth.  With ``return_buffers`` also a dict: ``point_id`` int32 and ``depth`` float32
+    ``[B, n_views, H ssaa, W ssaa]`` (-1 / +inf where empty) and ``radiance`` float32 ``[B, n_views, H, W, 3]``, of which
+    the image is ``rint(clamp(radiance, 0, 1) * 255)``.  Bitwise the same on every run, and a cloud's views do not depend
+    on the batch it is rendered in.
+
+    ``ValueError`` for bad shapes and options, before any GPU work; ``FpsgHipError`` for CPU tensors."""
+    H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+    if isinstance(ssaa, bool) or int(ssaa) != ssaa or int(ssaa) not in (1, 2, 4):
+        raise ValueError(f"ssaa must be 1, 2 or 4, got {ssaa}")
+    ssaa = int(ssaa)
+    if H < 1 or W < 1 or H * ssaa > RENDER_MAX_SIZE or W * ssaa > RENDER_MAX_SIZE:
+        raise ValueError(f"size * ssaa must be from 1 to {RENDER_MAX_SIZE}, got {(H, W)} * {ssaa}")
+    if not (ortho_scale > 0 and math.isfinite(ortho_scale)):
+        raise ValueError(f"ortho_scale must be positive and finite, got {ortho_scale}")
+    if not (point_radius > 0 and math.isfinite(point_radius)):
+        raise ValueError(f"point_radius must be positive and finite, got {point_radius}")
+    RW, RH = W * ssaa, H * ssaa
+    # the entry's R, from the float32 values it is given
+    R = round(256.0 * (float(np.float32(point_radius)) / float(np.float32(ortho_scale))) * max(RW, RH))
+    if not 1 <= R <= 256 * POINTS_MAX_RADIUS_PX:
+        raise ValueError(f"point_radius {point_radius} is {R / 256.0:.6g} sample pixels, from 1/256 to "
+                         f"{POINTS_MAX_RADIUS_PX} are supported")
+    log2s = material.log2_shininess()
+    if not isinstance(points, torch.Tensor) or points.dim() not in (2, 3) or points.size(-1) != 3 or points.numel() == 0:
+        raise ValueError(f"expected [N,3] or [B,N,3] points, got {tuple(getattr(points, 'shape', ()))}")
+    points = points.detach()
+    if points.dim() == 2:
+        points = points.unsqueeze(0)
+        if isinstance(colors, torch.Tensor) and colors.dim() == 2:
+            colors = colors.unsqueeze(0)
+    B, N = points.size(0), points.size(1)
+    if N > POINTS_MAX_N:
+        raise ValueError(f"clouds of more than {POINTS_MAX_N} points are not supported (got {N})")
+    if colors is not None:
+        if not isinstance(colors, torch.Tensor) or colors.dtype != torch.uint8 or tuple(colors.shape) != (B, N, 3):
+            raise ValueError(f"colors must be a uint8 tensor {(B, N, 3)}, got {getattr(colors, 'dtype', None)} "
+                             f"{tuple(getattr(colors, 'shape', ()))}")
+        if colors.device != points.device:
+            raise ValueError(f"colors are on {colors.device}, points on {points.device}")
+    mats = camera_views(elevations_deg, azimuths_deg, radius_cam, up) if views is None else \
+        np.ascontiguousarray(np.asarray(views, dtype=np.float32).reshape(-1, 12))
+    n_views = mats.shape[0]
+    if n_views < 1:
+        raise ValueError("no views")
+    bg_img = None
+    if isinstance(background, (np.ndarray, torch.Tensor)) and background.ndim == 3:
+        bg_img = torch.as_tensor(background)
+        if bg_img.dtype != torch.uint8 or tuple(bg_img.shape) != (H, W, 3):
+            raise ValueError(f"a background image must be uint8 [{H},{W},3], got {bg_img.dtype} {tuple(bg_img.shape)}")
+        params = material.params()
+    else:
+        params = material.params(background)
+    if B * n_views >= 65536:
+        raise ValueError(f"clouds * views must be below 65536, got {B} * {n_views}")
+    points = points.contiguous()
+    _hip.dev_tensor(points, torch.float32, "points")
+    dev = points.device
+    if colors is not None:
+        colors = colors.detach().contiguous()
+    lib = _hip.load()
+    ws_bytes = lib.fpsg_points_render_workspace_bytes(B, N, n_views, RW, RH)
+    if ws_bytes == 0:
+        raise ValueError(f"unsupported render shape (B={B}, N={N}, views={n_views}, {RW}x{RH})")
+    ws = torch.empty((ws_bytes // 16, 2), dtype=torch.int64, device=dev)
+    d_views = torch.from_numpy(mats).to(dev)
+    if bg_img is not None:
+        bg_img = bg_img.to(dev).contiguous()
+    image = torch.empty((B, n_views, H, W, 3), dtype=torch.uint8, device=dev)
+    radiance = point_id = depth = None
+    if return_buffers:
+        radiance = torch.empty((B, n_views, H, W, 3), dtype=torch.float32, device=dev)
+        point_id = torch.empty((B, n_views, RH, RW), dtype=torch.int32, device=dev)
+        depth = torch.empty((B, n_views, RH, RW), dtype=torch.float32, device=dev)
+    c_params = (ctypes.c_float * 17)(*params.tolist(), float(material.ambient), float(material.diffuse))
+
+    def opt(t):
+        return None if t is None else _hip.ptr(t)
+
+    with torch.cuda.device(dev):
+        rc = lib.fpsg_points_render(_hip.ptr(points), opt(colors), B, N, _hip.ptr(d_views), n_views, RW, RH, ssaa,
+                                    float(ortho_scale), float(point_radius), c_params, log2s, opt(bg_img),
+                                    _hip.ptr(image), opt(radiance), opt(point_id), opt(depth), _hip.ptr(ws),
+                                    ws.numel() * 8, _hip.stream_of(points))
+    _hip.check(rc, "fpsg_points_render")
+    if return_buffers:
+        return image, {"point_id": point_id, "depth": depth, "radiance": radiance}
     return image
 
 

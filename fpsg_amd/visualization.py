@@ -4,6 +4,10 @@ Mirrors reference ``src/models/visualization.py:9-28`` (``visualize_point_clouds
 figure (6x3 in, two 3-D axes, titles ``Sample: i`` / ``Ground Truth: i``, marker size 5),
 returned as ``[4, H, W]`` RGBA like the reference's renderer buffer.  PNG writing uses PIL
 (``imageio``, which the reference imports, is not needed).  Host-side only.
+
+``render_reconstruction`` is the same comparison drawn on the GPU (K29, ``meshes.render_points``): shaded spheres seen by
+the cameras of the conditioning views, both clouds on one scale, the generated one in the colours of the decoder's
+patches (``patch_colors``).
 """
 from __future__ import annotations
 
@@ -26,6 +30,52 @@ def visualize_point_clouds(pts, gtr, idx, pert_order=(0, 1, 2)):
     img = np.asarray(fig.canvas.buffer_rgba()).copy()
     plt.close(fig)
     return np.transpose(img, (2, 0, 1))
+
+
+# 16 colours for the decoder's patches, far apart in hue and of similar lightness (fixed: images stay comparable)
+PATCH_PALETTE = np.array([
+    [230, 25, 75], [60, 180, 75], [255, 225, 25], [0, 130, 200], [245, 130, 48], [145, 30, 180], [70, 240, 240],
+    [240, 50, 230], [210, 245, 60], [250, 190, 212], [0, 128, 128], [220, 190, 255], [170, 110, 40], [128, 0, 0],
+    [170, 255, 195], [0, 0, 128]], dtype=np.uint8)
+GREY = (204, 204, 204)            # PhongMaterial's default colour 0.8 as a byte
+
+
+def patch_colors(n_points: int, pts_per_patch: int) -> np.ndarray:
+    """``[n_points, 3]`` uint8: point ``i`` takes the colour of its patch ``i // pts_per_patch`` from the 16-entry
+    ``PATCH_PALETTE``, which repeats beyond 16 patches."""
+    if isinstance(n_points, bool) or int(n_points) != n_points or int(n_points) < 1:
+        raise ValueError(f"n_points must be a positive integer, got {n_points}")
+    if isinstance(pts_per_patch, bool) or int(pts_per_patch) != pts_per_patch or int(pts_per_patch) < 1:
+        raise ValueError(f"pts_per_patch must be a positive integer, got {pts_per_patch}")
+    patch = np.arange(int(n_points)) // int(pts_per_patch)
+    return PATCH_PALETTE[patch % len(PATCH_PALETTE)]
+
+
+def render_reconstruction(syn_pc, gt_pc, pts_per_patch=None, up="z", size=192):
+    """Generated against ground-truth clouds as shaded spheres (K29, ``meshes.render_points``) -> uint8
+    ``[Q * size, 2 * n_views * size, 3]``: one row per query; left the generated cloud's three views (elevation 60,
+    azimuths 0, 120, 240: the cameras of the conditioning views), coloured by decoder patch when ``pts_per_patch``
+    divides its point count and grey otherwise; right the ground truth's views in grey.  Camera, scale and point radius
+    are the same for both, so the two halves are on one scale.  ``syn_pc`` ``[Q,N,3]`` and ``gt_pc`` ``[Q,M,3]`` on a
+    GPU; ``ValueError`` for anything else about their shapes."""
+    import torch
+    from . import meshes
+    if not (isinstance(syn_pc, torch.Tensor) and isinstance(gt_pc, torch.Tensor) and syn_pc.dim() == 3 and
+            gt_pc.dim() == 3 and syn_pc.size(2) == 3 and gt_pc.size(2) == 3 and syn_pc.size(0) == gt_pc.size(0)):
+        raise ValueError(f"expected [Q,N,3] and [Q,M,3] clouds, got {tuple(getattr(syn_pc, 'shape', ()))} and "
+                         f"{tuple(getattr(gt_pc, 'shape', ()))}")
+    Q, N = syn_pc.size(0), syn_pc.size(1)
+    syn_pc, gt_pc = syn_pc.detach().float().contiguous(), gt_pc.detach().float().contiguous()
+    grey = torch.tensor(GREY, dtype=torch.uint8, device=syn_pc.device)
+    if pts_per_patch and N % int(pts_per_patch) == 0:
+        colors = torch.from_numpy(patch_colors(N, int(pts_per_patch))).to(syn_pc.device).expand(Q, N, 3).contiguous()
+    else:
+        colors = grey.expand(Q, N, 3).contiguous()
+    halves = [meshes.render_points(syn_pc, colors=colors, size=size, up=up),
+              meshes.render_points(gt_pc, colors=grey.expand(Q, gt_pc.size(1), 3).contiguous(), size=size, up=up)]
+    rows = [h.permute(0, 2, 1, 3, 4).reshape(Q, h.size(2), -1, 3) for h in halves]      # [Q, H, n_views W, 3]
+    sheet = torch.cat(rows, dim=2).reshape(Q * rows[0].size(1), -1, 3)
+    return sheet.cpu().numpy()
 
 
 def write_png(path: str, hwc: np.ndarray) -> None:

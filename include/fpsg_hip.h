@@ -1303,6 +1303,49 @@ int fpsg_mesh_render_materials(const float* verts, int V, const int32_t* faces, 
                                const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* face_id, float* depth,
                                void* ws, size_t ws_bytes, fpsg_stream_t stream);
 
+/* ---- K29: orthographic Phong views of point clouds, every point a small sphere ---------------------
+ * Shows what the model generates with the cameras of the views it was conditioned on: B clouds in one call, each seen
+ * by all the views, with occlusion, shading and an optional colour per point.  Every argument it shares with
+ * fpsg_mesh_render means what it means there.
+ * points [B,N,3] fp32; colors [B,N,3] uint8 or NULL; views [n_views,12] as K27; W x H the SAMPLE resolution, ssaa (1, 2
+ * or 4) a divisor of both; ortho_scale and radius in world units; params (HOST pointer, 17 floats) in K28's layout:
+ * ka[3], kd[3], ks[3], l[3], bg[3], ambient, diffuse; bg_image optional, as K27, shared by the clouds and the views.
+ * Outputs, any may be NULL, not all: image (uint8) and radiance (fp32) [B, n_views, H/ssaa, W/ssaa, 3]; point_id (int32,
+ * -1 = empty) and depth (fp32, +inf = empty) [B, n_views, H, W].
+ * All of the following in fp32 with every operation rounded on its own (no fma), divisions and sqrt correctly rounded.
+ * Project, per point, view and cloud: K27's vertex projection, which gives the snapped integers X, Y and the depth z.  A
+ *   point whose px, py or z is not finite is invalid and draws nothing.
+ * Radius in snapped units, by the entry on the host in double:
+ *   R = llrint(256 (radius / ortho_scale) max(W, H));  R < 1 or R > 256 FPSG_POINTS_MAX_RADIUS_PX is refused.
+ * Cover, at the sample centre P = (256 i + 128, 256 j + 128): dx = Px - X; dy = Py - Y; q = dx dx + dy dy in int64.  The
+ *   sample is covered iff q < R R: strict and in integers, so there is no rounding and no tie rule.
+ * Depth of the sphere at the sample: t = (float) q / (float) (R R);  c = sqrt(1 - t);  z_s = z - radius c.  (When t
+ *   rounds to 1, c is 0.)  A sample with z_s not finite is dropped.
+ * Z-buffer: per sample the minimum of (key(z_s) << 32) | point index, key as K27: the nearest sphere wins, the lowest
+ *   point index on equal depth, whatever the order of the launches.
+ * Shade, per covered sample, from the winner's X, Y and the sample centre: the normal in the camera frame is
+ *   nx = (float) dx / (float) R;  ny = -((float) dy / (float) R);  nz = -c, not renormalised.  ndl, diff, spec and the
+ *   squaring as K27 with that n.  Without colors: colour_c = (ka_c + kd_c diff) + ks_c spec.  With colors: the base
+ *   colour is b_c = (float) byte_c / 255, and a_c = ambient b_c;  d_c = diffuse b_c;  colour_c = (a_c + d_c diff) +
+ *   ks_c spec, as K28 forms it from a base colour.
+ * Resolve and image: K27's, per cloud and view.
+ * Workspace: fpsg_points_render_workspace_bytes = 16 B n_views N bytes (16-byte aligned): one record per (cloud, view,
+ * point).  There is no z-buffer in memory.
+ * Errors, all before any launch or copy: FPSG_E_SHAPE for B, N, n_views, W or H < 1, ssaa not 1, 2 or 4 or not a divisor
+ * of W and H, an ortho_scale or radius not positive and finite, R out of range, log2_shininess outside
+ * 0..FPSG_RENDER_MAX_LOG2_SHININESS, a workspace too small; FPSG_E_LIMIT for N > FPSG_POINTS_MAX_N, W or H >
+ * FPSG_RENDER_MAX_SIZE, n_views > FPSG_RENDER_MAX_VIEWS or B n_views >= 65536; FPSG_E_NULL for a null points, views,
+ * params or ws, or no output at all; FPSG_E_ALIGN for a misaligned pointer.  fpsg_points_render_workspace_bytes returns
+ * 0 for a refused shape.
+ */
+#define FPSG_POINTS_MAX_N 16384
+#define FPSG_POINTS_MAX_RADIUS_PX 64
+size_t fpsg_points_render_workspace_bytes(int B, int N, int n_views, int W, int H);
+int fpsg_points_render(const float* points, const uint8_t* colors, int B, int N, const float* views, int n_views, int W,
+                       int H, int ssaa, float ortho_scale, float radius, const float* params, int log2_shininess,
+                       const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* point_id, float* depth,
+                       void* ws, size_t ws_bytes, fpsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

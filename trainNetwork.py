@@ -79,6 +79,8 @@ def main(opt):
     checkpoint_path = os.path.join(opt.model_path, opt.name)
     checkpoint_imgs = os.path.join(checkpoint_path, "images")
     checkpoint_logs = os.path.join(checkpoint_path, f"log_{timestamp}.txt")
+    # how the sample images are drawn (an older namespace without the two options: the reference's panels)
+    drawing = {"renderer": getattr(opt, "sample_renderer", "matplotlib"), "up": getattr(opt, "sample_up", "z")}
     if is_main:
         os.makedirs(checkpoint_imgs, exist_ok=True)
 
@@ -224,7 +226,7 @@ def main(opt):
             for sample in dl_test if is_main else ():
                 model.eval()
                 model.draw_reconstruction(to_device(sample, device),
-                                          os.path.join(checkpoint_imgs, f"sample_img_{epoch}_test.png"))
+                                          os.path.join(checkpoint_imgs, f"sample_img_{epoch}_test.png"), **drawing)
                 model.train()
                 break
 
@@ -246,7 +248,7 @@ def main(opt):
             model.eval()
             for sample in dl:
                 model.draw_reconstruction(to_device(sample, device),
-                                          os.path.join(checkpoint_imgs, f"sample_img_{epoch}.png"))
+                                          os.path.join(checkpoint_imgs, f"sample_img_{epoch}.png"), **drawing)
                 break
             model.train()
         if world > 1:
