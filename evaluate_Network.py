@@ -46,7 +46,7 @@ def main(opt):
     checkpoint_path = os.path.join(opt.model_path, opt.name)
     os.makedirs(os.path.join(checkpoint_path, "images"), exist_ok=True)
 
-    _, ds_test = cli.build_datasets(opt, n_query, device)
+    _, ds_test = cli.build_datasets(opt, n_query, device, views=False)     # view 0, no jitter, whatever --n_views says
     _, dl_test = cli.build_loaders(opt, ds_test, ds_test)
 
     model = build_model(opt)

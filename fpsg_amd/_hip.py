@@ -252,6 +252,8 @@ SIGNATURES = {
     "fpsg_points_render": [_c_f32p, ctypes.c_void_p, _c_int, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_int,
                            ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_float), _c_int, ctypes.c_void_p,
                            ctypes.c_void_p, _c_f32p, _c_i32p, _c_f32p, ctypes.c_void_p, ctypes.c_size_t, _c_stream],
+    "fpsg_episode_views": [ctypes.c_void_p, _c_int, _c_int, _c_int, _c_i32p, _c_int, _c_i32p, _c_f32p, _c_f32p, _c_int,
+                           _c_int, _c_stream],
 }
 _RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_grad_norm_workspace_bytes": ctypes.c_size_t,
 "fpsg_chamfer_workspace_bytes": ctypes.c_size_t,

@@ -10,7 +10,9 @@ working).  ``--sequential_eval`` is declared with ``store_true``: the reference'
 Additions (all optional): ``--synthetic`` (file-free corpora of the reference's shapes),
 ``--episodes_per_step`` (episodes per optimizer step across all ranks; data-parallel under
 ``torchrun``), ``--img_encoder_path`` (local VGG16-BN weights; nothing is downloaded),
-``--resident`` (keep the corpora in HBM, assemble episodes on the device), ``--exact_emd`` (evaluation: the exact
+``--resident`` (keep the corpora in HBM, assemble episodes on the device), ``--n_views N`` with ``--view_jitter J`` /
+``--view_color_jitter C`` (training on all rendered views of the file-backed corpora: uint8 view corpora, a view, a crop
+window and a colour jitter drawn per image, decoded on the GPU by K30, ``fpsg_amd.views``), ``--exact_emd`` (evaluation: the exact
 EMD per class beside the two reference metrics), ``--set_metrics`` (evaluation: MMD, COV and 1-NNA under the Chamfer
 distance per class, over the class's generated and reference query clouds), ``--set_metrics_emd`` (the same under the
 exact EMD), ``--set_metrics_points N`` (evaluation: the clouds of the two set metrics reduced to N points each by farthest
@@ -76,6 +78,17 @@ def few_shot_parser(evaluation: bool = False) -> argparse.ArgumentParser:
     g.add_argument("--n_shot", type=int, default=20)
     g.add_argument("--n_query", type=int, default=0, help="Number of Query set [default: --n_shot];")
     g.add_argument("--resident", action="store_true", help="Keep corpora on the GPU (synthetic mode);")
+    g.add_argument("--n_views", type=int, default=1, metavar="N",
+                   help="Training: views kept per item, a random one per image and episode; 0 = all views found "
+                        "[default: 1 = the first view only, as the reference].  The views are kept as uint8 pixels and "
+                        "become the encoder's floats on the GPU (K30); evaluation always reads the first view;")
+    g.add_argument("--view_jitter", type=float, default=0.0, metavar="J",
+                   help="Training: a random square window per image, its side 1-J .. 1+J of the image's and its centre up "
+                        "to J/2 of the side off the middle, resampled to the image's size (clamp to edge), J in "
+                        "[0, 0.5) [default: 0 = off];")
+    g.add_argument("--view_color_jitter", type=float, default=0.0, metavar="C",
+                   help="Training: contrast and saturation 1-C .. 1+C and brightness -C/4 .. C/4 per image, C in [0, 1) "
+                        "[default: 0 = off];")
 
     g = p.add_argument_group("network")
     g.add_argument("--img_encoder", type=str, default="vgg_16")
@@ -198,6 +211,17 @@ def _uniform_percent(opt) -> None:
     opt.uniform_percentages = uniform_fractions(opt.uniform_percent)       # what the model takes
 
 
+def multi_view(opt) -> bool:
+    """Whether training reads the multi-view datasets (``fpsg_amd.views``): any of ``--n_views``, ``--view_jitter``,
+    ``--view_color_jitter`` away from its default.  ``ValueError`` for a bad value or a combination with ``--synthetic``;
+    a namespace from before the options: False."""
+    if getattr(opt, "n_views", None) is None:
+        return False
+    from .views import check_view_options
+    return check_view_options(opt.n_views, getattr(opt, "view_jitter", 0.0), getattr(opt, "view_color_jitter", 0.0),
+                              synthetic=bool(opt.synthetic))
+
+
 # validate()'s option checks in the order they run: (the attribute without which -- an older namespace -- the check is
 # skipped, the check: ValueError for a bad value, what goes in front of its message)
 _CHECKS = (
@@ -213,6 +237,7 @@ _CHECKS = (
     ("uniform_weight", _uniform_percent, "--uniform_percent: "),
     ("uniform_weight", lambda o: check_uniform_options(o.uniform_percentages, o.uniform_radius), "--uniform_"),
     ("ema_decay", lambda o: check_ema_decay(o.ema_decay), "--"),
+    ("n_views", multi_view, "--"),
 )
 
 
@@ -231,8 +256,11 @@ def validate(opt) -> None:
     eval_report.check(opt)          # the evaluation report's options; a training namespace has none of them
 
 
-def build_datasets(opt, n_query: int, device):
-    """(train, test) datasets with the reference's item layout."""
+def build_datasets(opt, n_query: int, device, views: bool = True):
+    """(train, test) datasets with the reference's item layout.  With ``--n_views`` other than 1 or a view jitter the
+    training dataset is the multi-view one (``fpsg_amd.views``: uint8 images and their tables, ``views.decode_episode``
+    after the upload); the test dataset is always the default one.  ``views=False`` (evaluation): the three options are
+    ignored."""
     if opt.synthetic:
         where = device if opt.resident else "cpu"
         need = opt.n_shot + max(n_query, 1)
@@ -246,8 +274,15 @@ def build_datasets(opt, n_query: int, device):
         cls, tfs = FewShotModelNet, modelnet_transform()
     else:
         cls, tfs = FewShotShapeNet, shapenet_transform()
-    ds = cls(opt.config_path, opt.refer_path, n_classes=opt.n_way, n_support=opt.n_shot,
-             n_query=n_query, transform=tfs)
+    if views and multi_view(opt):
+        from .views import MultiViewModelNet, MultiViewShapeNet
+        many = MultiViewModelNet if opt.dataset == "modelnet" else MultiViewShapeNet
+        ds = many(opt.config_path, opt.refer_path, n_classes=opt.n_way, n_support=opt.n_shot, n_query=n_query,
+                  transform=tfs, n_views=opt.n_views, view_jitter=opt.view_jitter,
+                  view_color_jitter=opt.view_color_jitter)
+    else:
+        ds = cls(opt.config_path, opt.refer_path, n_classes=opt.n_way, n_support=opt.n_shot,
+                 n_query=n_query, transform=tfs)
     ds_test = cls(opt.test_path, opt.refer_path, n_classes=opt.n_way, n_support=opt.n_shot,
                   n_query=n_query, transform=tfs)
     return ds, ds_test

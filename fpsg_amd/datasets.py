@@ -69,6 +69,18 @@ class ImageTransform:
         arr = np.asarray(img, dtype=np.float32) / 255.0
         return torch.from_numpy((arr - 0.5) / 0.5).permute(2, 0, 1).contiguous()
 
+    def to_uint8(self, img: Image.Image) -> np.ndarray:
+        """The uint8 ``[H, W, 3]`` pixels ``__call__`` converts to floats: the same crop and resize, nothing after them
+        (``fpsg_amd.views`` keeps corpora in this form and converts on the GPU, K30)."""
+        w, h = img.size
+        left, top = int(round((w - self.crop) / 2.0)), int(round((h - self.crop) / 2.0))
+        img = img.crop((left, top, left + self.crop, top + self.crop))
+        if w < h:
+            new = (self.size, max(1, int(self.size * img.size[1] / img.size[0])))
+        else:
+            new = (max(1, int(self.size * img.size[0] / img.size[1])), self.size)
+        return np.array(img.resize(new, Image.BILINEAR), dtype=np.uint8)
+
 
 def modelnet_transform() -> ImageTransform:
     return ImageTransform(550)

@@ -1346,6 +1346,45 @@ int fpsg_points_render(const float* points, const uint8_t* colors, int B, int N,
                        const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* point_id, float* depth,
                        void* ws, size_t ws_bytes, fpsg_stream_t stream);
 
+/* ---- K30: the uint8 views of an episode -> the float32 batch the image encoder reads ----------------
+ * One launch selects, resamples, colour-jitters and normalises the images of an episode.  All pointers are device
+ * memory.
+ * src [n_src,Hs,Ws,3] uint8, HWC as PIL gives it; sel [n] int32: the source image of output image k, entries may repeat
+ * and come in any order; geom [n,4] int32 = (x0, y0, step, 0) in 1/256 source pixel, or NULL for the identity
+ * (0, 0, 256); color [n,4] fp32 = (brightness, contrast, saturation, 0), or NULL for no photometric step;
+ * out [n,3,Ho,Wo] fp32.
+ * Sample position.  For output pixel (i, j), column i < Wo and row j < Ho:
+ *   X = x0 + i*step, Y = y0 + j*step, as int32.  The entry refuses shapes and the wrapper values where these could
+ *   overflow: |x0|, |y0| <= 2^24, 1 <= step <= 2^16, Ho, Wo <= 8192; the kernel clamps x0, y0 and step to those ranges.
+ *   ix = X >> 8 (arithmetic shift, a floor), fx = X & 255.  The same for y.
+ *   The taps ix, ix+1, iy, iy+1 are clamped to the image (clamp to edge): ix0 = min(max(ix, 0), Ws-1),
+ *   ix1 = min(max(ix+1, 0), Ws-1), and so for the rows.
+ * Blend.  Integer bilinear blend per channel, p the uint8 pixel:
+ *   a_r = p[r][ix0]*(256-fx) + p[r][ix1]*fx for the two rows r.
+ *   v = a_0*(256-fy) + a_1*fy.
+ *   v is an integer in [0, 255*65536], below 2^24, so (float)v is exact.
+ *   x = (float)v / 16711680.0f, a correctly rounded division.
+ *   At fx = fy = 0 this equals p / 255.0f bit for bit.
+ * Photometric step, only when color is not NULL.  It is applied always then, also at (0,1,1), in fp32 and in this order,
+ * every operation rounded on its own (no fma), br = brightness, c = contrast, s = saturation:
+ *   l = (0.299f*r + 0.587f*g) + 0.114f*b.
+ *   Per channel t = l + s*(x - l).
+ *   u = (t - 0.5f)*c + (0.5f + br).
+ *   u = min(max(u, 0), 1).
+ * Output.  y = (x_or_u - 0.5f) / 0.5f.
+ * Bad sel entry.  An entry outside [0, n_src) yields an image of quiet NaNs; src is not read for it.
+ * Errors, all before any HIP call: FPSG_E_SHAPE for n_src, Hs, Ws, n, Ho or Wo < 1; FPSG_E_LIMIT for Hs, Ws, Ho or Wo >
+ * FPSG_VIEWS_MAX_SIZE or n > FPSG_VIEWS_MAX_IMAGES; FPSG_E_NULL for a null src, sel or out; FPSG_E_ALIGN for a sel,
+ * geom, color or out that is not 4-byte aligned.  geom is device memory: the range of x0, y0 and step is checked by the
+ * Python wrapper on the host copy before the upload, and clamped in the kernel.
+ */
+#define FPSG_VIEWS_MAX_SIZE 8192
+#define FPSG_VIEWS_MAX_IMAGES 65535
+#define FPSG_VIEWS_MAX_OFFSET (1 << 24)
+#define FPSG_VIEWS_MAX_STEP (1 << 16)
+int fpsg_episode_views(const uint8_t* src, int n_src, int Hs, int Ws, const int32_t* sel, int n, const int32_t* geom,
+                       const float* color, float* out, int Ho, int Wo, fpsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

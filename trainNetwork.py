@@ -10,7 +10,10 @@ gradients are averaged with an RCCL all-reduce; the BatchNorm buffers of the ran
 evaluation or a save (``fpsg_amd.dist.BufferSync``); every rank evaluates a shard of the test items; rank 0 logs and
 saves).  ``--ema_decay D`` keeps an exponential moving average of the weights (``fpsg_amd.ema``, K23): every evaluation
 is followed by one of the averaged weights on the same test items (``[EMA] `` lines), ``model_epoch_N_ema.pt`` is saved
-beside ``model_epoch_N.pt`` and the sidecar gains an ``"ema"`` entry.
+beside ``model_epoch_N.pt`` and the sidecar gains an ``"ema"`` entry.  ``--n_views N`` / ``--view_jitter J`` /
+``--view_color_jitter C`` train on all rendered views of the file-backed corpora (``fpsg_amd.views``, K30): episodes
+arrive as uint8 images with their tables and become the usual sample dict right after the upload; the evaluation is the
+default one.
 
     python trainNetwork.py --synthetic --n_shot 1 --n_query 1 --epoch 2 --n_episode 10 \
         --pc_encoder_path tests/golden/pretrained_pcencoder_pointnet.pt --model_path /tmp/ckpt
@@ -27,7 +30,7 @@ from collections import defaultdict
 
 import torch
 
-from fpsg_amd import cli, winograd
+from fpsg_amd import cli, views, winograd
 from fpsg_amd import dist as fdist
 from fpsg_amd.engine import TrainStep, build_model, build_optimizer, to_device
 from fpsg_amd.episodes import EpisodePrefetcher
@@ -159,6 +162,8 @@ def main(opt):
     for epoch in range(start_epoch, opt.epoch + 1):
         # every rank draws its own episodes; different seeds per (epoch, rank)
         torch.manual_seed(1000003 * epoch + rank)
+        if hasattr(ds, "seed_views"):       # --n_views / --view_jitter / --view_color_jitter: their own generator
+            ds.seed_views(1000003 * epoch + rank)
         sums = torch.zeros(2 + len(REGULARISERS), dtype=torch.float64, device=device)    # query, support, the regularisers
         n_steps = max(1, opt.n_episode // eps_per_step)
         # exactly the episodes this rank uses (the worker must not draw one more from the global RNG: the
@@ -170,7 +175,7 @@ def main(opt):
                 local = []
                 for _ in range(local_n):
                     try:
-                        local.append(to_device(next(it), device))
+                        local.append(views.decode_episode(to_device(next(it), device)))    # uint8 views -> floats (K30)
                     except StopIteration:
                         raise RuntimeError(
                             f"the loader ran out of episodes: --n_episode {opt.n_episode} gives this rank "
@@ -247,7 +252,7 @@ def main(opt):
         if is_main and epoch % opt.sample_interval == 0:
             model.eval()
             for sample in dl:
-                model.draw_reconstruction(to_device(sample, device),
+                model.draw_reconstruction(views.decode_episode(to_device(sample, device)),
                                           os.path.join(checkpoint_imgs, f"sample_img_{epoch}.png"), **drawing)
                 break
             model.train()
