@@ -248,6 +248,13 @@ SIGNATURES = {
                                    _c_f32p, _c_int, _c_int, _c_int, _c_int, ctypes.c_float,
                                    ctypes.POINTER(ctypes.c_float), _c_int, ctypes.c_void_p, ctypes.c_void_p, _c_f32p,
                                    _c_i32p, _c_f32p, ctypes.c_void_p, ctypes.c_size_t, _c_stream],
+    "fpsg_mesh_vertex_normals": [_c_f32p, _c_int, _c_int, _c_i32p, _c_int, _c_i32p, _c_i32p, _c_int, _c_f32p, _c_stream],
+    "fpsg_mesh_render_smooth_workspace_bytes": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int],
+    "fpsg_mesh_render_smooth": [_c_f32p, _c_int, _c_i32p, _c_int, _c_i32p, _c_f32p, _c_f32p,
+                                ctypes.POINTER(ctypes.c_float), _c_int, ctypes.POINTER(ctypes.c_int32), _c_int,
+                                ctypes.c_void_p, ctypes.c_longlong, _c_f32p, _c_int, _c_int, _c_int, _c_int,
+                                ctypes.c_float, ctypes.POINTER(ctypes.c_float), _c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                _c_f32p, _c_i32p, _c_f32p, ctypes.c_void_p, ctypes.c_size_t, _c_stream],
     "fpsg_points_render_workspace_bytes": [_c_int, _c_int, _c_int, _c_int, _c_int],
     "fpsg_points_render": [_c_f32p, ctypes.c_void_p, _c_int, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_int,
                            ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_float), _c_int, ctypes.c_void_p,
@@ -269,6 +276,7 @@ _RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_grad_norm_workspace_bytes
              "fpsg_mesh_cdf_workspace_bytes": ctypes.c_size_t,
              "fpsg_mesh_render_workspace_bytes": ctypes.c_size_t,
              "fpsg_mesh_render_materials_workspace_bytes": ctypes.c_size_t,
+             "fpsg_mesh_render_smooth_workspace_bytes": ctypes.c_size_t,
              "fpsg_points_render_workspace_bytes": ctypes.c_size_t}
 
 _lib = None

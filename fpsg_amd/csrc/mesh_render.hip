@@ -11,6 +11,8 @@
 //   * render_shade_kernel: one output pixel per thread: its ssaa^2 samples shaded and composited over the background.
 // K28 (fpsg_mesh_render_materials) runs the same three kernels and then render_shade_materials_kernel, K27's shade
 // pass with a base colour per face: a material's Kd, or its texture looked up at the sample's interpolated uv.
+// K31b (fpsg_mesh_render_smooth) is K28 with the light's terms taken from a normal interpolated between the face's three
+// corner normals (the SMOOTH instantiation of the same shade kernel) in place of the face's own.
 #include "render_common.h"
 
 namespace fpsg {
@@ -258,11 +260,39 @@ __device__ __forceinline__ void texel_lookup(const unsigned char* __restrict__ t
   r = c[0]; g = c[1]; b = c[2];
 }
 
+// K28's barycentrics of the sample centre (i, j) in a drawn face, from the snapped corners; swap: the rasteriser's
+// exchange of corners 1 and 2 (A2 < 0) was applied, and what is interpolated must exchange with them.
+struct Bary {
+  float l0, l1, l2;
+  bool swap;
+};
+
+__device__ __forceinline__ Bary sample_bary(const v4i* __restrict__ snap_v, int ia, int ib, int ic, int i, int j) {
+  const v4i s0 = snap_v[ia];
+  v4i s1 = snap_v[ib], s2 = snap_v[ic];
+  i64 A2 = (i64)(s1.x - s0.x) * (i64)(s2.y - s0.y) - (i64)(s1.y - s0.y) * (i64)(s2.x - s0.x);
+  Bary r;
+  r.swap = A2 < 0;
+  if (r.swap) {
+    const v4i s = s1; s1 = s2; s2 = s;
+    A2 = -A2;
+  }
+  const int px = 256 * i + 128, py = 256 * j + 128;
+  const float A = (float)A2;                           // not 0: the face was drawn
+  r.l0 = (float)edge_fn(s1.x, s1.y, s2.x, s2.y, px, py) / A;
+  r.l1 = (float)edge_fn(s2.x, s2.y, s0.x, s0.y, px, py) / A;
+  r.l2 = (float)edge_fn(s0.x, s0.y, s1.x, s1.y, px, py) / A;
+  return r;
+}
+
+// SMOOTH (K31b): the light's terms from the normal interpolated between face_normals [F,3,3], which K28 does not read
+template <bool SMOOTH>
 __global__ __launch_bounds__(256) void render_shade_materials_kernel(
     const float* __restrict__ verts, const int* __restrict__ faces, int V, const float* __restrict__ views,
     const v4i* __restrict__ snapped, const u64* __restrict__ zbuf, int W, int H, int ssaa, MaterialParams Q,
-    MaterialTables T, const unsigned char* __restrict__ bg_img, unsigned char* __restrict__ image,
-    float* __restrict__ radiance, int* __restrict__ face_id, float* __restrict__ depth) {
+    MaterialTables T, const float* __restrict__ face_normals, const unsigned char* __restrict__ bg_img,
+    unsigned char* __restrict__ image, float* __restrict__ radiance, int* __restrict__ face_id,
+    float* __restrict__ depth) {
   const RenderParams& P = Q.base;
   const int ow = W / ssaa, oh = H / ssaa;
   const int ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -301,6 +331,27 @@ __global__ __launch_bounds__(256) void render_shade_materials_kernel(
       if (len > 0.0f && finite_f(len)) { nx = nx / len; ny = ny / len; nz = nz / len; }
       else { nx = 0.0f; ny = 0.0f; nz = -1.0f; }
       if (nz > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
+      Bary L = {0.0f, 0.0f, 0.0f, false};
+      if constexpr (SMOOTH) {
+        // the corner normals interpolated in world space, turned into the camera frame like the edges, normalised,
+        // and put on the side of the face that the camera sees; without a usable length the face's own normal stays
+        L = sample_bary(snap_v, ia, ib, ic, i, j);
+        const float* q = face_normals + (size_t)f * 9;
+        const float* q1 = L.swap ? q + 6 : q + 3;
+        const float* q2 = L.swap ? q + 3 : q + 6;
+        const float mx = (L.l0 * q[0] + L.l1 * q1[0]) + L.l2 * q2[0];
+        const float my = (L.l0 * q[1] + L.l1 * q1[1]) + L.l2 * q2[1];
+        const float mz = (L.l0 * q[2] + L.l1 * q1[2]) + L.l2 * q2[2];
+        float cx = (mx * M[0] + my * M[1]) + mz * M[2], cy = (mx * M[3] + my * M[4]) + mz * M[5],
+              cz = (mx * M[6] + my * M[7]) + mz * M[8];
+        const float mlen = __builtin_sqrtf((cx * cx + cy * cy) + cz * cz);
+        if (mlen > 0.0f && finite_f(mlen)) {
+          cx = cx / mlen; cy = cy / mlen; cz = cz / mlen;
+          const float side = (cx * nx + cy * ny) + cz * nz;
+          if (side < 0.0f) { cx = -cx; cy = -cy; cz = -cz; }
+          nx = cx; ny = cy; nz = cz;
+        }
+      }
       const float ndl = (nx * P.light[0] + ny * P.light[1]) + nz * P.light[2];
       const float diff = __builtin_fmaxf(ndl, 0.0f);
       float spec = ndl > 0.0f ? __builtin_fmaxf(P.light[2] - (2.0f * ndl) * nz, 0.0f) : 0.0f;
@@ -320,22 +371,13 @@ __global__ __launch_bounds__(256) void render_shade_materials_kernel(
         const float* q = T.face_uv + (size_t)f * 6;
         float u0 = q[0], v0 = q[1], u1 = q[2], v1 = q[3], u2 = q[4], v2 = q[5];
         if (finite_f(u0) && finite_f(v0) && finite_f(u1) && finite_f(v1) && finite_f(u2) && finite_f(v2)) {
-          const v4i s0 = snap_v[ia];
-          v4i s1 = snap_v[ib], s2 = snap_v[ic];
-          i64 A2 = (i64)(s1.x - s0.x) * (i64)(s2.y - s0.y) - (i64)(s1.y - s0.y) * (i64)(s2.x - s0.x);
-          if (A2 < 0) {                                // the rasteriser's swap, and the uv with the corners
-            const v4i s = s1; s1 = s2; s2 = s;
+          if constexpr (!SMOOTH) L = sample_bary(snap_v, ia, ib, ic, i, j);
+          if (L.swap) {                                // the rasteriser's swap, and the uv with the corners
             float t = u1; u1 = u2; u2 = t;
             t = v1; v1 = v2; v2 = t;
-            A2 = -A2;
           }
-          const int px = 256 * i + 128, py = 256 * j + 128;
-          const float A = (float)A2;                   // not 0: the face was drawn
-          const float l0 = (float)edge_fn(s1.x, s1.y, s2.x, s2.y, px, py) / A;
-          const float l1 = (float)edge_fn(s2.x, s2.y, s0.x, s0.y, px, py) / A;
-          const float l2 = (float)edge_fn(s0.x, s0.y, s1.x, s1.y, px, py) / A;
-          const float u = (l0 * u0 + l1 * u1) + l2 * u2;
-          const float v = (l0 * v0 + l1 * v1) + l2 * v2;
+          const float u = (L.l0 * u0 + L.l1 * u1) + L.l2 * u2;
+          const float v = (L.l0 * v0 + L.l1 * v1) + L.l2 * v2;
           const int* e = T.tex_table + (size_t)tex * 3;
           texel_lookup(T.texels + (size_t)e[0] * 3, e[1], e[2], u, v, b0, b1, b2);
         }
@@ -474,55 +516,62 @@ extern "C" size_t fpsg_mesh_render_materials_workspace_bytes(int V, int F, int n
   return material_ws(render_ws(V, F, n_views, W, H), M, T).total;
 }
 
-extern "C" int fpsg_mesh_render_materials(const float* verts, int V, const int32_t* faces, int F,
-                                          const int32_t* face_material, const float* face_uv, const float* materials,
-                                          int M, const int32_t* tex_table, int T, const uint8_t* texels,
-                                          long long n_texels, const float* views, int n_views, int W, int H, int ssaa,
-                                          float ortho_scale, const float* params, int log2_shininess,
-                                          const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* face_id,
-                                          float* depth, void* ws, size_t ws_bytes, fpsg_stream_t stream) {
-  using namespace fpsg;
+namespace fpsg {
+namespace {
+
+#define RENDER_REQUIRE_PTR(p)                                                                      \
+  do {                                                                                             \
+    FPSG_REQUIRE((p) != nullptr, FPSG_E_NULL, "%s: null pointer '%s'", fn, #p);                    \
+    FPSG_REQUIRE(!misaligned4(p), FPSG_E_ALIGN, "%s: '%s' not 4-byte aligned", fn, #p);            \
+  } while (0)
+
+// K28's entry and K31b's: the same checks, workspace and launches; smooth selects the shade pass that reads face_normals
+int render_materials_entry(const char* fn, bool smooth, const float* verts, int V, const int32_t* faces, int F,
+                           const int32_t* face_material, const float* face_uv, const float* face_normals,
+                           const float* materials, int M, const int32_t* tex_table, int T, const uint8_t* texels,
+                           long long n_texels, const float* views, int n_views, int W, int H, int ssaa,
+                           float ortho_scale, const float* params, int log2_shininess, const uint8_t* bg_image,
+                           uint8_t* image, float* radiance, int32_t* face_id, float* depth, void* ws, size_t ws_bytes,
+                           fpsg_stream_t stream) {
   FPSG_REQUIRE(render_shape_ok(V, F, n_views, W, H, ssaa), FPSG_E_SHAPE,
-               "fpsg_mesh_render_materials: V,F,n_views,W,H must be positive, ssaa from 1 to %d and a divisor of W "
-               "and H (got %d,%d,%d,%d,%d,%d)", FPSG_RENDER_MAX_SSAA, V, F, n_views, W, H, ssaa);
+               "%s: V,F,n_views,W,H must be positive, ssaa from 1 to %d and a divisor of W "
+               "and H (got %d,%d,%d,%d,%d,%d)", fn, FPSG_RENDER_MAX_SSAA, V, F, n_views, W, H, ssaa);
   FPSG_REQUIRE(M >= 0 && T >= 0 && n_texels >= 0, FPSG_E_SHAPE,
-               "fpsg_mesh_render_materials: M, T and n_texels must not be negative (got %d,%d,%lld)", M, T, n_texels);
+               "%s: M, T and n_texels must not be negative (got %d,%d,%lld)", fn, M, T, n_texels);
   FPSG_REQUIRE(ortho_scale > 0.0f && ortho_scale <= 3.0e38f, FPSG_E_SHAPE,
-               "fpsg_mesh_render_materials: ortho_scale must be positive and finite");
+               "%s: ortho_scale must be positive and finite", fn);
   FPSG_REQUIRE(log2_shininess >= 0 && log2_shininess <= FPSG_RENDER_MAX_LOG2_SHININESS, FPSG_E_SHAPE,
-               "fpsg_mesh_render_materials: log2_shininess must be from 0 to %d (got %d)",
-               FPSG_RENDER_MAX_LOG2_SHININESS, log2_shininess);
+               "%s: log2_shininess must be from 0 to %d (got %d)", fn, FPSG_RENDER_MAX_LOG2_SHININESS, log2_shininess);
   FPSG_REQUIRE(render_limit_ok(F, n_views, W, H), FPSG_E_LIMIT,
-               "fpsg_mesh_render_materials: W,H <= %d, n_views <= %d and F n_views < 2^31 are supported (got "
-               "%d,%d,%d,%d)", FPSG_RENDER_MAX_SIZE, FPSG_RENDER_MAX_VIEWS, W, H, n_views, F);
+               "%s: W,H <= %d, n_views <= %d and F n_views < 2^31 are supported (got "
+               "%d,%d,%d,%d)", fn, FPSG_RENDER_MAX_SIZE, FPSG_RENDER_MAX_VIEWS, W, H, n_views, F);
   FPSG_REQUIRE(material_limit_ok(M, T, n_texels), FPSG_E_LIMIT,
-               "fpsg_mesh_render_materials: M <= %d, T <= %d and n_texels <= %d are supported (got %d,%d,%lld)",
+               "%s: M <= %d, T <= %d and n_texels <= %d are supported (got %d,%d,%lld)", fn,
                FPSG_RENDER_MAX_MATERIALS, FPSG_RENDER_MAX_TEXTURES, FPSG_RENDER_MAX_TEXELS, M, T, n_texels);
-  FPSG_REQUIRE_PTR(verts); FPSG_REQUIRE_PTR(faces); FPSG_REQUIRE_PTR(views); FPSG_REQUIRE_PTR(ws);
-  FPSG_REQUIRE(params != nullptr, FPSG_E_NULL, "fpsg_mesh_render_materials: null pointer 'params'");
-  if (M > 0) { FPSG_REQUIRE_PTR(face_material); FPSG_REQUIRE_PTR(materials); }
-  if (T > 0) { FPSG_REQUIRE_PTR(face_uv); FPSG_REQUIRE_PTR(tex_table); }
-  FPSG_REQUIRE(T == 0 || texels != nullptr, FPSG_E_NULL, "fpsg_mesh_render_materials: null pointer 'texels'");
-  FPSG_REQUIRE(image || radiance || face_id || depth, FPSG_E_NULL, "fpsg_mesh_render_materials: no output requested");
+  RENDER_REQUIRE_PTR(verts); RENDER_REQUIRE_PTR(faces); RENDER_REQUIRE_PTR(views); RENDER_REQUIRE_PTR(ws);
+  FPSG_REQUIRE(params != nullptr, FPSG_E_NULL, "%s: null pointer 'params'", fn);
+  if (M > 0) { RENDER_REQUIRE_PTR(face_material); RENDER_REQUIRE_PTR(materials); }
+  if (T > 0) { RENDER_REQUIRE_PTR(face_uv); RENDER_REQUIRE_PTR(tex_table); }
+  if (smooth) RENDER_REQUIRE_PTR(face_normals);
+  FPSG_REQUIRE(T == 0 || texels != nullptr, FPSG_E_NULL, "%s: null pointer 'texels'", fn);
+  FPSG_REQUIRE(image || radiance || face_id || depth, FPSG_E_NULL, "%s: no output requested", fn);
   FPSG_REQUIRE(!misaligned4(radiance) && !misaligned4(face_id) && !misaligned4(depth), FPSG_E_ALIGN,
-               "fpsg_mesh_render_materials: an output is not 4-byte aligned");
-  FPSG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15u) == 0, FPSG_E_ALIGN,
-               "fpsg_mesh_render_materials: 'ws' must be 16-byte aligned");
+               "%s: an output is not 4-byte aligned", fn);
+  FPSG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15u) == 0, FPSG_E_ALIGN, "%s: 'ws' must be 16-byte aligned", fn);
   for (int t = 0; t < T; ++t) {                        // tex_table and materials are host memory
     const long long off = tex_table[3 * t], tw = tex_table[3 * t + 1], th = tex_table[3 * t + 2];
     FPSG_REQUIRE(off >= 0 && tw >= 1 && th >= 1 && off + tw * th <= n_texels, FPSG_E_SHAPE,
-                 "fpsg_mesh_render_materials: texture %d (offset %lld, %lld x %lld) reaches outside the %lld texels", t,
-                 off, tw, th, n_texels);
+                 "%s: texture %d (offset %lld, %lld x %lld) reaches outside the %lld texels", fn, t, off, tw, th,
+                 n_texels);
   }
   for (int m = 0; m < M; ++m) {
     const float ti = materials[4 * m + 3];
     FPSG_REQUIRE(ti >= -1.0f && ti < (float)T && ti == __builtin_floorf(ti), FPSG_E_SHAPE,
-                 "fpsg_mesh_render_materials: material %d has texture index %g, outside [-1, %d)", m, (double)ti, T);
+                 "%s: material %d has texture index %g, outside [-1, %d)", fn, m, (double)ti, T);
   }
   const RenderWs L = render_ws(V, F, n_views, W, H);
   const MaterialWs LM = material_ws(L, M, T);
-  FPSG_REQUIRE(ws_bytes >= LM.total, FPSG_E_SHAPE, "fpsg_mesh_render_materials: workspace of %zu bytes, %zu needed",
-               ws_bytes, LM.total);
+  FPSG_REQUIRE(ws_bytes >= LM.total, FPSG_E_SHAPE, "%s: workspace of %zu bytes, %zu needed", fn, ws_bytes, LM.total);
   MaterialParams Q;
   unpack_render_params(params, log2_shininess, Q.base);
   Q.ambient = params[15]; Q.diffuse = params[16];
@@ -547,7 +596,7 @@ extern "C" int fpsg_mesh_render_materials(const float* verts, int V, const int32
     e = hipMemcpyAsync(base + LM.materials, materials, (size_t)M * 16, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && T > 0)
     e = hipMemcpyAsync(base + LM.tex_table, tex_table, (size_t)T * 12, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) { set_error("fpsg_mesh_render_materials: %s", hipGetErrorString(e)); return (int)e; }
+  if (e != hipSuccess) { set_error("%s: %s", fn, hipGetErrorString(e)); return (int)e; }
   hipLaunchKernelGGL(render_project_kernel, dim3((unsigned)((V + 255) / 256), (unsigned)n_views), dim3(256), 0, st,
                      verts, V, views, ortho_scale, W, H, cam, snapped);
   hipLaunchKernelGGL(render_raster_kernel, dim3((unsigned)((F + 255) / 256), (unsigned)n_views), dim3(256), 0, st,
@@ -555,9 +604,46 @@ extern "C" int fpsg_mesh_render_materials(const float* verts, int V, const int32
   hipLaunchKernelGGL(render_raster_large_kernel, dim3(1024), dim3(256), 0, st, faces, F, V, cam, snapped, W, H, zbuf,
                      list, counter, (unsigned)n_views);
   const int ow = W / ssaa, oh = H / ssaa;
-  hipLaunchKernelGGL(render_shade_materials_kernel,
-                     dim3((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4), (unsigned)n_views), dim3(256), 0, st,
-                     verts, faces, V, views, snapped, zbuf, W, H, ssaa, Q, TB, bg_image, image, radiance, face_id,
-                     depth);
-  return launch_status("fpsg_mesh_render_materials");
+  const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4), (unsigned)n_views);
+  if (smooth)
+    hipLaunchKernelGGL(render_shade_materials_kernel<true>, grid, dim3(256), 0, st, verts, faces, V, views, snapped,
+                       zbuf, W, H, ssaa, Q, TB, face_normals, bg_image, image, radiance, face_id, depth);
+  else
+    hipLaunchKernelGGL(render_shade_materials_kernel<false>, grid, dim3(256), 0, st, verts, faces, V, views, snapped,
+                       zbuf, W, H, ssaa, Q, TB, face_normals, bg_image, image, radiance, face_id, depth);
+  return launch_status(fn);
+}
+#undef RENDER_REQUIRE_PTR
+
+}  // namespace
+}  // namespace fpsg
+
+extern "C" int fpsg_mesh_render_materials(const float* verts, int V, const int32_t* faces, int F,
+                                          const int32_t* face_material, const float* face_uv, const float* materials,
+                                          int M, const int32_t* tex_table, int T, const uint8_t* texels,
+                                          long long n_texels, const float* views, int n_views, int W, int H, int ssaa,
+                                          float ortho_scale, const float* params, int log2_shininess,
+                                          const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* face_id,
+                                          float* depth, void* ws, size_t ws_bytes, fpsg_stream_t stream) {
+  return fpsg::render_materials_entry("fpsg_mesh_render_materials", false, verts, V, faces, F, face_material, face_uv,
+                                      nullptr, materials, M, tex_table, T, texels, n_texels, views, n_views, W, H, ssaa,
+                                      ortho_scale, params, log2_shininess, bg_image, image, radiance, face_id, depth, ws,
+                                      ws_bytes, stream);
+}
+
+extern "C" size_t fpsg_mesh_render_smooth_workspace_bytes(int V, int F, int n_views, int W, int H, int M, int T) {
+  return fpsg_mesh_render_materials_workspace_bytes(V, F, n_views, W, H, M, T);
+}
+
+extern "C" int fpsg_mesh_render_smooth(const float* verts, int V, const int32_t* faces, int F,
+                                       const int32_t* face_material, const float* face_uv, const float* face_normals,
+                                       const float* materials, int M, const int32_t* tex_table, int T,
+                                       const uint8_t* texels, long long n_texels, const float* views, int n_views, int W,
+                                       int H, int ssaa, float ortho_scale, const float* params, int log2_shininess,
+                                       const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* face_id,
+                                       float* depth, void* ws, size_t ws_bytes, fpsg_stream_t stream) {
+  return fpsg::render_materials_entry("fpsg_mesh_render_smooth", true, verts, V, faces, F, face_material, face_uv,
+                                      face_normals, materials, M, tex_table, T, texels, n_texels, views, n_views, W, H,
+                                      ssaa, ortho_scale, params, log2_shininess, bg_image, image, radiance, face_id,
+                                      depth, ws, ws_bytes, stream);
 }

@@ -381,6 +381,27 @@ class ImgPCProtoNet(nn.Module):
         pc_z = self.pc_encoder(pcs.reshape(-1, *pcs.shape[2:]).transpose(2, 1))
         return self._decode_queries(img_z, pc_z)
 
+    @torch.no_grad()
+    def reconstruct_mesh(self, sample, grid: int = 16):
+        """The generated query shapes as triangle meshes -> ``(verts [Q, G*grid*grid, 3], faces [F, 3] int32)``:
+        ``reconstruct``'s encode (query images and support clouds only), then the decoder's ``G`` patches evaluated on a
+        regular ``grid x grid`` lattice (``PCDecoder.decode_grid``) and connected by ``surface.patch_faces``.  The faces
+        are shared by the queries.  Every module must be in evaluation mode (``RuntimeError`` otherwise)."""
+        from .surface import patch_faces
+        if any(m.training for m in self.modules()):
+            raise RuntimeError("reconstruct_mesh needs evaluation mode for every module (call .eval())")
+        decode_grid = getattr(self.pc_decoder, "decode_grid", None)
+        if decode_grid is None:
+            raise ValueError("reconstruct_mesh needs a decoder with decode_grid (PCDecoder)")
+        xq, pcs = sample["xq"], sample["pcs"]
+        img_z = self.img_encoder(xq.reshape(-1, *xq.shape[2:]))
+        pc_z = self.pc_encoder(pcs.reshape(-1, *pcs.shape[2:]).transpose(2, 1))
+        proto = pc_z.mean(0, keepdim=True).expand(img_z.size(0), -1)
+        verts = decode_grid(torch.cat([img_z, proto], dim=1), grid)
+        n_patches = self.pc_decoder.num_clusters * self.pc_decoder.num_nodes
+        faces = torch.from_numpy(patch_faces(grid, n_patches)).to(verts.device)
+        return verts, faces
+
     def draw_reconstruction(self, sample, img_path, renderer="matplotlib", up="z"):
         """Writes ``<dir>/<stem>.png`` (generated vs ground truth, one column per query) and
         the clouds as ``<stem>_<code>.npy`` / ``<stem>_<code>_gt.npy``.

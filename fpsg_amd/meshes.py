@@ -5,6 +5,9 @@ The host part (``load_mesh``, ``load_obj_scene``, ``pack_textures``, ``normalize
 ``camera_views``, ``write_modelnet_lists``, ``write_shapenet_lists``) needs no GPU.  ``sample_surface``,
 ``render_views`` and ``render_points`` (K29: views of point clouds as shaded spheres) run on the GPU only: a CPU tensor
 raises ``FpsgHipError``.
+
+Generated meshes (K31): ``corner_table`` and ``write_obj_mesh`` are host code; ``vertex_normals`` (K31a) and
+``render_views(face_normals=...)`` (K31b, smooth shading) run on the GPU only.
 """
 from __future__ import annotations
 
@@ -420,6 +423,57 @@ def write_ply_points(path: str, pts) -> None:
         f.write(head + body + "\n")
 
 
+def write_obj_mesh(path: str, verts, faces, *, normals=None, face_material=None, materials=None, mtl_name=None) -> None:
+    """A triangle mesh as a Wavefront ``.obj`` that ``load_obj_scene`` reads back: ``v`` records, with ``normals``
+    ``[V,3]`` also ``vn`` records and faces ``f a//a b//b c//c`` (vertex ``k`` has normal ``k``), without them ``f a b c``.
+    ``%.9g`` keeps every float32 bit.
+
+    ``face_material`` int ``[F]`` with ``materials``, a list of ``(name, (r, g, b))``: a ``usemtl`` line in front of
+    every run of faces with one material (faces stay in their order) and, beside the file, ``mtl_name`` (default: the
+    file's name with ``.mtl``) with a ``newmtl`` / ``Kd`` record per material.  An index outside the list is a
+    ``ValueError``, and so is one of the two arguments without the other."""
+    def host(a, dtype):
+        return np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, dtype=dtype)
+
+    v, f = host(verts, np.float32), host(faces, np.int64)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError(f"expected [V,3] vertices, got {v.shape}")
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"expected [F,3] faces, got {f.shape}")
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f"face indices must be in [0, {len(v)}), got {int(f.min())}..{int(f.max())}")
+    if (face_material is None) != (materials is None):
+        raise ValueError("face_material and materials go together")
+    lines = []
+    if materials is not None:
+        fm = host(face_material, np.int64).reshape(-1)
+        if fm.shape != (len(f),):
+            raise ValueError(f"face_material must have one entry per face ({len(f)}), got {fm.shape}")
+        if fm.size and (fm.min() < 0 or fm.max() >= len(materials)):
+            raise ValueError(f"face_material must index the {len(materials)} materials, got {int(fm.min())}..{int(fm.max())}")
+        mtl_name = mtl_name or os.path.splitext(os.path.basename(path))[0] + ".mtl"
+        lines.append(f"mtllib {mtl_name}")
+    lines += ["v %.9g %.9g %.9g" % tuple(p) for p in v.tolist()]
+    if normals is not None:
+        vn = host(normals, np.float32)
+        if vn.shape != v.shape:
+            raise ValueError(f"normals must be {v.shape}, got {vn.shape}")
+        lines += ["vn %.9g %.9g %.9g" % tuple(p) for p in vn.tolist()]
+        corner = "%d//%d"
+        rows = ["f " + " ".join(corner % (k, k) for k in t) for t in (f + 1).tolist()]
+    else:
+        rows = ["f %d %d %d" % tuple(t) for t in (f + 1).tolist()]
+    if materials is not None:
+        starts = np.nonzero(np.concatenate([[True], fm[1:] != fm[:-1]]))[0] if len(fm) else []
+        for k in reversed(list(starts)):
+            rows.insert(int(k), f"usemtl {materials[int(fm[k])][0]}")
+    with open(path, "w") as out:
+        out.write("\n".join(lines + rows) + "\n")
+    if materials is not None:
+        with open(os.path.join(os.path.dirname(path), mtl_name), "w") as out:
+            out.write("".join("newmtl %s\nKd %.9g %.9g %.9g\n" % (name, *kd) for name, kd in materials))
+
+
 # -------------------------------------------------------------------------------------------- K26
 def _mesh_tensors(verts, faces):
     if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.size(1) != 3 or verts.size(0) < 1:
@@ -591,7 +645,7 @@ def _scene_arguments(scene, F, dev):
 def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevations_deg=60.0,
                  azimuths_deg=range(0, 360, 30), radius: float = 3.0, ortho_scale: float = 2.0, up: str = "z",
                  ssaa: int = 2, background=(1.0, 1.0, 1.0), material: PhongMaterial = PhongMaterial(),
-                 return_buffers: bool = False, views=None, scene: RenderScene | None = None):
+                 return_buffers: bool = False, views=None, scene: RenderScene | None = None, face_normals=None):
     """Orthographic, flat-shaded Phong views of a mesh (K27) -> uint8 ``[n_views, H, W, 3]`` on the mesh's device.
 
     ``size``: an int (square) or ``(H, W)``; the mesh is rasterised at ``size * ssaa`` and every output pixel is the
@@ -605,6 +659,11 @@ def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevatio
     With ``scene`` (a ``RenderScene``, see ``scene_tensors``) the shade pass is K28's: a face with a material takes its
     base colour from the material's ``Kd`` or texture in place of ``material.color``, scaled by ``material.ambient`` and
     ``material.diffuse``; a face without one is shaded as without ``scene``, and so are ``face_id`` and ``depth``.
+
+    With ``face_normals`` (float32 ``[F,3,3]`` on the mesh's device: a world-space normal per corner, in the layout of
+    ``face_uv``) the views are smooth-shaded (K31b): the light's terms take the normal interpolated at the sample, put
+    on the side of the face the camera sees; where it has no length (zero or NaN corners) the face's own normal stays.
+    Colours are ``scene``'s when it is given as well, ``material.color`` otherwise; ``face_id`` and ``depth`` do not change.
 
     ``ValueError`` for bad shapes and options, ``FpsgHipError`` for CPU tensors."""
     H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
@@ -634,6 +693,15 @@ def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevatio
     V, F = verts.size(0), faces.size(0)
     RW, RH = W * ssaa, H * ssaa
     lib = _hip.load()
+    if face_normals is not None:
+        if not isinstance(face_normals, torch.Tensor) or face_normals.device != dev or \
+                tuple(face_normals.shape) != (F, 3, 3):
+            raise ValueError(f"face_normals must be a tensor {(F, 3, 3)} on {dev}, got "
+                             f"{tuple(getattr(face_normals, 'shape', ()))} on {getattr(face_normals, 'device', None)}")
+        face_normals = face_normals.detach().contiguous()
+        _hip.dev_tensor(face_normals, torch.float32, "face_normals")
+        if scene is None:                    # no materials: K27's colours
+            scene = RenderScene(None, None, np.zeros((0, 4), np.float32), np.zeros((0, 3), np.int32), None)
     if scene is not None:
         mat_table, tex_table, face_material, face_uv, texels = _scene_arguments(scene, F, dev)
         M, T = len(mat_table), len(tex_table)
@@ -661,13 +729,19 @@ def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevatio
         c_params = (ctypes.c_float * 17)(*params.tolist(), float(material.ambient), float(material.diffuse))
         c_mats = mat_table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if M else None
         c_table = tex_table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if T else None
-        with torch.cuda.device(dev):
-            rc = lib.fpsg_mesh_render_materials(
-                _hip.ptr(verts), V, _hip.ptr(faces), F, opt(face_material), opt(face_uv), c_mats, M, c_table, T,
-                opt(texels), 0 if texels is None else texels.size(0), _hip.ptr(d_views), n_views, RW, RH, ssaa,
-                float(ortho_scale), c_params, log2s, opt(bg_img), _hip.ptr(image), opt(radiance), opt(face_id),
+        tail = (c_mats, M, c_table, T, opt(texels), 0 if texels is None else texels.size(0), _hip.ptr(d_views), n_views, RW,
+                RH, ssaa, float(ortho_scale), c_params, log2s, opt(bg_img), _hip.ptr(image), opt(radiance), opt(face_id),
                 opt(depth), _hip.ptr(ws), ws.numel() * 8, _hip.stream_of(verts))
-        _hip.check(rc, "fpsg_mesh_render_materials")
+        with torch.cuda.device(dev):
+            if face_normals is not None:
+                entry = "fpsg_mesh_render_smooth"
+                rc = lib.fpsg_mesh_render_smooth(_hip.ptr(verts), V, _hip.ptr(faces), F, opt(face_material), opt(face_uv),
+                                                 _hip.ptr(face_normals), *tail)
+            else:
+                entry = "fpsg_mesh_render_materials"
+                rc = lib.fpsg_mesh_render_materials(_hip.ptr(verts), V, _hip.ptr(faces), F, opt(face_material),
+                                                    opt(face_uv), *tail)
+        _hip.check(rc, entry)
     else:
         with torch.cuda.device(dev):
             rc = lib.fpsg_mesh_render(_hip.ptr(verts), V, _hip.ptr(faces), F, _hip.ptr(d_views), n_views, RW, RH, ssaa,
@@ -677,6 +751,65 @@ def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevatio
     if return_buffers:
         return image, {"face_id": face_id, "depth": depth, "radiance": radiance}
     return image
+
+
+# -------------------------------------------------------------------------------------------- K31a
+def corner_table(faces, V: int):
+    """The incidence table K31a walks -> ``(offsets int32 [V+1], corner_faces int32 [n])``: the slice
+    ``corner_faces[offsets[v]:offsets[v+1]]`` lists the faces that name vertex ``v`` in ascending order, once per corner
+    that names it.  A face with an index outside ``[0, V)`` is listed nowhere (K27 does not draw it either).  Built on the
+    host by a stable numpy sort, once per topology: the meshes of a decoder share it."""
+    f = np.asarray(faces.detach().cpu() if isinstance(faces, torch.Tensor) else faces)
+    if f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+        raise ValueError(f"expected integer [F,3] faces, got {f.dtype} {f.shape}")
+    if isinstance(V, bool) or int(V) != V or int(V) < 1:
+        raise ValueError(f"V must be a positive integer, got {V}")
+    V = int(V)
+    f = f.astype(np.int64)
+    ok = ((f >= 0) & (f < V)).all(axis=1)
+    face = np.repeat(np.arange(len(f), dtype=np.int64)[ok], 3)       # ascending, a face's three corners side by side
+    vert = f[ok].reshape(-1)
+    order = np.argsort(vert, kind="stable")                          # stable: ascending faces inside every vertex
+    offsets = np.zeros(V + 1, np.int64)
+    np.cumsum(np.bincount(vert, minlength=V), out=offsets[1:])
+    return offsets.astype(np.int32), face[order].astype(np.int32)
+
+
+def vertex_normals(verts: torch.Tensor, faces: torch.Tensor, table=None) -> torch.Tensor:
+    """Area-weighted unit vertex normals (K31a) of one mesh ``[V,3]`` or of ``B`` meshes ``[B,V,3]`` that share
+    ``faces [F,3]`` -> float32 of ``verts``' shape.  A vertex's normal is the sum of the un-normalised face normals
+    ``(b - a) x (c - a)`` of the faces around it, divided by its length; ``(0, 0, 0)`` where that sum is zero or not
+    finite (an isolated vertex, opposed faces).  ``table``: ``corner_table(faces, V)`` when the caller keeps it for a
+    topology, built here otherwise; either array may be a numpy array or a tensor.  Bitwise the same on every run.
+
+    ``ValueError`` for bad shapes, ``FpsgHipError`` for CPU tensors."""
+    if not isinstance(verts, torch.Tensor) or verts.dim() not in (2, 3) or verts.size(-1) != 3 or verts.numel() == 0:
+        raise ValueError(f"expected [V,3] or [B,V,3] vertices, got {tuple(getattr(verts, 'shape', ()))}")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.size(1) != 3 or faces.size(0) < 1:
+        raise ValueError(f"expected [F,3] faces, got {tuple(getattr(faces, 'shape', ()))}")
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"faces must be int32 or int64, got {faces.dtype}")
+    batch = verts.detach().reshape(-1, verts.size(-2), 3).contiguous()
+    _hip.dev_tensor(batch, torch.float32, "verts")
+    dev = batch.device
+    if faces.device != dev:
+        raise ValueError(f"faces are on {faces.device}, verts on {dev}")
+    B, V, F = batch.size(0), batch.size(1), faces.size(0)
+    if table is None:
+        table = corner_table(faces, V)
+    offsets, corner_faces = (torch.as_tensor(t).to(device=dev, dtype=torch.int32).contiguous() for t in table)
+    n = corner_faces.numel()
+    if offsets.shape != (V + 1,) or corner_faces.dim() != 1 or n > 3 * F:
+        raise ValueError(f"table must be (offsets [{V + 1}], corner_faces [n <= {3 * F}]), got {tuple(offsets.shape)} and "
+                         f"{tuple(corner_faces.shape)}")
+    faces = faces.to(torch.int32).contiguous()
+    normals = torch.empty_like(batch)
+    with torch.cuda.device(dev):
+        rc = _hip.load().fpsg_mesh_vertex_normals(_hip.ptr(batch), B, V, _hip.ptr(faces), F, _hip.ptr(offsets),
+                                                  _hip.ptr(corner_faces) if n else None, n, _hip.ptr(normals),
+                                                  _hip.stream_of(batch))
+    _hip.check(rc, "fpsg_mesh_vertex_normals")
+    return normals.reshape(verts.shape)
 
 
 # -------------------------------------------------------------------------------------------- K29

@@ -761,6 +761,33 @@ class PCDecoder(nn.Module):
             return self._forward_batched(hidden_feat, grid, generator, pack)
         return self._forward_looped(hidden_feat, grid, generator)
 
+    def decode_grid(self, hidden_feat, g: int):
+        """The decoder evaluated on ``surface.regular_grid(g)`` for every patch: ``hidden[B, bottleneck]`` ->
+        ``[B, G*g*g, 3]``, patch ``p``'s sample ``(i, j)`` at row ``p*g*g + i*g + j`` -- the vertices that
+        ``surface.patch_faces(g, G)`` connects to a mesh.  Needs the SQUARE template (the grid is one of the unit square)
+        and evaluation mode: in training mode BatchNorm would take its statistics from the grid and move the running
+        ones (``RuntimeError``, before any work).  K9 takes the first layer for ``g`` in {2, 4, 8, 16} where
+        ``fpsg_dec1_fits``; other sizes run the library chain."""
+        from .surface import regular_grid
+        if getattr(self.conf, "template_type", None) != "SQUARE":
+            raise ValueError(f"decode_grid needs template_type SQUARE (a grid on the unit square), the decoder has "
+                             f"{getattr(self.conf, 'template_type', None)!r}")
+        if any(m.training for m in self.modules()):
+            raise RuntimeError("decode_grid needs evaluation mode (call .eval()): in training mode BatchNorm would "
+                               "normalise with the grid's statistics and update the running ones")
+        uv = torch.from_numpy(regular_grid(g)).to(hidden_feat.device)                   # [2, g*g]
+        patch = uv.unsqueeze(0).expand(hidden_feat.size(0), -1, -1)
+        grid = [[patch for _ in range(self.num_nodes)] for _ in range(self.num_clusters)]
+        return self.forward(hidden_feat, grid=grid)
+
+    def first_layer_path(self, hidden_feat, P: int) -> str:
+        """What evaluates the patch MLPs' first layer for these latents and ``P`` points per patch: ``"K9"``
+        (``_layer1_fused_ok``, the batched form's own switch) or ``"library"`` -- for reports, not for dispatch."""
+        act = self.cluster_pool[0].deformer.activation
+        fused = self.batched and self.conf.raw_dim == 3 and _layer1_fused_ok(hidden_feat, hidden_feat,
+                                                                             hidden_feat.size(0), int(P), act)
+        return "K9" if fused else "library"
+
     def pair_ready(self, hidden_a, hidden_b) -> bool:
         """``forward_pair`` has its joint form for these inputs: the batched decoder in training mode on the GPU, ReLU
         patch MLPs, K9's patch sizes.  ``FPSG_DECODE_PAIR=0`` keeps the two separate passes (A/B measurements)."""
@@ -920,7 +947,12 @@ class PCDecoder(nn.Module):
             else:
                 g = torch.empty((G, B, dim, P), dtype=torch.float32, device=x.device).normal_(0, 1, generator=generator)
         else:
-            g = torch.stack([t for per_cluster in grid for t in per_cluster])          # [G,B,dim,P]
+            patches = [t for per_cluster in grid for t in per_cluster]
+            P = patches[0].shape[-1]                # an injected grid brings its own patch size (decode_grid)
+            if any(t.shape[-1] != P for t in patches):
+                raise ValueError(f"PCDecoder: the patches of one call must have one size, got "
+                                 f"{sorted({int(t.shape[-1]) for t in patches})}")
+            g = torch.stack(patches)                                                    # [G,B,dim,P]
         h = g.permute(0, 2, 1, 3).reshape(G, g.size(2), B * P)                          # [G,dim,B*P]
 
         # ---- per-cluster deformers, applied to each of the cluster's R patches

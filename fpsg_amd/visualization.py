@@ -7,7 +7,8 @@ returned as ``[4, H, W]`` RGBA like the reference's renderer buffer.  PNG writin
 
 ``render_reconstruction`` is the same comparison drawn on the GPU (K29, ``meshes.render_points``): shaded spheres seen by
 the cameras of the conditioning views, both clouds on one scale, the generated one in the colours of the decoder's
-patches (``patch_colors``).
+patches (``patch_colors``).  ``render_mesh_reconstruction`` draws the generated shape as a smooth-shaded mesh instead
+(K31: ``PCDecoder.decode_grid``'s vertices, ``meshes.vertex_normals``, ``meshes.render_views(face_normals=...)``).
 """
 from __future__ import annotations
 
@@ -76,6 +77,48 @@ def render_reconstruction(syn_pc, gt_pc, pts_per_patch=None, up="z", size=192):
     rows = [h.permute(0, 2, 1, 3, 4).reshape(Q, h.size(2), -1, 3) for h in halves]      # [Q, H, n_views W, 3]
     sheet = torch.cat(rows, dim=2).reshape(Q * rows[0].size(1), -1, 3)
     return sheet.cpu().numpy()
+
+
+def patch_materials(n_patches: int) -> list:
+    """``[(name, (r, g, b))]`` for ``meshes.write_obj_mesh``: patch ``p`` is ``patch_<p>`` with the ``Kd`` of its
+    ``PATCH_PALETTE`` colour (which repeats beyond 16 patches), a byte over 255 rounded to float32."""
+    kd = (PATCH_PALETTE[np.arange(int(n_patches)) % len(PATCH_PALETTE)].astype(np.float64) / 255.0).astype(np.float32)
+    return [(f"patch_{p}", tuple(float(c) for c in kd[p])) for p in range(int(n_patches))]
+
+
+def render_mesh_reconstruction(verts, faces, gt_pc, g, up="z", size=192):
+    """Generated meshes against ground-truth clouds -> uint8 ``[Q * size, 2 * 3 * size, 3]``, ``render_reconstruction``'s
+    layout on one scale: left three smooth-shaded views (K31b; elevation 60, azimuths 0, 120, 240) of each generated
+    mesh, its vertex normals from K31a and one ``Kd`` material per patch from ``PATCH_PALETTE``; right the ground truth
+    as K29's grey spheres.  ``verts`` ``[Q, n_patches*g*g, 3]`` and ``faces`` as ``ImgPCProtoNet.reconstruct_mesh`` returns
+    them, ``gt_pc`` ``[Q,M,3]``, all on one GPU; ``ValueError`` for anything else about their shapes."""
+    import torch
+    from . import meshes, surface
+    if not (isinstance(verts, torch.Tensor) and isinstance(gt_pc, torch.Tensor) and isinstance(faces, torch.Tensor) and
+            verts.dim() == 3 and gt_pc.dim() == 3 and verts.size(2) == 3 and gt_pc.size(2) == 3 and
+            verts.size(0) == gt_pc.size(0) and faces.dim() == 2 and faces.size(1) == 3):
+        raise ValueError(f"expected [Q,V,3] vertices, [F,3] faces and [Q,M,3] clouds, got "
+                         f"{tuple(getattr(verts, 'shape', ()))}, {tuple(getattr(faces, 'shape', ()))} and "
+                         f"{tuple(getattr(gt_pc, 'shape', ()))}")
+    Q, V = verts.size(0), verts.size(1)
+    n_patches = V // (int(g) * int(g)) if g else 0
+    if n_patches < 1 or n_patches * g * g != V or faces.size(0) != n_patches * 2 * (g - 1) ** 2:
+        raise ValueError(f"{V} vertices and {faces.size(0)} faces are not patches of a {g} x {g} grid")
+    dev = verts.device
+    verts, gt_pc = verts.detach().float().contiguous(), gt_pc.detach().float().contiguous()
+    faces = faces.to(torch.int32).contiguous()
+    normals = meshes.vertex_normals(verts, faces, meshes.corner_table(faces, V))        # one table for the Q meshes
+    kd = np.array([c for _, c in patch_materials(n_patches)], dtype=np.float32)
+    scene = meshes.RenderScene(torch.from_numpy(surface.patch_face_material(g, n_patches)).to(dev), None,
+                               np.concatenate([kd, np.full((n_patches, 1), -1.0, np.float32)], axis=1),
+                               np.zeros((0, 3), np.int32), None)
+    index = faces.long()
+    left = torch.stack([meshes.render_views(verts[q], faces, size=size, elevations_deg=60.0, azimuths_deg=(0, 120, 240),
+                                            up=up, scene=scene, face_normals=normals[q][index]) for q in range(Q)])
+    grey = torch.tensor(GREY, dtype=torch.uint8, device=dev)
+    right = meshes.render_points(gt_pc, colors=grey.expand(Q, gt_pc.size(1), 3).contiguous(), size=size, up=up)
+    rows = [h.permute(0, 2, 1, 3, 4).reshape(Q, h.size(2), -1, 3) for h in (left, right)]   # [Q, H, n_views W, 3]
+    return torch.cat(rows, dim=2).reshape(Q * rows[0].size(1), -1, 3).cpu().numpy()
 
 
 def write_png(path: str, hwc: np.ndarray) -> None:

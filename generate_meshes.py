@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Generated shapes as triangle meshes: every test item's queries as ``.obj`` files and a sheet of smooth-shaded views.
+
+    python generate_meshes.py --synthetic --n_shot 1 --n_query 1 --sequential_eval \\
+        --model_path /tmp/ckpt --name 0 --eval_model model_epoch_2.pt --output /tmp/meshes --grid 16
+
+Takes the evaluation entry point's options for data and model (``evaluate_Network.py``: ``--synthetic`` or the list
+files, ``--model_path --name --eval_model``, ``--n_shot --n_query``, ``--sequential_eval``, ``--sample_up``) and builds both
+with the same helpers.  The decoder's 16 patches are evaluated on a regular ``--grid`` x ``--grid`` lattice of the unit
+square and neighbouring samples connected (``ImgPCProtoNet.reconstruct_mesh``).  For each test item it writes
+
+- ``<output>/<class>/<item>_q<k>.obj`` per query ``k``: vertices, area-weighted vertex normals (K31a) and a material per
+  patch, in ``<output>/<class>/patches.mtl`` (``Kd`` = the patch's colour of ``visualization.PATCH_PALETTE``);
+- ``<output>/<class>/<item>.png``: one row per query, left three smooth-shaded views of the mesh (K31b), right the
+  ground-truth cloud as shaded spheres (K29), on one scale -- unless ``--no_sheet`` is given.
+
+``<item>`` is the item's position in the test loader, five digits.  Prints one summary line.  Runs on a ROCm GPU only.
+"""
+from __future__ import annotations
+
+import os
+
+os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")   # before the HIP runtime initialises (fpsg_amd/__init__.py)
+import sys
+
+
+def build_parser():
+    from fpsg_amd import cli
+    p = cli.few_shot_parser(evaluation=True)          # the evaluation's options; this tool's are added to the object
+    p.description = __doc__.split("\n")[0]
+    g = p.add_argument_group("meshes")
+    g.add_argument("--output", type=str, default="meshes", metavar="DIR", help="Where the files go [default: meshes];")
+    g.add_argument("--grid", type=int, default=16, metavar="G",
+                   help="Samples per patch and side, 2..64: G*G vertices and 2(G-1)^2 faces per patch [default: 16];")
+    g.add_argument("--max_items", type=int, default=0, metavar="N", help="Stop after N test items [default: 0 = all];")
+    g.add_argument("--no_sheet", action="store_true", help="Write the .obj files only, no .png sheets;")
+    return p
+
+
+def main(opt) -> int:
+    import torch
+
+    from fpsg_amd import cli, meshes, surface
+    from fpsg_amd._hip import FpsgHipError
+    from fpsg_amd.engine import build_model, to_device
+    from fpsg_amd.visualization import patch_materials, render_mesh_reconstruction, write_png
+
+    cli.validate(opt)
+    try:
+        surface.regular_grid(opt.grid)
+    except ValueError as e:
+        raise SystemExit(f"--grid: {e}") from None
+    if opt.max_items < 0:
+        raise SystemExit("--max_items must not be negative")
+    if not torch.cuda.is_available():
+        raise FpsgHipError("generate_meshes.py runs on a ROCm GPU only (no CPU fallback)")
+    n_query = opt.n_shot if opt.n_query == 0 else opt.n_query
+    device = cli.pick_device(opt)
+    torch.manual_seed(0)                 # the episodes' draws (supports; the order without --sequential_eval): the same files on every run
+    _, ds_test = cli.build_datasets(opt, n_query, device, views=False)
+    _, dl_test = cli.build_loaders(opt, ds_test, ds_test)
+    model = build_model(opt)
+    weights = os.path.join(opt.model_path, opt.name, opt.eval_model)
+    if opt.eval_model != "NONE" or os.path.exists(weights):
+        model.load_state_dict(torch.load(weights, map_location="cpu", weights_only=True))
+    else:
+        print("WARNING: --eval_model not given, meshing randomly initialised weights")
+    model = model.to(device).eval()
+
+    g = opt.grid
+    n_patches = model.pc_decoder.num_clusters * model.pc_decoder.num_nodes
+    materials = patch_materials(n_patches)
+    face_material = surface.patch_face_material(g, n_patches)
+    table = faces = None
+    items, first_layer = 0, "-"
+    for item, sample in enumerate(dl_test):
+        if opt.max_items and item >= opt.max_items:
+            break
+        sample = to_device(sample, device)
+        verts, item_faces = model.reconstruct_mesh(sample, grid=g)
+        if faces is None:                              # the topology is the same for every item: one table
+            faces = item_faces
+            table = meshes.corner_table(faces, verts.size(1))
+            first_layer = model.pc_decoder.first_layer_path(verts.new_zeros((verts.size(0), 1)), g * g)
+        normals = meshes.vertex_normals(verts, faces, table)
+        folder = os.path.join(opt.output, str(sample["class"][0]))
+        os.makedirs(folder, exist_ok=True)
+        host_v, host_n, host_f = verts.cpu().numpy(), normals.cpu().numpy(), faces.cpu().numpy()
+        for k in range(verts.size(0)):
+            meshes.write_obj_mesh(os.path.join(folder, f"{item:05d}_q{k}.obj"), host_v[k], host_f, normals=host_n[k],
+                                  face_material=face_material, materials=materials, mtl_name="patches.mtl")
+        if not opt.no_sheet:
+            pcq = sample["pcq"].squeeze(0)
+            sheet = render_mesh_reconstruction(verts, faces, pcq.reshape(-1, *pcq.shape[-2:]), g,
+                                               up=getattr(opt, "sample_up", "z"))
+            write_png(os.path.join(folder, f"{item:05d}.png"), sheet)
+        items += 1
+    kernels = f"decoder first layer {first_layer}, normals K31a" + ("" if opt.no_sheet else ", views K31b + K29")
+    print(f"{opt.output}: {items} items x {n_query} queries, {n_patches * g * g} vertices and "
+          f"{n_patches * 2 * (g - 1) ** 2} faces per mesh ({kernels})")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(build_parser().parse_args()))

@@ -1385,6 +1385,67 @@ int fpsg_points_render(const float* points, const uint8_t* colors, int B, int N,
 int fpsg_episode_views(const uint8_t* src, int n_src, int Hs, int Ws, const int32_t* sel, int n, const int32_t* geom,
                        const float* color, float* out, int Ho, int Wo, fpsg_stream_t stream);
 
+/* ---- K31a: area-weighted vertex normals of meshes that share their faces ---------------------------
+ * For the meshes a decoder generates: B vertex arrays on one topology (the patches' regular grids), so the faces and
+ * the table below are built once and serve every mesh.  All pointers are device memory.
+ * verts [B,V,3] fp32; faces [F,3] int32; normals [B,V,3] fp32 (output).
+ * Corner table, built by the caller once per topology: offsets [V+1] int32 and corner_faces [n] int32.  The slice
+ *   corner_faces[offsets[v] .. offsets[v+1]) lists, in ascending order, the faces that name vertex v, once per corner
+ *   that names it (a face (v, v, w) appears twice in v's slice).  A face with an index outside [0, V) is listed
+ *   nowhere, so n <= 3 F.
+ * All of the following in fp32 with every operation rounded on its own (no fma), division and sqrt correctly rounded.
+ * Per mesh and vertex v:  s = (0, 0, 0);  for every entry f of v's slice, in order, with the face's vertices a, b, c in
+ *   the faces' own order:  e1 = b - a;  e2 = c - a;
+ *   nx = e1y e2z - e1z e2y;  ny = e1z e2x - e1x e2z;  nz = e1x e2y - e1y e2x  (components as in K26, NOT normalised:
+ *   the face's normal times twice its area, which is the area weighting);  s = s + n, per component.
+ *   len = sqrt((sx sx + sy sy) + sz sz);  normal = s / len per component, or (0, 0, 0) when len is 0 or not finite.
+ * What the kernel does with a table that does not follow the rule: a slice is clamped to 0 <= begin <= end <= n, an
+ *   entry outside [0, F) is skipped, and so is a face with an index outside [0, V).  Such a table gives other normals
+ *   than the definition's, and never a read or write outside the arrays.
+ * Gather form: one thread per (mesh, vertex), no atomics; bitwise the same on every run.
+ * Errors, all before the launch: FPSG_E_SHAPE for B, V or F < 1, n < 0 or n > 3 F; FPSG_E_LIMIT for
+ * B > FPSG_NORMALS_MAX_MESHES, V or F > FPSG_MESH_MAX_FACES; FPSG_E_NULL for a null verts, faces, offsets or normals,
+ * or a null corner_faces with n > 0; FPSG_E_ALIGN for a misaligned pointer.
+ */
+#define FPSG_NORMALS_MAX_MESHES 65535
+int fpsg_mesh_vertex_normals(const float* verts, int B, int V, const int32_t* faces, int F, const int32_t* offsets,
+                             const int32_t* corner_faces, int n, float* normals, fpsg_stream_t stream);
+
+/* ---- K31b: K28's views lit by interpolated corner normals (smooth shading) --------------------------
+ * fpsg_mesh_render_smooth projects, rasterises and fills the z-buffer with K27's kernels, so face_id and depth are
+ * K27's; the base colour, the resolve and the outputs are K28's; only the normal that the light's terms use differs.
+ * Every argument it shares with fpsg_mesh_render_materials means what it means there (params: 17 floats; M = 0 and
+ * T = 0 as there: without materials the colours are K27's ka, kd).
+ * Extra input: face_normals [F,3,3] fp32 (device): per face the normals of its corners 0, 1, 2 in world space, in the
+ *   layout of face_uv.  They need not have unit length.
+ * All of the following in fp32 with every operation rounded on its own (no fma), divisions and sqrt correctly rounded.
+ * Shade, per covered sample of face f:
+ *   g = K27's unit face normal in the camera frame, after its fallback (0,0,-1) and its two-sided flip (g_z <= 0).
+ *   l0, l1, l2 = K28's barycentrics of the sample centre from the snapped corners: A2 in int64; A2 < 0: corners 1 and
+ *     2 swap, and their normals n1 and n2 with them; E0 = edge(1,2), E1 = edge(2,0), E2 = edge(0,1);
+ *     l_k = (float) E_k / (float) A2.
+ *   m = (l0 n0 + l1 n1) + l2 n2, per component (world space).
+ *   t = ((mx rx + my ry) + mz rz, likewise with up, likewise with forward): m in the camera frame, as K27 turns edges.
+ *   len = sqrt((tx tx + ty ty) + tz tz).
+ *   len is 0 or not finite (zero normals, NaN, inf, opposed corners):  c = g.
+ *   Otherwise c = t / len per component;  side = (cx gx + cy gy) + cz gz;  c = -c when side < 0: the interpolated
+ *     normal follows the side of the face that the camera sees, as g does.
+ *   ndl = (cx lx + cy ly) + cz lz;  diff = max(ndl, 0);  spec = ndl > 0 ? max(lz - (2 ndl) cz, 0) : 0, squared
+ *     log2_shininess times;  colour: K28's from diff, spec and the face's base colour.
+ *   Corner normals that are all zero, or all NaN, therefore give fpsg_mesh_render_materials' outputs bit for bit.
+ * Workspace: fpsg_mesh_render_smooth_workspace_bytes = fpsg_mesh_render_materials_workspace_bytes.
+ * Errors, all before any launch or copy: those of fpsg_mesh_render_materials; FPSG_E_NULL for a null face_normals,
+ * FPSG_E_ALIGN for a misaligned one.
+ */
+size_t fpsg_mesh_render_smooth_workspace_bytes(int V, int F, int n_views, int W, int H, int M, int T);
+int fpsg_mesh_render_smooth(const float* verts, int V, const int32_t* faces, int F, const int32_t* face_material,
+                            const float* face_uv, const float* face_normals, const float* materials, int M,
+                            const int32_t* tex_table, int T, const uint8_t* texels, long long n_texels,
+                            const float* views, int n_views, int W, int H, int ssaa, float ortho_scale,
+                            const float* params, int log2_shininess, const uint8_t* bg_image, uint8_t* image,
+                            float* radiance, int32_t* face_id, float* depth, void* ws, size_t ws_bytes,
+                            fpsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
