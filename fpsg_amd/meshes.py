@@ -8,6 +8,9 @@ raises ``FpsgHipError``.
 
 Generated meshes (K31): ``corner_table`` and ``write_obj_mesh`` are host code; ``vertex_normals`` (K31a) and
 ``render_views(face_normals=...)`` (K31b, smooth shading) run on the GPU only.
+
+Mesh accuracy (K32): ``point_mesh_distance`` (the nearest triangle of every point) and ``mesh_accuracy`` (that distance
+and K26 + K1 the other way round, for one mesh and one cloud) run on the GPU only.
 """
 from __future__ import annotations
 
@@ -38,6 +41,10 @@ RENDER_MAX_TEXTURES = 4096      # FPSG_RENDER_MAX_TEXTURES
 RENDER_MAX_TEXELS = 1 << 28     # FPSG_RENDER_MAX_TEXELS
 POINTS_MAX_N = 16384            # FPSG_POINTS_MAX_N
 POINTS_MAX_RADIUS_PX = 64       # FPSG_POINTS_MAX_RADIUS_PX
+POINT_MESH_MAX_POINTS = 1 << 20  # FPSG_POINT_MESH_MAX_POINTS
+POINT_MESH_MAX_MESHES = 65535   # FPSG_POINT_MESH_MAX_MESHES
+POINT_MESH_MAX_TOTAL = 1 << 26  # FPSG_POINT_MESH_MAX_TOTAL
+POINT_MESH_MAX_CHUNKS = 64      # FPSG_POINT_MESH_MAX_CHUNKS
 
 
 # ------------------------------------------------------------------------------------------ files
@@ -810,6 +817,110 @@ def vertex_normals(verts: torch.Tensor, faces: torch.Tensor, table=None) -> torc
                                                   _hip.stream_of(batch))
     _hip.check(rc, "fpsg_mesh_vertex_normals")
     return normals.reshape(verts.shape)
+
+
+# -------------------------------------------------------------------------------------------- K32
+def _batched_mesh_tensors(verts, faces):
+    """``_mesh_tensors``' checks for vertices ``[V,3]`` or ``[B,V,3]`` -> (verts detached and contiguous, faces int32)."""
+    if not isinstance(verts, torch.Tensor) or verts.dim() not in (2, 3) or verts.size(-1) != 3 or verts.numel() == 0:
+        raise ValueError(f"expected [V,3] or [B,V,3] vertices, got {tuple(getattr(verts, 'shape', ()))}")
+    if verts.dtype != torch.float32:
+        raise ValueError(f"verts must be float32, got {verts.dtype}")
+    if verts.dim() == 2:
+        return _mesh_tensors(verts.contiguous(), faces)
+    V = verts.size(1)
+    if V > MESH_MAX_FACES:
+        raise ValueError(f"meshes of more than {MESH_MAX_FACES} vertices are not supported (got {V})")
+    _, faces = _mesh_tensors(verts[0].contiguous(), faces)       # the faces' checks, against the V every mesh has
+    return verts.detach().contiguous(), faces
+
+
+def point_mesh_distance(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, *, closest: bool = False,
+                        bary: bool = False, chunks=None) -> dict:
+    """The nearest point of a triangle mesh for every point of a cloud (K32), exact, by brute force over the faces.
+
+    ``points``: ``[N,3]`` (B = 1) or ``[B,N,3]`` float32; ``verts``: ``[V,3]``, one mesh for all clouds, or ``[B,V,3]``, a
+    mesh per cloud; ``faces``: ``[F,3]`` int32 or int64, shared.  -> a dict: ``"dist2"`` float32 ``[B,N]``, the squared
+    distance to the surface; ``"face"`` int64 ``[B,N]``, the nearest face (the lowest id on ties); with ``closest`` also
+    ``"closest"`` float32 ``[B,N,3]``, the nearest point, and with ``bary`` ``"bary"`` float32 ``[B,N,3]``, its weights on
+    the face's corners.  A point with a non-finite coordinate gets ``+inf``, ``-1`` and NaN.  Faces without area count as
+    their edges.  ``chunks`` (1..64) splits the faces over that many workgroups per block of points; the bits do not
+    depend on it, and the library chooses when it is None.  Forward only: inputs are detached.  Bitwise the same on
+    every run.
+
+    ``ValueError`` for bad shapes, dtypes or face indices outside the vertices; ``FpsgHipError`` for CPU tensors."""
+    if not isinstance(points, torch.Tensor) or points.dim() not in (2, 3) or points.size(-1) != 3 or points.numel() == 0:
+        raise ValueError(f"expected [N,3] or [B,N,3] points, got {tuple(getattr(points, 'shape', ()))}")
+    if points.dtype != torch.float32:
+        raise ValueError(f"points must be float32, got {points.dtype}")
+    if chunks is not None and (isinstance(chunks, bool) or int(chunks) != chunks or
+                               not 1 <= int(chunks) <= POINT_MESH_MAX_CHUNKS):
+        raise ValueError(f"chunks must be None or an integer from 1 to {POINT_MESH_MAX_CHUNKS}, got {chunks}")
+    pts = points.detach().reshape(-1, points.size(-2), 3).contiguous()
+    B, N = pts.size(0), pts.size(1)
+    verts, faces = _batched_mesh_tensors(verts, faces)
+    per_mesh = verts.dim() == 3
+    if per_mesh and verts.size(0) != B:
+        raise ValueError(f"{verts.size(0)} meshes for {B} clouds")
+    _hip.dev_tensor(pts, torch.float32, "points")
+    dev = verts.device
+    if pts.device != dev:
+        raise ValueError(f"points are on {pts.device}, verts on {dev}")
+    V, F = verts.size(-2), faces.size(0)
+    if N > POINT_MESH_MAX_POINTS or B > POINT_MESH_MAX_MESHES or B * N > POINT_MESH_MAX_TOTAL:
+        raise ValueError(f"up to {POINT_MESH_MAX_POINTS} points per cloud, {POINT_MESH_MAX_MESHES} clouds and "
+                         f"{POINT_MESH_MAX_TOTAL} points in all are supported, got {B} x {N}")
+    lib = _hip.load()
+    c = 0 if chunks is None else int(chunks)
+    ws_bytes = lib.fpsg_point_mesh_workspace_bytes(B, N, F, c)
+    if ws_bytes == 0:
+        raise ValueError(f"unsupported shape (B={B}, N={N}, F={F}, chunks={chunks})")
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=dev)
+    dist2 = torch.empty((B, N), dtype=torch.float32, device=dev)
+    face = torch.empty((B, N), dtype=torch.int32, device=dev)
+    q = torch.empty((B, N, 3), dtype=torch.float32, device=dev) if closest else None
+    w = torch.empty((B, N, 3), dtype=torch.float32, device=dev) if bary else None
+    with torch.cuda.device(dev):
+        rc = lib.fpsg_point_mesh_distance(_hip.ptr(pts), B, N, _hip.ptr(verts), V, int(per_mesh), _hip.ptr(faces), F, c,
+                                          _hip.ptr(dist2), _hip.ptr(face), None if q is None else _hip.ptr(q),
+                                          None if w is None else _hip.ptr(w), _hip.ptr(ws), ws.numel() * 8,
+                                          _hip.stream_of(pts))
+    _hip.check(rc, "fpsg_point_mesh_distance")
+    out = {"dist2": dist2, "face": face.long()}
+    if closest:
+        out["closest"] = q
+    if bary:
+        out["bary"] = w
+    return out
+
+
+def mesh_accuracy(verts: torch.Tensor, faces: torch.Tensor, cloud: torch.Tensor, *, n_samples=None, generator=None,
+                  u=None) -> dict:
+    """How well one mesh ``(verts [V,3], faces [F,3])`` reconstructs one ground-truth ``cloud [N,3]`` -> Python floats:
+
+    - ``"completeness"``: the mean distance from the cloud's points to the surface (K32);
+    - ``"accuracy"``: the mean distance from ``n_samples`` area-weighted surface samples (K26; default: the cloud's size;
+      ``generator`` and ``u`` as in ``sample_surface``) to their nearest cloud points (K1);
+    - ``"chamfer"``: the two directions' mean squared distances, summed;
+    - ``"hausdorff"``: the larger of the two directions' largest distances.
+
+    Square roots and means are taken in float64 on the device; the four numbers come back in one read.
+    ``ValueError`` and ``FpsgHipError`` as ``point_mesh_distance`` and ``sample_surface``."""
+    from .metrics import nearest_rows
+    if not isinstance(cloud, torch.Tensor) or cloud.dim() != 2 or cloud.size(1) != 3 or cloud.size(0) < 1:
+        raise ValueError(f"expected a [N,3] cloud, got {tuple(getattr(cloud, 'shape', ()))}")
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2:
+        raise ValueError(f"expected [V,3] vertices, got {tuple(getattr(verts, 'shape', ()))}")
+    n = cloud.size(0) if n_samples is None else n_samples
+    if isinstance(n, bool) or int(n) != n or int(n) < 1:
+        raise ValueError(f"n_samples must be a positive integer, got {n_samples}")
+    cloud = cloud.detach().contiguous()
+    to_surface = point_mesh_distance(cloud, verts, faces)["dist2"][0].to(torch.float64)
+    samples, _ = sample_surface(verts, faces, int(n), generator=generator, u=u)
+    to_cloud = nearest_rows(samples.unsqueeze(0), cloud.unsqueeze(0))[0][0].to(torch.float64)
+    values = torch.stack([to_surface.sqrt().mean(), to_cloud.sqrt().mean(), to_surface.mean() + to_cloud.mean(),
+                          torch.maximum(to_surface.max(), to_cloud.max()).sqrt()]).tolist()
+    return dict(zip(("completeness", "accuracy", "chamfer", "hausdorff"), values))
 
 
 # -------------------------------------------------------------------------------------------- K29

@@ -15,13 +15,23 @@ square and neighbouring samples connected (``ImgPCProtoNet.reconstruct_mesh``). 
   ground-truth cloud as shaded spheres (K29), on one scale -- unless ``--no_sheet`` is given.
 
 ``<item>`` is the item's position in the test loader, five digits.  Prints one summary line.  Runs on a ROCm GPU only.
+
+With ``--metrics`` every generated mesh is also measured against its query's ground-truth cloud
+(``meshes.mesh_accuracy``: the points' distance to the surface by K32, the distance of ``--metrics_samples`` surface
+samples, K26, to the cloud by K1): one line per class, ``Class: <name> -- P2S: ..; S2P: ..; Mesh CD: ..; Mesh HD: ..``,
+and ``<output>/metrics.json``.
 """
 from __future__ import annotations
 
+import json
 import os
 
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")   # before the HIP runtime initialises (fpsg_amd/__init__.py)
 import sys
+
+
+METRIC_KEYS = ("completeness", "accuracy", "chamfer", "hausdorff")        # meshes.mesh_accuracy's, in the line's order
+METRIC_LABELS = ("P2S", "S2P", "Mesh CD", "Mesh HD")
 
 
 def build_parser():
@@ -34,6 +44,11 @@ def build_parser():
                    help="Samples per patch and side, 2..64: G*G vertices and 2(G-1)^2 faces per patch [default: 16];")
     g.add_argument("--max_items", type=int, default=0, metavar="N", help="Stop after N test items [default: 0 = all];")
     g.add_argument("--no_sheet", action="store_true", help="Write the .obj files only, no .png sheets;")
+    g.add_argument("--metrics", action="store_true",
+                   help="Measure every mesh against its ground-truth cloud (K32 + K26 + K1): a line per class and "
+                        "<output>/metrics.json;")
+    g.add_argument("--metrics_samples", type=int, default=None, metavar="S",
+                   help="With --metrics: surface samples per mesh [default: the cloud's size];")
     return p
 
 
@@ -52,6 +67,10 @@ def main(opt) -> int:
         raise SystemExit(f"--grid: {e}") from None
     if opt.max_items < 0:
         raise SystemExit("--max_items must not be negative")
+    if opt.metrics_samples is not None and not opt.metrics:
+        raise SystemExit("--metrics_samples needs --metrics")
+    if opt.metrics_samples is not None and opt.metrics_samples < 1:
+        raise SystemExit(f"--metrics_samples must be positive, got {opt.metrics_samples}")
     if not torch.cuda.is_available():
         raise FpsgHipError("generate_meshes.py runs on a ROCm GPU only (no CPU fallback)")
     n_query = opt.n_shot if opt.n_query == 0 else opt.n_query
@@ -73,6 +92,7 @@ def main(opt) -> int:
     face_material = surface.patch_face_material(g, n_patches)
     table = faces = None
     items, first_layer = 0, "-"
+    per_class, samples = {}, opt.metrics_samples          # --metrics: class -> one row of four means per item
     for item, sample in enumerate(dl_test):
         if opt.max_items and item >= opt.max_items:
             break
@@ -89,13 +109,33 @@ def main(opt) -> int:
         for k in range(verts.size(0)):
             meshes.write_obj_mesh(os.path.join(folder, f"{item:05d}_q{k}.obj"), host_v[k], host_f, normals=host_n[k],
                                   face_material=face_material, materials=materials, mtl_name="patches.mtl")
+        pcq = sample["pcq"].squeeze(0)
+        clouds = pcq.reshape(-1, *pcq.shape[-2:])          # the queries' ground truth, [Q, N, 3]
         if not opt.no_sheet:
-            pcq = sample["pcq"].squeeze(0)
-            sheet = render_mesh_reconstruction(verts, faces, pcq.reshape(-1, *pcq.shape[-2:]), g,
-                                               up=getattr(opt, "sample_up", "z"))
+            sheet = render_mesh_reconstruction(verts, faces, clouds, g, up=getattr(opt, "sample_up", "z"))
             write_png(os.path.join(folder, f"{item:05d}.png"), sheet)
+        if opt.metrics:
+            samples = samples or clouds.size(1)
+            draws = torch.Generator().manual_seed(item)    # on the CPU: the same numbers on every run and device
+            rows = []
+            for k in range(verts.size(0)):
+                u = torch.rand((samples, 3), generator=draws, dtype=torch.float32)
+                acc = meshes.mesh_accuracy(verts[k], faces, clouds[k], n_samples=samples, u=u)
+                rows.append([acc[name] for name in METRIC_KEYS])
+            per_class.setdefault(str(sample["class"][0]), []).append([sum(col) / len(col) for col in zip(*rows)])
         items += 1
     kernels = f"decoder first layer {first_layer}, normals K31a" + ("" if opt.no_sheet else ", views K31b + K29")
+    if opt.metrics:
+        report = {"grid": g, "samples": samples, "faces": n_patches * 2 * (g - 1) ** 2, "classes": {}}
+        for name in sorted(per_class):
+            means = [sum(col) / len(col) for col in zip(*per_class[name])]
+            report["classes"][name] = dict(zip(METRIC_KEYS, means), items=len(per_class[name]))
+            print(f"Class: {name} -- " + "; ".join(f"{label}: {v}" for label, v in zip(METRIC_LABELS, means)))
+        os.makedirs(opt.output, exist_ok=True)
+        with open(os.path.join(opt.output, "metrics.json"), "w") as f:
+            json.dump(report, f, indent=1, sort_keys=True)
+            f.write("\n")
+        kernels += ", distances K32 + K26 + K1"
     print(f"{opt.output}: {items} items x {n_query} queries, {n_patches * g * g} vertices and "
           f"{n_patches * 2 * (g - 1) ** 2} faces per mesh ({kernels})")
     return 0

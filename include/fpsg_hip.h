@@ -1446,6 +1446,56 @@ int fpsg_mesh_render_smooth(const float* verts, int V, const int32_t* faces, int
                             float* radiance, int32_t* face_id, float* depth, void* ws, size_t ws_bytes,
                             fpsg_stream_t stream);
 
+/* ---- K32: the nearest triangle of every point (point-to-mesh distance) ------------------------------
+ * For every point of B clouds the nearest point of a triangle mesh, by brute force over the faces.  The definition is
+ * the project's own (parity with published code: UNPINNED).  All pointers are device memory.
+ * points [B,N,3] fp32; verts [V,3] fp32 shared by the B clouds (verts_per_mesh = 0) or [B,V,3] (verts_per_mesh = 1);
+ * faces [F,3] int32, shared.  Outputs: dist2 [B,N] fp32, face [B,N] int32, closest [B,N,3] fp32 or NULL, bary [B,N,3]
+ * fp32 or NULL.
+ * All of the following in fp32 with every operation rounded on its own (no fma), the division correctly rounded.
+ *   dot(x, y) = (x0 y0 + x1 y1) + x2 y2;   rc(x) = 1.0f / x when x > 0 and x is finite, else 0;
+ *   clamp(t) = min(max(t, 0), 1) and least(x, y, ..) with the minimum and maximum that return the other operand when one
+ *   is NaN (fminf, fmaxf).  Vector operations are per component.
+ * Per face with corners a, b, c (indices in [0, V); a face with an index outside is skipped):
+ *   e0 = b - a;  e1 = c - a;  e2 = c - b;
+ *   d00 = dot(e0,e0);  d01 = dot(e0,e1);  d11 = dot(e1,e1);  d22 = dot(e2,e2);  det = d00 d11 - d01 d01;
+ *   r0 = rc(d00);  r1 = rc(d11);  r2 = rc(d22);  rd = rc(det).
+ * Per point p and face, four candidates, each a point of the triangle:
+ *   ap = p - a;  bp = p - b;  s0 = dot(ap,e0);  s1 = dot(ap,e1);  s2 = dot(bp,e2);
+ *   t0 = clamp(s0 r0);  q0 = a + e0 t0;     t1 = clamp(s1 r1);  q1 = a + e1 t1;     t2 = clamp(s2 r2);  q2 = b + e2 t2;
+ *   v = (d11 s0 - d01 s1) rd;  w = (d00 s1 - d01 s0) rd;  qI = a + (e0 v + e1 w),
+ *     valid only when rd > 0 and v >= 0 and w >= 0 and v + w <= 1;
+ *   d(q) = dot(p - q, p - q);   the pair's value m = least(d(q0), d(q1), d(q2), and d(qI) when valid); its candidate is
+ *   the first of q0, q1, q2, qI whose d equals m.  A candidate whose d is NaN never wins.
+ *   A sliver or a face without area (rd = 0, or v, w spoilt by cancellation) therefore degrades to the nearest point of
+ *   its edges, and a face collapsed to one point (r0 = r1 = r2 = 0, every t = 0) to the distance to that point.
+ * Per point: best = +inf, face = -1; for the faces in ascending order: m < best: best = m, face = f.  The minimum is exact,
+ *   so the lowest face id wins ties and the bits depend neither on the tiling nor on chunks.
+ *   dist2 = best;  closest = the winning pair's candidate q;  bary = its weights on (a, b, c):
+ *   q0: (1 - t0, t0, 0);  q1: (1 - t1, 0, t1);  q2: (0, 1 - t2, t2);  qI: ((1 - v) - w, v, w).
+ *   A point with a non-finite coordinate, or a mesh without a usable face, keeps dist2 = +inf and face = -1; its closest
+ *   and bary are NaN.
+ * The faces are split over `chunks` slices of ceil(F / chunks) consecutive faces (1..FPSG_POINT_MESH_MAX_CHUNKS; <= 0:
+ * the library chooses from B, N and F); every slice writes a packed 64-bit (dist2 bits << 32 | face) partial per point
+ * to the workspace (non-negative floats order as unsigned integers) and a second kernel takes their minimum in
+ * ascending order and recomputes closest and bary for the winner with the same operations.  No atomics: bitwise the
+ * same on every run.  The kernels never read outside the arrays, whatever faces holds.
+ * Workspace: fpsg_point_mesh_workspace_bytes(B, N, F, chunks) bytes, 8-byte aligned; 0 for a shape the entry refuses.
+ * Errors, all before any launch, shape and limit checks in front of the pointer checks: FPSG_E_SHAPE for B, N, V or
+ * F < 1, verts_per_mesh not 0 or 1 or a workspace too small; FPSG_E_LIMIT for N > FPSG_POINT_MESH_MAX_POINTS, B >
+ * FPSG_POINT_MESH_MAX_MESHES, B N > FPSG_POINT_MESH_MAX_TOTAL, V or F > FPSG_MESH_MAX_FACES or chunks >
+ * FPSG_POINT_MESH_MAX_CHUNKS; FPSG_E_NULL for a null points, verts, faces, dist2, face or ws; FPSG_E_ALIGN for a
+ * misaligned pointer (ws: 8 bytes).
+ */
+#define FPSG_POINT_MESH_MAX_POINTS (1 << 20)
+#define FPSG_POINT_MESH_MAX_MESHES 65535
+#define FPSG_POINT_MESH_MAX_TOTAL (1 << 26)
+#define FPSG_POINT_MESH_MAX_CHUNKS 64
+size_t fpsg_point_mesh_workspace_bytes(int B, int N, int F, int chunks);
+int fpsg_point_mesh_distance(const float* points, int B, int N, const float* verts, int V, int verts_per_mesh,
+                             const int32_t* faces, int F, int chunks, float* dist2, int32_t* face, float* closest,
+                             float* bary, void* ws, size_t ws_bytes, fpsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
