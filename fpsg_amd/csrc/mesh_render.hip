@@ -8,11 +8,13 @@
 //     the thread, a larger one is appended to a list;
 //   * render_raster_large_kernel: a fixed grid strides over the list's entries, kChunks waves each, lanes over the
 //     bounding box's pixels;
-//   * render_shade_kernel: one output pixel per thread: its ssaa^2 samples shaded and composited over the background.
-// K28 (fpsg_mesh_render_materials) runs the same three kernels and then render_shade_materials_kernel, K27's shade
-// pass with a base colour per face: a material's Kd, or its texture looked up at the sample's interpolated uv.
-// K31b (fpsg_mesh_render_smooth) is K28 with the light's terms taken from a normal interpolated between the face's three
-// corner normals (the SMOOTH instantiation of the same shade kernel) in place of the face's own.
+//   * render_shade_kernel<FLAT>: one output pixel per thread: its ssaa^2 samples shaded and composited over the
+//     background.
+// K28 (fpsg_mesh_render_materials) and K31b (fpsg_mesh_render_smooth) are the same entry (render_entry), the same three
+// kernels and two more instantiations of the shade kernel.  MATERIALS: a base colour per face, a material's Kd or its
+// texture looked up at the sample's interpolated uv.  SMOOTH: that, with the light's terms taken from a normal
+// interpolated between the face's three corner normals in place of the face's own.  The light's terms, the colours and
+// the resolve are render_common.h's, shared with K29.
 #include "render_common.h"
 
 namespace fpsg {
@@ -146,78 +148,28 @@ __global__ __launch_bounds__(256) void render_raster_large_kernel(const int* __r
   }
 }
 
-__global__ __launch_bounds__(256) void render_shade_kernel(const float* __restrict__ verts,
-                                                           const int* __restrict__ faces,
-                                                           const float* __restrict__ views,
-                                                           const u64* __restrict__ zbuf, int W, int H, int ssaa,
-                                                           RenderParams P, const unsigned char* __restrict__ bg_img,
-                                                           unsigned char* __restrict__ image,
-                                                           float* __restrict__ radiance, int* __restrict__ face_id,
-                                                           float* __restrict__ depth) {
-  const int ow = W / ssaa, oh = H / ssaa;
-  const int ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (ox >= ow || oy >= oh) return;
-  const int view = blockIdx.z;
-  const float* M = views + (size_t)view * 12;
-  const u64* z0 = zbuf + (size_t)view * W * H;
-  float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f;
-  int covered = 0;
-  for (int sy = 0; sy < ssaa; ++sy) {
-    for (int sx = 0; sx < ssaa; ++sx) {
-      const int i = ox * ssaa + sx, j = oy * ssaa + sy;
-      const size_t pix = (size_t)j * W + i;
-      const u64 key = z0[pix];
-      const bool hit = key != kEmpty;
-      if (face_id) face_id[(size_t)view * W * H + pix] = hit ? (int)(unsigned)key : -1;
-      if (depth) depth[(size_t)view * W * H + pix] = hit ? key_depth((unsigned)(key >> 32)) : __builtin_inff();
-      if (!hit) continue;
-      const unsigned f = (unsigned)key;                // written by the rasteriser: a face with indices in range
-      const float* a = verts + (size_t)faces[(size_t)f * 3] * 3;
-      const float* b = verts + (size_t)faces[(size_t)f * 3 + 1] * 3;
-      const float* c = verts + (size_t)faces[(size_t)f * 3 + 2] * 3;
-      // world-space edges turned into the camera frame: no cancellation against the camera's distance
-      const float w1x = b[0] - a[0], w1y = b[1] - a[1], w1z = b[2] - a[2];
-      const float w2x = c[0] - a[0], w2y = c[1] - a[1], w2z = c[2] - a[2];
-      const float e1x = (w1x * M[0] + w1y * M[1]) + w1z * M[2], e1y = (w1x * M[3] + w1y * M[4]) + w1z * M[5],
-                  e1z = (w1x * M[6] + w1y * M[7]) + w1z * M[8];
-      const float e2x = (w2x * M[0] + w2y * M[1]) + w2z * M[2], e2y = (w2x * M[3] + w2y * M[4]) + w2z * M[5],
-                  e2z = (w2x * M[6] + w2y * M[7]) + w2z * M[8];
-      float nx = e1y * e2z - e1z * e2y;
-      float ny = e1z * e2x - e1x * e2z;
-      float nz = e1x * e2y - e1y * e2x;
-      const float len = __builtin_sqrtf((nx * nx + ny * ny) + nz * nz);
-      if (len > 0.0f && finite_f(len)) { nx = nx / len; ny = ny / len; nz = nz / len; }
-      else { nx = 0.0f; ny = 0.0f; nz = -1.0f; }
-      if (nz > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }   // two-sided: towards the camera, which looks along +z
-      const float ndl = (nx * P.light[0] + ny * P.light[1]) + nz * P.light[2];
-      const float diff = __builtin_fmaxf(ndl, 0.0f);
-      // r = 2 (n.l) n - l, v = (0, 0, -1): r.v = l_z - 2 (n.l) n_z
-      float spec = ndl > 0.0f ? __builtin_fmaxf(P.light[2] - (2.0f * ndl) * nz, 0.0f) : 0.0f;
-      for (int k = 0; k < P.log2_shininess; ++k) spec = spec * spec;
-      acc0 += (P.ka[0] + P.kd[0] * diff) + P.ks[0] * spec;
-      acc1 += (P.ka[1] + P.kd[1] * diff) + P.ks[1] * spec;
-      acc2 += (P.ka[2] + P.kd[2] * diff) + P.ks[2] * spec;
-      ++covered;
-    }
-  }
-  const float inv = 1.0f / (float)(ssaa * ssaa);
-  const float rest = 1.0f - (float)covered * inv;
-  const size_t o = (((size_t)view * oh + oy) * ow + ox) * 3;
-  float bg0 = P.bg[0], bg1 = P.bg[1], bg2 = P.bg[2];
-  if (bg_img) {
-    const unsigned char* q = bg_img + ((size_t)oy * ow + ox) * 3;
-    bg0 = (float)q[0] / 255.0f; bg1 = (float)q[1] / 255.0f; bg2 = (float)q[2] / 255.0f;
-  }
-  const float r0 = acc0 * inv + bg0 * rest, r1 = acc1 * inv + bg1 * rest, r2 = acc2 * inv + bg2 * rest;
-  if (radiance) { radiance[o] = r0; radiance[o + 1] = r1; radiance[o + 2] = r2; }
-  if (image) {
-    image[o] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r0, 0.0f), 1.0f) * 255.0f);
-    image[o + 1] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r1, 0.0f), 1.0f) * 255.0f);
-    image[o + 2] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r2, 0.0f), 1.0f) * 255.0f);
-  }
+// ---- the shade pass: K27's flat Phong, K28's materials and textures, K31b's interpolated normals -----------------
+// The unit normal of the face (a, b, c) in the frame of the view M, towards the camera, which looks along +z (both
+// sides of a face are lit); (0, 0, -1) for a face without area.
+__device__ __forceinline__ void face_normal_cam(const float* __restrict__ a, const float* __restrict__ b,
+                                                const float* __restrict__ c, const float* __restrict__ M, float& nx,
+                                                float& ny, float& nz) {
+  // world-space edges turned into the camera frame: no cancellation against the camera's distance
+  const float w1x = b[0] - a[0], w1y = b[1] - a[1], w1z = b[2] - a[2];
+  const float w2x = c[0] - a[0], w2y = c[1] - a[1], w2z = c[2] - a[2];
+  const float e1x = (w1x * M[0] + w1y * M[1]) + w1z * M[2], e1y = (w1x * M[3] + w1y * M[4]) + w1z * M[5],
+              e1z = (w1x * M[6] + w1y * M[7]) + w1z * M[8];
+  const float e2x = (w2x * M[0] + w2y * M[1]) + w2z * M[2], e2y = (w2x * M[3] + w2y * M[4]) + w2z * M[5],
+              e2z = (w2x * M[6] + w2y * M[7]) + w2z * M[8];
+  nx = e1y * e2z - e1z * e2y;
+  ny = e1z * e2x - e1x * e2z;
+  nz = e1x * e2y - e1y * e2x;
+  const float len = __builtin_sqrtf((nx * nx + ny * ny) + nz * nz);
+  if (len > 0.0f && finite_f(len)) { nx = nx / len; ny = ny / len; nz = nz / len; }
+  else { nx = 0.0f; ny = 0.0f; nz = -1.0f; }
+  if (nz > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
 }
 
-// ---- K28: the shade pass with materials and textures ------------------------------------------------------------
 struct MaterialTables {
   const int* face_material;              // [F], outside [0, M): no material
   const v4f* materials;                  // [M]: Kd and the texture index (validated by the entry: -1 or in [0, T))
@@ -285,9 +237,15 @@ __device__ __forceinline__ Bary sample_bary(const v4i* __restrict__ snap_v, int 
   return r;
 }
 
-// SMOOTH (K31b): the light's terms from the normal interpolated between face_normals [F,3,3], which K28 does not read
-template <bool SMOOTH>
-__global__ __launch_bounds__(256) void render_shade_materials_kernel(
+// One output pixel per thread: its ssaa^2 samples shaded and composited over the background.
+//   FLAT (K27): the face's normal and the colour in ka, kd.  It reads neither snapped, T, face_normals nor
+//     Q.ambient / Q.diffuse: the K27 entry has none of them to give.
+//   MATERIALS (K28): a face with a material takes its base colour from the material's Kd or texture.
+//   SMOOTH (K31b): K28 with the light's terms from the normal interpolated between face_normals [F,3,3].
+enum Shade { FLAT, MATERIALS, SMOOTH };
+
+template <Shade MODE>
+__global__ __launch_bounds__(256) void render_shade_kernel(
     const float* __restrict__ verts, const int* __restrict__ faces, int V, const float* __restrict__ views,
     const v4i* __restrict__ snapped, const u64* __restrict__ zbuf, int W, int H, int ssaa, MaterialParams Q,
     MaterialTables T, const float* __restrict__ face_normals, const unsigned char* __restrict__ bg_img,
@@ -314,25 +272,10 @@ __global__ __launch_bounds__(256) void render_shade_materials_kernel(
       if (!hit) continue;
       const unsigned f = (unsigned)key;                // written by the rasteriser: a face with indices in range
       const int ia = faces[(size_t)f * 3], ib = faces[(size_t)f * 3 + 1], ic = faces[(size_t)f * 3 + 2];
-      const float* a = verts + (size_t)ia * 3;
-      const float* b = verts + (size_t)ib * 3;
-      const float* c = verts + (size_t)ic * 3;
-      // the light's terms: K27's, operation for operation
-      const float w1x = b[0] - a[0], w1y = b[1] - a[1], w1z = b[2] - a[2];
-      const float w2x = c[0] - a[0], w2y = c[1] - a[1], w2z = c[2] - a[2];
-      const float e1x = (w1x * M[0] + w1y * M[1]) + w1z * M[2], e1y = (w1x * M[3] + w1y * M[4]) + w1z * M[5],
-                  e1z = (w1x * M[6] + w1y * M[7]) + w1z * M[8];
-      const float e2x = (w2x * M[0] + w2y * M[1]) + w2z * M[2], e2y = (w2x * M[3] + w2y * M[4]) + w2z * M[5],
-                  e2z = (w2x * M[6] + w2y * M[7]) + w2z * M[8];
-      float nx = e1y * e2z - e1z * e2y;
-      float ny = e1z * e2x - e1x * e2z;
-      float nz = e1x * e2y - e1y * e2x;
-      const float len = __builtin_sqrtf((nx * nx + ny * ny) + nz * nz);
-      if (len > 0.0f && finite_f(len)) { nx = nx / len; ny = ny / len; nz = nz / len; }
-      else { nx = 0.0f; ny = 0.0f; nz = -1.0f; }
-      if (nz > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
+      float nx, ny, nz;
+      face_normal_cam(verts + (size_t)ia * 3, verts + (size_t)ib * 3, verts + (size_t)ic * 3, M, nx, ny, nz);
       Bary L = {0.0f, 0.0f, 0.0f, false};
-      if constexpr (SMOOTH) {
+      if constexpr (MODE == SMOOTH) {
         // the corner normals interpolated in world space, turned into the camera frame like the edges, normalised,
         // and put on the side of the face that the camera sees; without a usable length the face's own normal stays
         L = sample_bary(snap_v, ia, ib, ic, i, j);
@@ -352,58 +295,39 @@ __global__ __launch_bounds__(256) void render_shade_materials_kernel(
           nx = cx; ny = cy; nz = cz;
         }
       }
-      const float ndl = (nx * P.light[0] + ny * P.light[1]) + nz * P.light[2];
-      const float diff = __builtin_fmaxf(ndl, 0.0f);
-      float spec = ndl > 0.0f ? __builtin_fmaxf(P.light[2] - (2.0f * ndl) * nz, 0.0f) : 0.0f;
-      for (int k = 0; k < P.log2_shininess; ++k) spec = spec * spec;
-      ++covered;
-      const int m = T.M > 0 ? T.face_material[f] : -1;
-      if ((unsigned)m >= (unsigned)T.M) {              // no material: K27's colour
-        acc0 += (P.ka[0] + P.kd[0] * diff) + P.ks[0] * spec;
-        acc1 += (P.ka[1] + P.kd[1] * diff) + P.ks[1] * spec;
-        acc2 += (P.ka[2] + P.kd[2] * diff) + P.ks[2] * spec;
-        continue;
-      }
-      const v4f mat = T.materials[m];
-      float b0 = mat.x, b1 = mat.y, b2 = mat.z;
-      const int tex = (int)mat.w;
-      if (tex >= 0) {
-        const float* q = T.face_uv + (size_t)f * 6;
-        float u0 = q[0], v0 = q[1], u1 = q[2], v1 = q[3], u2 = q[4], v2 = q[5];
-        if (finite_f(u0) && finite_f(v0) && finite_f(u1) && finite_f(v1) && finite_f(u2) && finite_f(v2)) {
-          if constexpr (!SMOOTH) L = sample_bary(snap_v, ia, ib, ic, i, j);
-          if (L.swap) {                                // the rasteriser's swap, and the uv with the corners
-            float t = u1; u1 = u2; u2 = t;
-            t = v1; v1 = v2; v2 = t;
+      float diff, spec, c0, c1, c2;
+      light_terms(P, nx, ny, nz, diff, spec);
+      int m = -1;
+      if constexpr (MODE != FLAT) m = T.M > 0 ? T.face_material[f] : -1;
+      if (MODE == FLAT || (unsigned)m >= (unsigned)T.M) {   // no material
+        phong_color(P, diff, spec, c0, c1, c2);
+      } else {
+        const v4f mat = T.materials[m];
+        float b0 = mat.x, b1 = mat.y, b2 = mat.z;
+        const int tex = (int)mat.w;
+        if (tex >= 0) {
+          const float* q = T.face_uv + (size_t)f * 6;
+          float u0 = q[0], v0 = q[1], u1 = q[2], v1 = q[3], u2 = q[4], v2 = q[5];
+          if (finite_f(u0) && finite_f(v0) && finite_f(u1) && finite_f(v1) && finite_f(u2) && finite_f(v2)) {
+            if constexpr (MODE != SMOOTH) L = sample_bary(snap_v, ia, ib, ic, i, j);
+            if (L.swap) {                              // the rasteriser's swap, and the uv with the corners
+              float t = u1; u1 = u2; u2 = t;
+              t = v1; v1 = v2; v2 = t;
+            }
+            const float u = (L.l0 * u0 + L.l1 * u1) + L.l2 * u2;
+            const float v = (L.l0 * v0 + L.l1 * v1) + L.l2 * v2;
+            const int* e = T.tex_table + (size_t)tex * 3;
+            texel_lookup(T.texels + (size_t)e[0] * 3, e[1], e[2], u, v, b0, b1, b2);
           }
-          const float u = (L.l0 * u0 + L.l1 * u1) + L.l2 * u2;
-          const float v = (L.l0 * v0 + L.l1 * v1) + L.l2 * v2;
-          const int* e = T.tex_table + (size_t)tex * 3;
-          texel_lookup(T.texels + (size_t)e[0] * 3, e[1], e[2], u, v, b0, b1, b2);
         }
+        phong_color(Q, b0, b1, b2, diff, spec, c0, c1, c2);
       }
-      const float a0 = Q.ambient * b0, a1 = Q.ambient * b1, a2 = Q.ambient * b2;
-      const float d0 = Q.diffuse * b0, d1 = Q.diffuse * b1, d2 = Q.diffuse * b2;
-      acc0 += (a0 + d0 * diff) + P.ks[0] * spec;
-      acc1 += (a1 + d1 * diff) + P.ks[1] * spec;
-      acc2 += (a2 + d2 * diff) + P.ks[2] * spec;
+      acc0 += c0; acc1 += c1; acc2 += c2;
+      ++covered;
     }
   }
-  const float inv = 1.0f / (float)(ssaa * ssaa);
-  const float rest = 1.0f - (float)covered * inv;
-  const size_t o = (((size_t)view * oh + oy) * ow + ox) * 3;
-  float bg0 = P.bg[0], bg1 = P.bg[1], bg2 = P.bg[2];
-  if (bg_img) {
-    const unsigned char* q = bg_img + ((size_t)oy * ow + ox) * 3;
-    bg0 = (float)q[0] / 255.0f; bg1 = (float)q[1] / 255.0f; bg2 = (float)q[2] / 255.0f;
-  }
-  const float r0 = acc0 * inv + bg0 * rest, r1 = acc1 * inv + bg1 * rest, r2 = acc2 * inv + bg2 * rest;
-  if (radiance) { radiance[o] = r0; radiance[o + 1] = r1; radiance[o + 2] = r2; }
-  if (image) {
-    image[o] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r0, 0.0f), 1.0f) * 255.0f);
-    image[o + 1] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r1, 0.0f), 1.0f) * 255.0f);
-    image[o + 2] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r2, 0.0f), 1.0f) * 255.0f);
-  }
+  resolve_pixel(acc0, acc1, acc2, covered, ssaa, P, bg_img, (size_t)oy * ow + ox,
+                (((size_t)view * oh + oy) * ow + ox) * 3, radiance, image);
 }
 
 struct RenderWs {
@@ -422,7 +346,8 @@ inline RenderWs render_ws(int V, int F, int NV, int W, int H) {
   return w;
 }
 
-// K28's workspace: K27's, then the material and texture tables copied from the host
+// K28's workspace: K27's, then the material and texture tables copied from the host; nothing more for M = T = 0, so
+// K27's size is this one's
 struct MaterialWs {
   size_t materials, tex_table, total;
 };
@@ -449,90 +374,20 @@ inline bool render_limit_ok(int F, int NV, int W, int H) {
          (uint64_t)F * (uint64_t)NV <= 0x7fffffffull;
 }
 
-}  // namespace
-}  // namespace fpsg
-
-extern "C" size_t fpsg_mesh_render_workspace_bytes(int V, int F, int n_views, int W, int H) {
-  using namespace fpsg;
-  if (!render_shape_ok(V, F, n_views, W, H, 1) || !render_limit_ok(F, n_views, W, H)) return 0;
-  return render_ws(V, F, n_views, W, H).total;
-}
-
-extern "C" int fpsg_mesh_render(const float* verts, int V, const int32_t* faces, int F, const float* views,
-                                int n_views, int W, int H, int ssaa, float ortho_scale, const float* params,
-                                int log2_shininess, const uint8_t* bg_image, uint8_t* image, float* radiance,
-                                int32_t* face_id, float* depth, void* ws, size_t ws_bytes, fpsg_stream_t stream) {
-  using namespace fpsg;
-  FPSG_REQUIRE(render_shape_ok(V, F, n_views, W, H, ssaa), FPSG_E_SHAPE,
-               "fpsg_mesh_render: V,F,n_views,W,H must be positive, ssaa from 1 to %d and a divisor of W and H "
-               "(got %d,%d,%d,%d,%d,%d)", FPSG_RENDER_MAX_SSAA, V, F, n_views, W, H, ssaa);
-  FPSG_REQUIRE(ortho_scale > 0.0f && ortho_scale <= 3.0e38f, FPSG_E_SHAPE,
-               "fpsg_mesh_render: ortho_scale must be positive and finite");
-  FPSG_REQUIRE(log2_shininess >= 0 && log2_shininess <= FPSG_RENDER_MAX_LOG2_SHININESS, FPSG_E_SHAPE,
-               "fpsg_mesh_render: log2_shininess must be from 0 to %d (got %d)", FPSG_RENDER_MAX_LOG2_SHININESS,
-               log2_shininess);
-  FPSG_REQUIRE(render_limit_ok(F, n_views, W, H), FPSG_E_LIMIT,
-               "fpsg_mesh_render: W,H <= %d, n_views <= %d and F n_views < 2^31 are supported (got %d,%d,%d,%d)",
-               FPSG_RENDER_MAX_SIZE, FPSG_RENDER_MAX_VIEWS, W, H, n_views, F);
-  FPSG_REQUIRE_PTR(verts); FPSG_REQUIRE_PTR(faces); FPSG_REQUIRE_PTR(views); FPSG_REQUIRE_PTR(ws);
-  FPSG_REQUIRE(params != nullptr, FPSG_E_NULL, "fpsg_mesh_render: null pointer 'params'");
-  FPSG_REQUIRE(image || radiance || face_id || depth, FPSG_E_NULL, "fpsg_mesh_render: no output requested");
-  FPSG_REQUIRE(!misaligned4(radiance) && !misaligned4(face_id) && !misaligned4(depth), FPSG_E_ALIGN,
-               "fpsg_mesh_render: an output is not 4-byte aligned");
-  FPSG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15u) == 0, FPSG_E_ALIGN, "fpsg_mesh_render: 'ws' must be 16-byte aligned");
-  const RenderWs L = render_ws(V, F, n_views, W, H);
-  FPSG_REQUIRE(ws_bytes >= L.total, FPSG_E_SHAPE, "fpsg_mesh_render: workspace of %zu bytes, %zu needed", ws_bytes,
-               L.total);
-  RenderParams P;
-  unpack_render_params(params, log2_shininess, P);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  v4f* cam = reinterpret_cast<v4f*>(base + L.cam);
-  v4i* snapped = reinterpret_cast<v4i*>(base + L.snapped);
-  u64* zbuf = reinterpret_cast<u64*>(base + L.zbuf);
-  unsigned* list = reinterpret_cast<unsigned*>(base + L.list);
-  unsigned* counter = reinterpret_cast<unsigned*>(base + L.counter);
-  hipError_t e = hipMemsetAsync(zbuf, 0xff, (size_t)n_views * W * H * 8, st);
-  if (e == hipSuccess) e = hipMemsetAsync(counter, 0, 16, st);
-  if (e != hipSuccess) { set_error("fpsg_mesh_render: %s", hipGetErrorString(e)); return (int)e; }
-  hipLaunchKernelGGL(render_project_kernel, dim3((unsigned)((V + 255) / 256), (unsigned)n_views), dim3(256), 0, st,
-                     verts, V, views, ortho_scale, W, H, cam, snapped);
-  hipLaunchKernelGGL(render_raster_kernel, dim3((unsigned)((F + 255) / 256), (unsigned)n_views), dim3(256), 0, st,
-                     faces, F, V, cam, snapped, W, H, zbuf, list, counter);
-  // a fixed grid strides over the list, whose length only the device knows
-  hipLaunchKernelGGL(render_raster_large_kernel, dim3(1024), dim3(256), 0, st, faces, F, V, cam, snapped, W, H, zbuf,
-                     list, counter, (unsigned)n_views);
-  const int ow = W / ssaa, oh = H / ssaa;
-  hipLaunchKernelGGL(render_shade_kernel, dim3((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4), (unsigned)n_views),
-                     dim3(256), 0, st, verts, faces, views, zbuf, W, H, ssaa, P, bg_image, image, radiance, face_id, depth);
-  return launch_status("fpsg_mesh_render");
-}
-
-extern "C" size_t fpsg_mesh_render_materials_workspace_bytes(int V, int F, int n_views, int W, int H, int M, int T) {
-  using namespace fpsg;
-  if (!render_shape_ok(V, F, n_views, W, H, 1) || !render_limit_ok(F, n_views, W, H) || M < 0 || T < 0 ||
-      !material_limit_ok(M, T, 0))
-    return 0;
-  return material_ws(render_ws(V, F, n_views, W, H), M, T).total;
-}
-
-namespace fpsg {
-namespace {
-
-#define RENDER_REQUIRE_PTR(p)                                                                      \
+#define RENDER_REQUIRE_PTR(p)                                                                     \
   do {                                                                                             \
     FPSG_REQUIRE((p) != nullptr, FPSG_E_NULL, "%s: null pointer '%s'", fn, #p);                    \
     FPSG_REQUIRE(!misaligned4(p), FPSG_E_ALIGN, "%s: '%s' not 4-byte aligned", fn, #p);            \
   } while (0)
 
-// K28's entry and K31b's: the same checks, workspace and launches; smooth selects the shade pass that reads face_normals
-int render_materials_entry(const char* fn, bool smooth, const float* verts, int V, const int32_t* faces, int F,
-                           const int32_t* face_material, const float* face_uv, const float* face_normals,
-                           const float* materials, int M, const int32_t* tex_table, int T, const uint8_t* texels,
-                           long long n_texels, const float* views, int n_views, int W, int H, int ssaa,
-                           float ortho_scale, const float* params, int log2_shininess, const uint8_t* bg_image,
-                           uint8_t* image, float* radiance, int32_t* face_id, float* depth, void* ws, size_t ws_bytes,
-                           fpsg_stream_t stream) {
+// The entry of K27, K28 and K31b: the same checks, workspace and launches; mode selects the shade pass.  K27 comes
+// with M = T = 0, no tables and 15 floats in params; face_normals is K31b's alone.
+int render_entry(const char* fn, Shade mode, const float* verts, int V, const int32_t* faces, int F,
+                 const int32_t* face_material, const float* face_uv, const float* face_normals, const float* materials,
+                 int M, const int32_t* tex_table, int T, const uint8_t* texels, long long n_texels, const float* views,
+                 int n_views, int W, int H, int ssaa, float ortho_scale, const float* params, int log2_shininess,
+                 const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* face_id, float* depth, void* ws,
+                 size_t ws_bytes, fpsg_stream_t stream) {
   FPSG_REQUIRE(render_shape_ok(V, F, n_views, W, H, ssaa), FPSG_E_SHAPE,
                "%s: V,F,n_views,W,H must be positive, ssaa from 1 to %d and a divisor of W "
                "and H (got %d,%d,%d,%d,%d,%d)", fn, FPSG_RENDER_MAX_SSAA, V, F, n_views, W, H, ssaa);
@@ -552,7 +407,7 @@ int render_materials_entry(const char* fn, bool smooth, const float* verts, int 
   FPSG_REQUIRE(params != nullptr, FPSG_E_NULL, "%s: null pointer 'params'", fn);
   if (M > 0) { RENDER_REQUIRE_PTR(face_material); RENDER_REQUIRE_PTR(materials); }
   if (T > 0) { RENDER_REQUIRE_PTR(face_uv); RENDER_REQUIRE_PTR(tex_table); }
-  if (smooth) RENDER_REQUIRE_PTR(face_normals);
+  if (mode == SMOOTH) RENDER_REQUIRE_PTR(face_normals);
   FPSG_REQUIRE(T == 0 || texels != nullptr, FPSG_E_NULL, "%s: null pointer 'texels'", fn);
   FPSG_REQUIRE(image || radiance || face_id || depth, FPSG_E_NULL, "%s: no output requested", fn);
   FPSG_REQUIRE(!misaligned4(radiance) && !misaligned4(face_id) && !misaligned4(depth), FPSG_E_ALIGN,
@@ -572,9 +427,9 @@ int render_materials_entry(const char* fn, bool smooth, const float* verts, int 
   const RenderWs L = render_ws(V, F, n_views, W, H);
   const MaterialWs LM = material_ws(L, M, T);
   FPSG_REQUIRE(ws_bytes >= LM.total, FPSG_E_SHAPE, "%s: workspace of %zu bytes, %zu needed", fn, ws_bytes, LM.total);
-  MaterialParams Q;
-  unpack_render_params(params, log2_shininess, Q.base);
-  Q.ambient = params[15]; Q.diffuse = params[16];
+  MaterialParams Q = {};
+  if (mode == FLAT) unpack_render_params(params, log2_shininess, Q.base);
+  else unpack_material_params(params, log2_shininess, Q);
   hipStream_t st = static_cast<hipStream_t>(stream);
   char* base = static_cast<char*>(ws);
   v4f* cam = reinterpret_cast<v4f*>(base + L.cam);
@@ -601,22 +456,42 @@ int render_materials_entry(const char* fn, bool smooth, const float* verts, int 
                      verts, V, views, ortho_scale, W, H, cam, snapped);
   hipLaunchKernelGGL(render_raster_kernel, dim3((unsigned)((F + 255) / 256), (unsigned)n_views), dim3(256), 0, st,
                      faces, F, V, cam, snapped, W, H, zbuf, list, counter);
+  // a fixed grid strides over the list, whose length only the device knows
   hipLaunchKernelGGL(render_raster_large_kernel, dim3(1024), dim3(256), 0, st, faces, F, V, cam, snapped, W, H, zbuf,
                      list, counter, (unsigned)n_views);
   const int ow = W / ssaa, oh = H / ssaa;
   const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4), (unsigned)n_views);
-  if (smooth)
-    hipLaunchKernelGGL(render_shade_materials_kernel<true>, grid, dim3(256), 0, st, verts, faces, V, views, snapped,
-                       zbuf, W, H, ssaa, Q, TB, face_normals, bg_image, image, radiance, face_id, depth);
-  else
-    hipLaunchKernelGGL(render_shade_materials_kernel<false>, grid, dim3(256), 0, st, verts, faces, V, views, snapped,
-                       zbuf, W, H, ssaa, Q, TB, face_normals, bg_image, image, radiance, face_id, depth);
+  const auto shade = mode == FLAT ? render_shade_kernel<FLAT>
+                     : mode == SMOOTH ? render_shade_kernel<SMOOTH> : render_shade_kernel<MATERIALS>;
+  hipLaunchKernelGGL(shade, grid, dim3(256), 0, st, verts, faces, V, views, snapped, zbuf, W, H, ssaa, Q, TB,
+                     face_normals, bg_image, image, radiance, face_id, depth);
   return launch_status(fn);
 }
 #undef RENDER_REQUIRE_PTR
 
 }  // namespace
 }  // namespace fpsg
+
+extern "C" size_t fpsg_mesh_render_materials_workspace_bytes(int V, int F, int n_views, int W, int H, int M, int T) {
+  using namespace fpsg;
+  if (!render_shape_ok(V, F, n_views, W, H, 1) || !render_limit_ok(F, n_views, W, H) || M < 0 || T < 0 ||
+      !material_limit_ok(M, T, 0))
+    return 0;
+  return material_ws(render_ws(V, F, n_views, W, H), M, T).total;
+}
+
+extern "C" size_t fpsg_mesh_render_workspace_bytes(int V, int F, int n_views, int W, int H) {
+  return fpsg_mesh_render_materials_workspace_bytes(V, F, n_views, W, H, 0, 0);   // material_ws adds nothing
+}
+
+extern "C" int fpsg_mesh_render(const float* verts, int V, const int32_t* faces, int F, const float* views,
+                                int n_views, int W, int H, int ssaa, float ortho_scale, const float* params,
+                                int log2_shininess, const uint8_t* bg_image, uint8_t* image, float* radiance,
+                                int32_t* face_id, float* depth, void* ws, size_t ws_bytes, fpsg_stream_t stream) {
+  return fpsg::render_entry("fpsg_mesh_render", fpsg::FLAT, verts, V, faces, F, nullptr, nullptr, nullptr, nullptr, 0,
+                            nullptr, 0, nullptr, 0, views, n_views, W, H, ssaa, ortho_scale, params, log2_shininess,
+                            bg_image, image, radiance, face_id, depth, ws, ws_bytes, stream);
+}
 
 extern "C" int fpsg_mesh_render_materials(const float* verts, int V, const int32_t* faces, int F,
                                           const int32_t* face_material, const float* face_uv, const float* materials,
@@ -625,10 +500,10 @@ extern "C" int fpsg_mesh_render_materials(const float* verts, int V, const int32
                                           float ortho_scale, const float* params, int log2_shininess,
                                           const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* face_id,
                                           float* depth, void* ws, size_t ws_bytes, fpsg_stream_t stream) {
-  return fpsg::render_materials_entry("fpsg_mesh_render_materials", false, verts, V, faces, F, face_material, face_uv,
-                                      nullptr, materials, M, tex_table, T, texels, n_texels, views, n_views, W, H, ssaa,
-                                      ortho_scale, params, log2_shininess, bg_image, image, radiance, face_id, depth, ws,
-                                      ws_bytes, stream);
+  return fpsg::render_entry("fpsg_mesh_render_materials", fpsg::MATERIALS, verts, V, faces, F, face_material, face_uv,
+                            nullptr, materials, M, tex_table, T, texels, n_texels, views, n_views, W, H, ssaa,
+                            ortho_scale, params, log2_shininess, bg_image, image, radiance, face_id, depth, ws, ws_bytes,
+                            stream);
 }
 
 extern "C" size_t fpsg_mesh_render_smooth_workspace_bytes(int V, int F, int n_views, int W, int H, int M, int T) {
@@ -642,8 +517,8 @@ extern "C" int fpsg_mesh_render_smooth(const float* verts, int V, const int32_t*
                                        int H, int ssaa, float ortho_scale, const float* params, int log2_shininess,
                                        const uint8_t* bg_image, uint8_t* image, float* radiance, int32_t* face_id,
                                        float* depth, void* ws, size_t ws_bytes, fpsg_stream_t stream) {
-  return fpsg::render_materials_entry("fpsg_mesh_render_smooth", true, verts, V, faces, F, face_material, face_uv,
-                                      face_normals, materials, M, tex_table, T, texels, n_texels, views, n_views, W, H,
-                                      ssaa, ortho_scale, params, log2_shininess, bg_image, image, radiance, face_id,
-                                      depth, ws, ws_bytes, stream);
+  return fpsg::render_entry("fpsg_mesh_render_smooth", fpsg::SMOOTH, verts, V, faces, F, face_material, face_uv,
+                            face_normals, materials, M, tex_table, T, texels, n_texels, views, n_views, W, H, ssaa,
+                            ortho_scale, params, log2_shininess, bg_image, image, radiance, face_id, depth, ws, ws_bytes,
+                            stream);
 }

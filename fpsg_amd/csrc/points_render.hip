@@ -1,6 +1,7 @@
 // points_render.hip -- K29: orthographic Phong views of point clouds, every point a small sphere, for gfx950.  The
 // definition is in include/fpsg_hip.h (K29) and DESIGN.md: K27's projection and snap per point, coverage by an integer
-// circle test, the sphere's depth per sample, a 64-bit (depth, point) minimum per sample, K27's resolve.
+// circle test, the sphere's depth per sample, a 64-bit (depth, point) minimum per sample, K27's resolve.  The light's
+// terms, the colours and the resolve are render_common.h's, the ones the mesh renderers run.
 //
 // Structure: the z-buffer never leaves the chip.
 //   * points_project_kernel: one (cloud, view, point) per thread -> one 16-byte record (X, Y, depth bits, colour and
@@ -119,29 +120,18 @@ __global__ __launch_bounds__(256) void points_tile_kernel(const v4i* __restrict_
     float c;
     sphere_at(r.x, r.y, 256 * i + 128, 256 * j + 128, R2, fR2, dx, dy, c);
     const float nx = (float)dx / fR, ny = -((float)dy / fR), nz = -c;
-    const float ndl = (nx * P.light[0] + ny * P.light[1]) + nz * P.light[2];
-    const float diff = __builtin_fmaxf(ndl, 0.0f);
-    float spec = ndl > 0.0f ? __builtin_fmaxf(P.light[2] - (2.0f * ndl) * nz, 0.0f) : 0.0f;
-    for (int k = 0; k < P.log2_shininess; ++k) spec = spec * spec;
-    if (COLORS) {
-      const float b0 = (float)(r.w & 255) / 255.0f, b1 = (float)((r.w >> 8) & 255) / 255.0f,
-                  b2 = (float)((r.w >> 16) & 255) / 255.0f;
-      const float a0 = Q.ambient * b0, a1 = Q.ambient * b1, a2 = Q.ambient * b2;
-      const float d0 = Q.diffuse * b0, d1 = Q.diffuse * b1, d2 = Q.diffuse * b2;
-      col[0][s] = (a0 + d0 * diff) + P.ks[0] * spec;
-      col[1][s] = (a1 + d1 * diff) + P.ks[1] * spec;
-      col[2][s] = (a2 + d2 * diff) + P.ks[2] * spec;
-    } else {
-      col[0][s] = (P.ka[0] + P.kd[0] * diff) + P.ks[0] * spec;
-      col[1][s] = (P.ka[1] + P.kd[1] * diff) + P.ks[1] * spec;
-      col[2][s] = (P.ka[2] + P.kd[2] * diff) + P.ks[2] * spec;
-    }
+    float diff, spec;
+    light_terms(P, nx, ny, nz, diff, spec);
+    if (COLORS)
+      phong_color(Q, (float)(r.w & 255) / 255.0f, (float)((r.w >> 8) & 255) / 255.0f,
+                  (float)((r.w >> 16) & 255) / 255.0f, diff, spec, col[0][s], col[1][s], col[2][s]);
+    else
+      phong_color(P, diff, spec, col[0][s], col[1][s], col[2][s]);
   }
   if (!image && !radiance) return;                                             // uniform
   __syncthreads();
 
   const int ow = W / ssaa, oh = H / ssaa, side = kTile / ssaa;                 // ssaa divides 32, W and H
-  const float inv = 1.0f / (float)(ssaa * ssaa);
   for (int o = tid; o < side * side; o += kThreads) {
     const int lx = o % side, ly = o / side;
     const int ox = tx0 / ssaa + lx, oy = ty0 / ssaa + ly;
@@ -156,20 +146,8 @@ __global__ __launch_bounds__(256) void points_tile_kernel(const v4i* __restrict_
         ++covered;
       }
     }
-    const float rest = 1.0f - (float)covered * inv;
-    float bg0 = P.bg[0], bg1 = P.bg[1], bg2 = P.bg[2];
-    if (bg_img) {
-      const unsigned char* q = bg_img + ((size_t)oy * ow + ox) * 3;
-      bg0 = (float)q[0] / 255.0f; bg1 = (float)q[1] / 255.0f; bg2 = (float)q[2] / 255.0f;
-    }
-    const float r0 = acc0 * inv + bg0 * rest, r1 = acc1 * inv + bg1 * rest, r2 = acc2 * inv + bg2 * rest;
-    const size_t out = ((bv * oh + oy) * ow + ox) * 3;
-    if (radiance) { radiance[out] = r0; radiance[out + 1] = r1; radiance[out + 2] = r2; }
-    if (image) {
-      image[out] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r0, 0.0f), 1.0f) * 255.0f);
-      image[out + 1] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r1, 0.0f), 1.0f) * 255.0f);
-      image[out + 2] = (unsigned char)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(r2, 0.0f), 1.0f) * 255.0f);
-    }
+    resolve_pixel(acc0, acc1, acc2, covered, ssaa, P, bg_img, (size_t)oy * ow + ox, ((bv * oh + oy) * ow + ox) * 3,
+                  radiance, image);
   }
 }
 
@@ -229,8 +207,7 @@ extern "C" int fpsg_points_render(const float* points, const uint8_t* colors, in
   FPSG_REQUIRE(ws_bytes >= need, FPSG_E_SHAPE, "fpsg_points_render: workspace of %zu bytes, %zu needed", ws_bytes,
                need);
   MaterialParams Q;
-  unpack_render_params(params, log2_shininess, Q.base);
-  Q.ambient = params[15]; Q.diffuse = params[16];
+  unpack_material_params(params, log2_shininess, Q);
   hipStream_t st = static_cast<hipStream_t>(stream);
   v4i* rec = static_cast<v4i*>(ws);
   const unsigned bv = (unsigned)B * (unsigned)n_views;                         // below 65536: a grid's y and z take it

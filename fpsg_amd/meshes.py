@@ -649,6 +649,73 @@ def _scene_arguments(scene, F, dev):
     return mat_table, tex_table, face_material, face_uv, texels
 
 
+def _opt(t):
+    return None if t is None else _hip.ptr(t)
+
+
+class _RenderJob:
+    """What ``render_views`` and ``render_points`` share, in three steps because both raise their own errors in between:
+    the image size, ``ssaa`` and ``ortho_scale``; the views, the background and the shading parameters; on the device,
+    the uploads, the output buffers and the arguments every render entry takes."""
+
+    def __init__(self, size, ssaa, allowed, allowed_text, ortho_scale):
+        """``allowed``: the caller's ``ssaa`` values, ``allowed_text``: how its message names them."""
+        H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        if isinstance(ssaa, bool) or int(ssaa) != ssaa or int(ssaa) not in allowed:
+            raise ValueError(f"ssaa must be {allowed_text}, got {ssaa}")
+        ssaa = int(ssaa)
+        if H < 1 or W < 1 or H * ssaa > RENDER_MAX_SIZE or W * ssaa > RENDER_MAX_SIZE:
+            raise ValueError(f"size * ssaa must be from 1 to {RENDER_MAX_SIZE}, got {(H, W)} * {ssaa}")
+        if not (ortho_scale > 0 and math.isfinite(ortho_scale)):
+            raise ValueError(f"ortho_scale must be positive and finite, got {ortho_scale}")
+        self.H, self.W, self.ssaa, self.ortho_scale = H, W, ssaa, float(ortho_scale)
+        self.RW, self.RH = W * ssaa, H * ssaa
+
+    def camera(self, material, background, views, *camera):
+        """The view matrices (``views``, or ``camera_views(*camera)``), the background colour or image and ``params``."""
+        self.mats = camera_views(*camera) if views is None else \
+            np.ascontiguousarray(np.asarray(views, dtype=np.float32).reshape(-1, 12))
+        self.n_views = self.mats.shape[0]
+        if self.n_views < 1:
+            raise ValueError("no views")
+        self.bg_img = None
+        if isinstance(background, (np.ndarray, torch.Tensor)) and background.ndim == 3:
+            self.bg_img = torch.as_tensor(background)
+            if self.bg_img.dtype != torch.uint8 or tuple(self.bg_img.shape) != (self.H, self.W, 3):
+                raise ValueError(f"a background image must be uint8 [{self.H},{self.W},3], got {self.bg_img.dtype} "
+                                 f"{tuple(self.bg_img.shape)}")
+        self.material = material
+        self.params = material.params() if self.bg_img is not None else material.params(background)
+
+    def allocate(self, dev, lead, id_name, return_buffers):
+        """Views and background image to ``dev``; the outputs, ``lead`` in front of their shapes.  Only the image
+        without ``return_buffers``."""
+        self.d_views = torch.from_numpy(self.mats).to(dev)
+        if self.bg_img is not None:
+            self.bg_img = self.bg_img.to(dev).contiguous()
+        lead = (*lead, self.n_views)
+        self.image = torch.empty((*lead, self.H, self.W, 3), dtype=torch.uint8, device=dev)
+        self.id_name, self.buffers = id_name, None
+        if return_buffers:
+            self.buffers = {id_name: torch.empty((*lead, self.RH, self.RW), dtype=torch.int32, device=dev),
+                            "depth": torch.empty((*lead, self.RH, self.RW), dtype=torch.float32, device=dev),
+                            "radiance": torch.empty((*lead, self.H, self.W, 3), dtype=torch.float32, device=dev)}
+
+    def view_args(self):
+        return _hip.ptr(self.d_views), self.n_views, self.RW, self.RH, self.ssaa, self.ortho_scale
+
+    def shade_args(self, log2s, ws, stream, base_colors=True):
+        """``base_colors``: the 17-float ``params`` of the entries that scale a base colour, K27's 15 otherwise."""
+        scales = [float(self.material.ambient), float(self.material.diffuse)] if base_colors else []
+        c_params = (ctypes.c_float * (15 + len(scales)))(*self.params.tolist(), *scales)
+        b = self.buffers or {}
+        return (c_params, log2s, _opt(self.bg_img), _hip.ptr(self.image), _opt(b.get("radiance")),
+                _opt(b.get(self.id_name)), _opt(b.get("depth")), _hip.ptr(ws), ws.numel() * 8, stream)
+
+    def result(self):
+        return self.image if self.buffers is None else (self.image, self.buffers)
+
+
 def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevations_deg=60.0,
                  azimuths_deg=range(0, 360, 30), radius: float = 3.0, ortho_scale: float = 2.0, up: str = "z",
                  ssaa: int = 2, background=(1.0, 1.0, 1.0), material: PhongMaterial = PhongMaterial(),
@@ -673,32 +740,12 @@ def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevatio
     Colours are ``scene``'s when it is given as well, ``material.color`` otherwise; ``face_id`` and ``depth`` do not change.
 
     ``ValueError`` for bad shapes and options, ``FpsgHipError`` for CPU tensors."""
-    H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
-    if isinstance(ssaa, bool) or int(ssaa) != ssaa or not 1 <= int(ssaa) <= RENDER_MAX_SSAA:
-        raise ValueError(f"ssaa must be an integer from 1 to {RENDER_MAX_SSAA}, got {ssaa}")
-    ssaa = int(ssaa)
-    if H < 1 or W < 1 or H * ssaa > RENDER_MAX_SIZE or W * ssaa > RENDER_MAX_SIZE:
-        raise ValueError(f"size * ssaa must be from 1 to {RENDER_MAX_SIZE}, got {(H, W)} * {ssaa}")
-    if not (ortho_scale > 0 and math.isfinite(ortho_scale)):
-        raise ValueError(f"ortho_scale must be positive and finite, got {ortho_scale}")
+    job = _RenderJob(size, ssaa, range(1, RENDER_MAX_SSAA + 1), f"an integer from 1 to {RENDER_MAX_SSAA}", ortho_scale)
     log2s = material.log2_shininess()
-    mats = camera_views(elevations_deg, azimuths_deg, radius, up) if views is None else \
-        np.ascontiguousarray(np.asarray(views, dtype=np.float32).reshape(-1, 12))
-    n_views = mats.shape[0]
-    if n_views < 1:
-        raise ValueError("no views")
-    bg_img = None
-    if isinstance(background, (np.ndarray, torch.Tensor)) and background.ndim == 3:
-        bg_img = torch.as_tensor(background)
-        if bg_img.dtype != torch.uint8 or tuple(bg_img.shape) != (H, W, 3):
-            raise ValueError(f"a background image must be uint8 [{H},{W},3], got {bg_img.dtype} {tuple(bg_img.shape)}")
-        params = material.params()
-    else:
-        params = material.params(background)
+    job.camera(material, background, views, elevations_deg, azimuths_deg, radius, up)
     verts, faces = _mesh_tensors(verts, faces)
     dev = verts.device
     V, F = verts.size(0), faces.size(0)
-    RW, RH = W * ssaa, H * ssaa
     lib = _hip.load()
     if face_normals is not None:
         if not isinstance(face_normals, torch.Tensor) or face_normals.device != dev or \
@@ -709,55 +756,26 @@ def render_views(verts: torch.Tensor, faces: torch.Tensor, *, size=600, elevatio
         _hip.dev_tensor(face_normals, torch.float32, "face_normals")
         if scene is None:                    # no materials: K27's colours
             scene = RenderScene(None, None, np.zeros((0, 4), np.float32), np.zeros((0, 3), np.int32), None)
+    entry, scene_args, M, T = "fpsg_mesh_render", [], 0, 0
     if scene is not None:
         mat_table, tex_table, face_material, face_uv, texels = _scene_arguments(scene, F, dev)
         M, T = len(mat_table), len(tex_table)
-        ws_bytes = lib.fpsg_mesh_render_materials_workspace_bytes(V, F, n_views, RW, RH, M, T)
-    else:
-        ws_bytes = lib.fpsg_mesh_render_workspace_bytes(V, F, n_views, RW, RH)
+        entry = "fpsg_mesh_render_materials" if face_normals is None else "fpsg_mesh_render_smooth"
+        scene_args = [_opt(face_material), _opt(face_uv), *([] if face_normals is None else [_hip.ptr(face_normals)]),
+                      mat_table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if M else None, M,
+                      tex_table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if T else None, T, _opt(texels),
+                      0 if texels is None else texels.size(0)]
+    # K27's workspace is K28's without tables
+    ws_bytes = lib.fpsg_mesh_render_materials_workspace_bytes(V, F, job.n_views, job.RW, job.RH, M, T)
     if ws_bytes == 0:
-        raise ValueError(f"unsupported render shape (V={V}, F={F}, views={n_views}, {RW}x{RH})")
+        raise ValueError(f"unsupported render shape (V={V}, F={F}, views={job.n_views}, {job.RW}x{job.RH})")
     ws = torch.empty((ws_bytes // 16 + 1, 2), dtype=torch.int64, device=dev)
-    d_views = torch.from_numpy(mats).to(dev)
-    if bg_img is not None:
-        bg_img = bg_img.to(dev).contiguous()
-    image = torch.empty((n_views, H, W, 3), dtype=torch.uint8, device=dev)
-    radiance = face_id = depth = None
-    if return_buffers:
-        radiance = torch.empty((n_views, H, W, 3), dtype=torch.float32, device=dev)
-        face_id = torch.empty((n_views, RH, RW), dtype=torch.int32, device=dev)
-        depth = torch.empty((n_views, RH, RW), dtype=torch.float32, device=dev)
-    c_params = (ctypes.c_float * 15)(*params.tolist())
-
-    def opt(t):
-        return None if t is None else _hip.ptr(t)
-
-    if scene is not None:
-        c_params = (ctypes.c_float * 17)(*params.tolist(), float(material.ambient), float(material.diffuse))
-        c_mats = mat_table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if M else None
-        c_table = tex_table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if T else None
-        tail = (c_mats, M, c_table, T, opt(texels), 0 if texels is None else texels.size(0), _hip.ptr(d_views), n_views, RW,
-                RH, ssaa, float(ortho_scale), c_params, log2s, opt(bg_img), _hip.ptr(image), opt(radiance), opt(face_id),
-                opt(depth), _hip.ptr(ws), ws.numel() * 8, _hip.stream_of(verts))
-        with torch.cuda.device(dev):
-            if face_normals is not None:
-                entry = "fpsg_mesh_render_smooth"
-                rc = lib.fpsg_mesh_render_smooth(_hip.ptr(verts), V, _hip.ptr(faces), F, opt(face_material), opt(face_uv),
-                                                 _hip.ptr(face_normals), *tail)
-            else:
-                entry = "fpsg_mesh_render_materials"
-                rc = lib.fpsg_mesh_render_materials(_hip.ptr(verts), V, _hip.ptr(faces), F, opt(face_material),
-                                                    opt(face_uv), *tail)
-        _hip.check(rc, entry)
-    else:
-        with torch.cuda.device(dev):
-            rc = lib.fpsg_mesh_render(_hip.ptr(verts), V, _hip.ptr(faces), F, _hip.ptr(d_views), n_views, RW, RH, ssaa,
-                                      float(ortho_scale), c_params, log2s, opt(bg_img), _hip.ptr(image), opt(radiance),
-                                      opt(face_id), opt(depth), _hip.ptr(ws), ws.numel() * 8, _hip.stream_of(verts))
-        _hip.check(rc, "fpsg_mesh_render")
-    if return_buffers:
-        return image, {"face_id": face_id, "depth": depth, "radiance": radiance}
-    return image
+    job.allocate(dev, (), "face_id", return_buffers)
+    with torch.cuda.device(dev):
+        rc = getattr(lib, entry)(_hip.ptr(verts), V, _hip.ptr(faces), F, *scene_args, *job.view_args(),
+                                 *job.shade_args(log2s, ws, _hip.stream_of(verts), base_colors=scene is not None))
+    _hip.check(rc, entry)
+    return job.result()
 
 
 # -------------------------------------------------------------------------------------------- K31a
@@ -942,17 +960,10 @@ def render_points(points: torch.Tensor, *, colors=None, size=256, elevations_deg
     on the batch it is rendered in.
 
     ``ValueError`` for bad shapes and options, before any GPU work; ``FpsgHipError`` for CPU tensors."""
-    H, W = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
-    if isinstance(ssaa, bool) or int(ssaa) != ssaa or int(ssaa) not in (1, 2, 4):
-        raise ValueError(f"ssaa must be 1, 2 or 4, got {ssaa}")
-    ssaa = int(ssaa)
-    if H < 1 or W < 1 or H * ssaa > RENDER_MAX_SIZE or W * ssaa > RENDER_MAX_SIZE:
-        raise ValueError(f"size * ssaa must be from 1 to {RENDER_MAX_SIZE}, got {(H, W)} * {ssaa}")
-    if not (ortho_scale > 0 and math.isfinite(ortho_scale)):
-        raise ValueError(f"ortho_scale must be positive and finite, got {ortho_scale}")
+    job = _RenderJob(size, ssaa, (1, 2, 4), "1, 2 or 4", ortho_scale)
     if not (point_radius > 0 and math.isfinite(point_radius)):
         raise ValueError(f"point_radius must be positive and finite, got {point_radius}")
-    RW, RH = W * ssaa, H * ssaa
+    RW, RH = job.RW, job.RH
     # the entry's R, from the float32 values it is given
     R = round(256.0 * (float(np.float32(point_radius)) / float(np.float32(ortho_scale))) * max(RW, RH))
     if not 1 <= R <= 256 * POINTS_MAX_RADIUS_PX:
@@ -975,19 +986,8 @@ def render_points(points: torch.Tensor, *, colors=None, size=256, elevations_deg
                              f"{tuple(getattr(colors, 'shape', ()))}")
         if colors.device != points.device:
             raise ValueError(f"colors are on {colors.device}, points on {points.device}")
-    mats = camera_views(elevations_deg, azimuths_deg, radius_cam, up) if views is None else \
-        np.ascontiguousarray(np.asarray(views, dtype=np.float32).reshape(-1, 12))
-    n_views = mats.shape[0]
-    if n_views < 1:
-        raise ValueError("no views")
-    bg_img = None
-    if isinstance(background, (np.ndarray, torch.Tensor)) and background.ndim == 3:
-        bg_img = torch.as_tensor(background)
-        if bg_img.dtype != torch.uint8 or tuple(bg_img.shape) != (H, W, 3):
-            raise ValueError(f"a background image must be uint8 [{H},{W},3], got {bg_img.dtype} {tuple(bg_img.shape)}")
-        params = material.params()
-    else:
-        params = material.params(background)
+    job.camera(material, background, views, elevations_deg, azimuths_deg, radius_cam, up)
+    n_views = job.n_views
     if B * n_views >= 65536:
         raise ValueError(f"clouds * views must be below 65536, got {B} * {n_views}")
     points = points.contiguous()
@@ -1000,29 +1000,12 @@ def render_points(points: torch.Tensor, *, colors=None, size=256, elevations_deg
     if ws_bytes == 0:
         raise ValueError(f"unsupported render shape (B={B}, N={N}, views={n_views}, {RW}x{RH})")
     ws = torch.empty((ws_bytes // 16, 2), dtype=torch.int64, device=dev)
-    d_views = torch.from_numpy(mats).to(dev)
-    if bg_img is not None:
-        bg_img = bg_img.to(dev).contiguous()
-    image = torch.empty((B, n_views, H, W, 3), dtype=torch.uint8, device=dev)
-    radiance = point_id = depth = None
-    if return_buffers:
-        radiance = torch.empty((B, n_views, H, W, 3), dtype=torch.float32, device=dev)
-        point_id = torch.empty((B, n_views, RH, RW), dtype=torch.int32, device=dev)
-        depth = torch.empty((B, n_views, RH, RW), dtype=torch.float32, device=dev)
-    c_params = (ctypes.c_float * 17)(*params.tolist(), float(material.ambient), float(material.diffuse))
-
-    def opt(t):
-        return None if t is None else _hip.ptr(t)
-
+    job.allocate(dev, (B,), "point_id", return_buffers)
     with torch.cuda.device(dev):
-        rc = lib.fpsg_points_render(_hip.ptr(points), opt(colors), B, N, _hip.ptr(d_views), n_views, RW, RH, ssaa,
-                                    float(ortho_scale), float(point_radius), c_params, log2s, opt(bg_img),
-                                    _hip.ptr(image), opt(radiance), opt(point_id), opt(depth), _hip.ptr(ws),
-                                    ws.numel() * 8, _hip.stream_of(points))
+        rc = lib.fpsg_points_render(_hip.ptr(points), _opt(colors), B, N, *job.view_args(), float(point_radius),
+                                    *job.shade_args(log2s, ws, _hip.stream_of(points)))
     _hip.check(rc, "fpsg_points_render")
-    if return_buffers:
-        return image, {"point_id": point_id, "depth": depth, "radiance": radiance}
-    return image
+    return job.result()
 
 
 # ------------------------------------------------------------------------------------- list files

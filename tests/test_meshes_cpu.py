@@ -337,6 +337,32 @@ def test_entry_points_refuse_bad_arguments_on_the_host(lib):
     assert lib.fpsg_mesh_render_workspace_bytes(8, 4, 2, 8193, 32) == 0
 
 
+def test_mesh_render_refusals_their_codes_and_their_prefix(lib):
+    """``fpsg_mesh_render``'s own refusals, all in front of the first launch, so made-up aligned addresses do.  The
+    codes are those the library returned when the entry still had its own copy of the checks."""
+    import ctypes
+    params = (ctypes.c_float * 15)()
+    need = lib.fpsg_mesh_render_workspace_bytes(8, 4, 2, 64, 64)
+    good = dict(verts=0x1000, V=8, faces=0x2000, W=64, ssaa=1, image=0x5000, radiance=None, ws=0x10000, ws_bytes=need)
+
+    def render(**kw):
+        a = {**good, **kw}
+        rc = lib.fpsg_mesh_render(a["verts"], a["V"], a["faces"], 4, 0x3000, 2, a["W"], 64, a["ssaa"], ctypes.c_float(2.0),
+                                  params, 5, None, a["image"], a["radiance"], None, None, a["ws"], a["ws_bytes"], None)
+        assert lib.fpsg_last_error().startswith(b"fpsg_mesh_render:"), lib.fpsg_last_error()
+        return rc, lib.fpsg_last_error()
+
+    for kw, code, text in [(dict(V=0), -2, b"must be positive"),
+                           (dict(W=66, ssaa=4), -2, b"a divisor of W and H"),
+                           (dict(verts=None), -1, b"null pointer 'verts'"),
+                           (dict(radiance=0x6002), -3, b"an output is not 4-byte aligned"),
+                           (dict(image=None), -1, b"no output requested"),
+                           (dict(ws=0x10008), -3, b"'ws' must be 16-byte aligned"),
+                           (dict(ws_bytes=need - 1), -2, b"workspace of %d bytes, %d needed" % (need - 1, need))]:
+        rc, message = render(**kw)
+        assert rc == code and text in message, (kw, rc, message)
+
+
 def test_wrappers_have_no_cpu_fallback_and_check_shapes_first():
     from fpsg_amd._hip import FpsgHipError
     v, f = ref.cube()
