@@ -264,6 +264,12 @@ SIGNATURES = {
     "fpsg_point_mesh_workspace_bytes": [_c_int, _c_int, _c_int, _c_int],
     "fpsg_point_mesh_distance": [_c_f32p, _c_int, _c_int, _c_f32p, _c_int, _c_int, _c_i32p, _c_int, _c_int, _c_f32p,
                                  _c_i32p, _c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_size_t, _c_stream],
+    "fpsg_point_normals_workspace_bytes": [_c_int, _c_int, _c_int],
+    "fpsg_point_normals": [_c_f32p, _c_int, _c_int, _c_int, _c_int, _c_f32p, _c_f32p, _c_f32p, _c_i32p, ctypes.c_void_p,
+                           ctypes.c_size_t, _c_stream],
+    "fpsg_point_normals_orient_workspace_bytes": [_c_int, _c_int, _c_int],
+    "fpsg_point_normals_orient": [_c_f32p, _c_f32p, _c_i32p, _c_int, _c_int, _c_int, _c_int, _c_f32p, _c_i32p,
+                                  ctypes.c_void_p, ctypes.c_size_t, _c_stream],
 }
 _RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_grad_norm_workspace_bytes": ctypes.c_size_t,
 "fpsg_chamfer_workspace_bytes": ctypes.c_size_t,
@@ -281,7 +287,9 @@ _RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_grad_norm_workspace_bytes
              "fpsg_mesh_render_materials_workspace_bytes": ctypes.c_size_t,
              "fpsg_mesh_render_smooth_workspace_bytes": ctypes.c_size_t,
              "fpsg_points_render_workspace_bytes": ctypes.c_size_t,
-             "fpsg_point_mesh_workspace_bytes": ctypes.c_size_t}
+             "fpsg_point_mesh_workspace_bytes": ctypes.c_size_t,
+             "fpsg_point_normals_workspace_bytes": ctypes.c_size_t,
+             "fpsg_point_normals_orient_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 _lock = threading.Lock()

@@ -418,16 +418,24 @@ def normalize_mesh(verts, mode: str = "bbox") -> np.ndarray:
     return np.ascontiguousarray(v, dtype=np.float32)
 
 
-def write_ply_points(path: str, pts) -> None:
-    """The ASCII vertex-only PLY that ``datasets.ply_reader`` reads back; ``%.9g`` keeps every float32 bit."""
+def write_ply_points(path: str, pts, normals=None) -> None:
+    """The ASCII vertex-only PLY that ``datasets.ply_reader`` reads back; ``%.9g`` keeps every float32 bit.  With
+    ``normals`` ``[N,3]`` the vertices also carry ``nx ny nz`` (what a Poisson reconstruction reads): six columns."""
     p = np.asarray(pts.detach().cpu() if isinstance(pts, torch.Tensor) else pts, dtype=np.float32)
     if p.ndim != 2 or p.shape[1] != 3:
         raise ValueError(f"expected [N,3] points, got {p.shape}")
     head = ("ply\nformat ascii 1.0\n"
-            f"element vertex {p.shape[0]}\nproperty float x\nproperty float y\nproperty float z\nend_header\n")
-    body = "\n".join("%.9g %.9g %.9g" % (x, y, z) for x, y, z in p.tolist())
+            f"element vertex {p.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n")
+    if normals is None:
+        body = "\n".join("%.9g %.9g %.9g" % (x, y, z) for x, y, z in p.tolist())
+    else:
+        n = np.asarray(normals.detach().cpu() if isinstance(normals, torch.Tensor) else normals, dtype=np.float32)
+        if n.shape != p.shape:
+            raise ValueError(f"expected {p.shape} normals, got {n.shape}")
+        head += "property float nx\nproperty float ny\nproperty float nz\n"
+        body = "\n".join("%.9g %.9g %.9g %.9g %.9g %.9g" % tuple(row) for row in np.concatenate([p, n], axis=1).tolist())
     with open(path, "w") as f:
-        f.write(head + body + "\n")
+        f.write(head + "end_header\n" + body + "\n")
 
 
 def write_obj_mesh(path: str, verts, faces, *, normals=None, face_material=None, materials=None, mtl_name=None) -> None:
@@ -939,6 +947,51 @@ def mesh_accuracy(verts: torch.Tensor, faces: torch.Tensor, cloud: torch.Tensor,
     values = torch.stack([to_surface.sqrt().mean(), to_cloud.sqrt().mean(), to_surface.mean() + to_cloud.mean(),
                           torch.maximum(to_surface.max(), to_cloud.max()).sqrt()]).tolist()
     return dict(zip(("completeness", "accuracy", "chamfer", "hausdorff"), values))
+
+
+def mesh_normal_consistency(verts: torch.Tensor, faces: torch.Tensor, cloud: torch.Tensor, *, k: int = 16, n_samples=None,
+                            generator=None, u=None, cloud_normals=None) -> dict:
+    """How well the surface directions of one mesh ``(verts [V,3], faces [F,3])`` agree with those of one ground-truth
+    ``cloud [N,3]`` -> Python floats in [0, 1], signs not counted:
+
+    - ``"to_surface"``: the mean over the cloud's points of ``|n_p . g_f|``, ``n_p`` the point's normal (K33 over ``k``
+      neighbours with ``orient="none"``, or ``cloud_normals [N,3]``) and ``g_f`` the unit geometric normal of its nearest
+      face (K32), zero for a face without area;
+    - ``"to_cloud"``: the mean over ``n_samples`` surface samples (K26; default: the cloud's size; ``generator`` and ``u``
+      as in ``sample_surface``) of ``|g_face(sample) . n_q|``, ``q`` the sample's nearest cloud point (K1);
+    - ``"normal_consistency"``: their mean.
+
+    Means are taken in float64 on the device; the three numbers come back in one read.  ``ValueError`` and
+    ``FpsgHipError`` as ``point_mesh_distance``, ``sample_surface`` and ``normals.estimate_normals``."""
+    from .metrics import nearest_rows
+    from .normals import estimate_normals
+    if not isinstance(cloud, torch.Tensor) or cloud.dim() != 2 or cloud.size(1) != 3 or cloud.size(0) < 1:
+        raise ValueError(f"expected a [N,3] cloud, got {tuple(getattr(cloud, 'shape', ()))}")
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2:
+        raise ValueError(f"expected [V,3] vertices, got {tuple(getattr(verts, 'shape', ()))}")
+    n = cloud.size(0) if n_samples is None else n_samples
+    if isinstance(n, bool) or int(n) != n or int(n) < 1:
+        raise ValueError(f"n_samples must be a positive integer, got {n_samples}")
+    cloud = cloud.detach().contiguous()
+    if cloud_normals is None:
+        cloud_normals = estimate_normals(cloud, k, orient="none")
+    elif not isinstance(cloud_normals, torch.Tensor) or cloud_normals.shape != cloud.shape:
+        raise ValueError(f"cloud_normals must have the cloud's shape {tuple(cloud.shape)}, got "
+                         f"{tuple(getattr(cloud_normals, 'shape', ()))}")
+    face = point_mesh_distance(cloud, verts, faces)["face"][0]
+    samples, sample_face = sample_surface(verts, faces, int(n), generator=generator, u=u)
+    nearest = nearest_rows(samples.unsqueeze(0), cloud.unsqueeze(0))[2][0].long()
+    with torch.no_grad():
+        corners = verts.detach().to(torch.float64)[faces.long()]                      # [F,3,3]
+        g = torch.linalg.cross(corners[:, 1] - corners[:, 0], corners[:, 2] - corners[:, 0])
+        length = g.norm(dim=1, keepdim=True)
+        g = torch.where(length > 0, g / torch.where(length > 0, length, torch.ones_like(length)), torch.zeros_like(g))
+        cn = cloud_normals.detach().to(device=cloud.device, dtype=torch.float64)
+        to_surface = (cn * g[face.clamp(min=0)]).sum(-1).abs()
+        to_surface = torch.where(face >= 0, to_surface, torch.zeros_like(to_surface)).mean()
+        to_cloud = (g[sample_face] * cn[nearest]).sum(-1).abs().mean()
+        values = torch.stack([to_surface, to_cloud, 0.5 * (to_surface + to_cloud)]).tolist()
+    return dict(zip(("to_surface", "to_cloud", "normal_consistency"), values))
 
 
 # -------------------------------------------------------------------------------------------- K29

@@ -19,7 +19,10 @@ square and neighbouring samples connected (``ImgPCProtoNet.reconstruct_mesh``). 
 With ``--metrics`` every generated mesh is also measured against its query's ground-truth cloud
 (``meshes.mesh_accuracy``: the points' distance to the surface by K32, the distance of ``--metrics_samples`` surface
 samples, K26, to the cloud by K1): one line per class, ``Class: <name> -- P2S: ..; S2P: ..; Mesh CD: ..; Mesh HD: ..``,
-and ``<output>/metrics.json``.
+and ``<output>/metrics.json``.  With ``--normal_consistency`` each line also ends with ``; NC: ..``
+(``meshes.mesh_normal_consistency``: the cloud's normals by K33 over ``--normals_k`` neighbours against the faces'
+normals, on the same samples), each class row of ``metrics.json`` gets ``"normal_consistency"`` and the report
+``"normals_k"``.
 """
 from __future__ import annotations
 
@@ -49,6 +52,10 @@ def build_parser():
                         "<output>/metrics.json;")
     g.add_argument("--metrics_samples", type=int, default=None, metavar="S",
                    help="With --metrics: surface samples per mesh [default: the cloud's size];")
+    g.add_argument("--normal_consistency", action="store_true",
+                   help="With --metrics: also the normal consistency of mesh and cloud (K33 + K32 + K26 + K1), 'NC';")
+    g.add_argument("--normals_k", type=int, default=None, metavar="K",
+                   help="With --normal_consistency: neighbours per point for the cloud's normals, 3..32 [default: 16];")
     return p
 
 
@@ -71,6 +78,13 @@ def main(opt) -> int:
         raise SystemExit("--metrics_samples needs --metrics")
     if opt.metrics_samples is not None and opt.metrics_samples < 1:
         raise SystemExit(f"--metrics_samples must be positive, got {opt.metrics_samples}")
+    if opt.normal_consistency and not opt.metrics:
+        raise SystemExit("--normal_consistency needs --metrics")
+    if opt.normals_k is not None and not opt.normal_consistency:
+        raise SystemExit("--normals_k needs --normal_consistency (and --metrics)")
+    normals_k = 16 if opt.normals_k is None else opt.normals_k
+    if not 3 <= normals_k <= 32:
+        raise SystemExit(f"--normals_k must be from 3 to 32, got {normals_k}")
     if not torch.cuda.is_available():
         raise FpsgHipError("generate_meshes.py runs on a ROCm GPU only (no CPU fallback)")
     n_query = opt.n_shot if opt.n_query == 0 else opt.n_query
@@ -122,20 +136,27 @@ def main(opt) -> int:
                 u = torch.rand((samples, 3), generator=draws, dtype=torch.float32)
                 acc = meshes.mesh_accuracy(verts[k], faces, clouds[k], n_samples=samples, u=u)
                 rows.append([acc[name] for name in METRIC_KEYS])
+                if opt.normal_consistency:
+                    nc = meshes.mesh_normal_consistency(verts[k], faces, clouds[k], k=normals_k, n_samples=samples, u=u)
+                    rows[-1].append(nc["normal_consistency"])
             per_class.setdefault(str(sample["class"][0]), []).append([sum(col) / len(col) for col in zip(*rows)])
         items += 1
     kernels = f"decoder first layer {first_layer}, normals K31a" + ("" if opt.no_sheet else ", views K31b + K29")
     if opt.metrics:
         report = {"grid": g, "samples": samples, "faces": n_patches * 2 * (g - 1) ** 2, "classes": {}}
+        keys, labels = METRIC_KEYS, METRIC_LABELS
+        if opt.normal_consistency:
+            report["normals_k"] = normals_k
+            keys, labels = keys + ("normal_consistency",), labels + ("NC",)
         for name in sorted(per_class):
             means = [sum(col) / len(col) for col in zip(*per_class[name])]
-            report["classes"][name] = dict(zip(METRIC_KEYS, means), items=len(per_class[name]))
-            print(f"Class: {name} -- " + "; ".join(f"{label}: {v}" for label, v in zip(METRIC_LABELS, means)))
+            report["classes"][name] = dict(zip(keys, means), items=len(per_class[name]))
+            print(f"Class: {name} -- " + "; ".join(f"{label}: {v}" for label, v in zip(labels, means)))
         os.makedirs(opt.output, exist_ok=True)
         with open(os.path.join(opt.output, "metrics.json"), "w") as f:
             json.dump(report, f, indent=1, sort_keys=True)
             f.write("\n")
-        kernels += ", distances K32 + K26 + K1"
+        kernels += ", distances K32 + K26 + K1" + (", normals K33" if opt.normal_consistency else "")
     print(f"{opt.output}: {items} items x {n_query} queries, {n_patches * g * g} vertices and "
           f"{n_patches * 2 * (g - 1) ** 2} faces per mesh ({kernels})")
     return 0

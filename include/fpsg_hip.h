@@ -1496,6 +1496,76 @@ int fpsg_point_mesh_distance(const float* points, int B, int N, const float* ver
                              const int32_t* faces, int F, int chunks, float* dist2, int32_t* face, float* closest,
                              float* bary, void* ws, size_t ws_bytes, fpsg_stream_t stream);
 
+/* ---- K33: normals of a point cloud (k-NN PCA, sign rules, orientation along a spanning forest) ------------
+ * The pipeline of Hoppe et al. (1992), as PCL and Open3D run it: the k nearest neighbours of every point, PCA of the
+ * neighbourhood, the eigenvector of the smallest eigenvalue; then one sign per point.  The published codes are not
+ * pinned; the definition below is the specification (parity UNPINNED).  All pointers are device memory.
+ *
+ * K33a, fpsg_point_normals.  Inputs: B clouds xyz [N,3] fp32, FPSG_NORMALS_POINTS_MIN_K <= k <= FPSG_NORMALS_POINTS_MAX_K,
+ * N >= k + 1; ref [B,3] fp32 (sign_mode 1 and 2; may be NULL with sign_mode 0).  Outputs: normals [B,N,3] fp32; variation
+ * [B,N] fp32 or NULL; nbr_idx [B,N,k] int32 or NULL.
+ *   d2(i,j)  = fma(dz,dz, fma(dy,dy, dx*dx)), dx = x_j - x_i                              (K1's sq_dist, as K21)
+ *   K(i)     = the k indices j != i with the smallest (d2(i,j), j) in lexicographic order (ties: the lower index),
+ *              stored nearest first.  j == i is skipped by index: a duplicate of point i is a neighbour at distance 0.
+ *              The set is exact and bitwise the same on every run.  A slot that no candidate entered (non-finite
+ *              coordinates only) holds i itself, so every stored index is in [0, N).
+ *   The neighbourhood is {i} and K(i): k + 1 points.  All of the following in fp32, every operation rounded on its own:
+ *   o_s      = x_j - x_i per component for the s-th neighbour j (the point's own offset is 0; the differences are exact
+ *              where the cloud lies far from the origin)
+ *   mu       = (o_1 + o_2 + .. + o_k) / (k + 1), summed from +0 in list order
+ *   C        = mu mu^T + sum_s (o_s - mu)(o_s - mu)^T, in list order: centred BEFORE the products, six entries
+ *   trace    = (C00 + C11) + C22.  Where trace is 0, not finite, or so small that 1 / trace is not finite:
+ *              normal = (0,0,0), variation = 0.
+ *   A        = C * (1 / trace); eight cyclic Jacobi sweeps over the planes (0,1), (0,2), (1,2) (a fixed count) with
+ *              theta = (a_qq - a_pp) / (2 a_pq), t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)), t = 0 where a_pq == 0,
+ *              c = 1 / sqrt(t^2 + 1), s = t c; the eigenvalues are the diagonal left over, lambda0 the smallest (the
+ *              lowest position on ties), the normal its column of the accumulated rotations times 1 / sqrt of its
+ *              squared length.
+ *   variation = min(max(lambda0, 0) / ((a00 + a11) + a22), 1/3): Pauly's surface variation, in [0, 1/3].
+ *   sign_mode 0 (canonical): the component of largest magnitude is positive, the lowest axis wins ties; the output is
+ *              a function of the cloud alone.
+ *   sign_mode 1 (toward ref[b]): with e = (nx (rx - px) + ny (ry - py)) + nz (rz - pz) on the canonical normal, the
+ *              normal is negated where e < 0.   sign_mode 2 (away from ref[b]): negated where e > 0.
+ *              Where e is exactly 0 (or NaN) the canonical sign stays.
+ * Two launches (the sweep; one thread per point for the PCA); the lists pass through nbr_idx, or through the workspace
+ * (fpsg_point_normals_workspace_bytes) when nbr_idx is NULL.
+ *
+ * K33b, fpsg_point_normals_orient.  Inputs: xyz, normals_in [B,N,3] fp32, nbr_idx [B,N,k] int32 (K33a's, or any table),
+ * axis in 0..2.  Outputs: normals_out [B,N,3] fp32 (must not overlap normals_in), parent [B,N] int32 or NULL.
+ *   edges    : i ~ j iff j is an entry of row i or i is an entry of row j; an entry outside [0, N), or equal to its own
+ *              row, is no edge.
+ *   w(i,j)   = 1 - |(nx mx + ny my) + nz mz| on normals_in, fp32, every operation rounded on its own: bitwise
+ *              symmetric and independent of any sign.  A zero normal is an ordinary vertex of weight 1 to everyone.
+ *   forest   : Prim's with K24's tie rules.  Every non-tree vertex keeps a key and a parent, replaced only by a
+ *              STRICTLY smaller weight to a vertex that joins; each step adds the non-tree vertex with the smallest
+ *              (key, index).  When no non-tree vertex has a key, the next root is the non-tree vertex with the largest
+ *              xyz[., axis], the lowest index on ties; the first root is chosen the same way.  Exactly N steps.
+ *   signs    : a root is negated where its `axis` component is < 0; a vertex v that joins under parent u is negated
+ *              where (ux vx + uy vy) + uz vz < 0 with u's ORIENTED normal.  parent is -1 at roots.
+ * One workgroup per cloud; keys and parents live in LDS (8 N bytes: N <= FPSG_NORMALS_POINTS_MAX_N fits the 160 KB).  The
+ * reverse lists come from two gather sweeps (count, fill) into the workspace: three launches.
+ *
+ * Both: no atomics, nothing passes between workgroups inside a launch; a cloud's results depend neither on B nor on its
+ * place in the batch and are bitwise the same on every run; non-finite coordinates or normals give unspecified values
+ * for that cloud only; no index outside [0, N) is ever stored or dereferenced; the calls only enqueue work on `stream`.
+ * Errors, all before any launch, shape and limit checks in front of the pointer checks: FPSG_E_SHAPE for B < 1, k
+ * outside 3..32, N < k + 1, sign_mode or axis outside 0..2, a workspace too small; FPSG_E_LIMIT for N >
+ * FPSG_NORMALS_POINTS_MAX_N or B > FPSG_NORMALS_POINTS_MAX_B; FPSG_E_NULL for a null xyz, normals, normals_in, nbr_idx (K33b),
+ * normals_out or ws, or a null ref with sign_mode 1 or 2; FPSG_E_ALIGN for a misaligned pointer.  The workspace functions
+ * return 0 for a shape the entries refuse.
+ */
+#define FPSG_NORMALS_POINTS_MIN_K 3
+#define FPSG_NORMALS_POINTS_MAX_K 32
+#define FPSG_NORMALS_POINTS_MAX_N 16384
+#define FPSG_NORMALS_POINTS_MAX_B 65535
+size_t fpsg_point_normals_workspace_bytes(int B, int N, int k);
+int fpsg_point_normals(const float* xyz, int B, int N, int k, int sign_mode, const float* ref, float* normals,
+                       float* variation, int32_t* nbr_idx, void* ws, size_t ws_bytes, fpsg_stream_t stream);
+size_t fpsg_point_normals_orient_workspace_bytes(int B, int N, int k);
+int fpsg_point_normals_orient(const float* xyz, const float* normals_in, const int32_t* nbr_idx, int B, int N, int k,
+                              int axis, float* normals_out, int32_t* parent, void* ws, size_t ws_bytes,
+                              fpsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
