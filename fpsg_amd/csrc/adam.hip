@@ -485,24 +485,6 @@ inline size_t grad_norm_blocks(size_t n) {
   return blocks > (size_t)kNormBlocksMax ? (size_t)kNormBlocksMax : blocks;
 }
 
-template <int M>
-__device__ __forceinline__ double lane_xor_f64(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  const unsigned lo = lane_xor<M>((unsigned)b), hi = lane_xor<M>((unsigned)(b >> 32));
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// wave_sum of fpsg_common.h on a double: the same fixed butterfly, the two halves exchanged separately
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  v += lane_xor_f64<1>(v);
-  v += lane_xor_f64<2>(v);
-  v += lane_xor_f64<4>(v);
-  v += lane_xor_f64<8>(v);
-  v += lane_xor_f64<16>(v);
-  v += lane_xor_f64<32>(v);
-  return v;
-}
-
 // Vector slot j holds the flat positions 4j .. 4j+3 (slot n/4: the n % 4 tail, the rest of it zeros).  Thread t of the
 // grid takes the slots t, t + T, t + 2T, ... (T threads in the grid) in that order; element e of every slot goes into
 // the thread's accumulator e, a_e = fma(g, g, a_e) in fp64 (the square of an fp32 value is exact there).  Then

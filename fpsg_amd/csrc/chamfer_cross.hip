@@ -182,8 +182,8 @@ __global__ __launch_bounds__(kXThreads) void chamfer_cross_kernel(
         float v = __builtin_inff();
 #pragma unroll
         for (int t = 0; t < 16; t += 2) v = __builtin_fminf(__builtin_fminf(v, vt[t]), vt[t + 1]);
-        v = __builtin_fminf(v, __uint_as_float(lane_xor<16>(__float_as_uint(v))));
-        v = __builtin_fminf(v, __uint_as_float(lane_xor<32>(__float_as_uint(v))));
+        v = __builtin_fminf(v, lane_xor_f<16>(v));
+        v = __builtin_fminf(v, lane_xor_f<32>(v));
         if (lane < 16) atomicMin(&colmin[cbase + cl], __float_as_uint(v));
       }
     }

@@ -431,7 +431,7 @@ __global__ __launch_bounds__(kRedThreads) void chamfer_loss_reduce_kernel(
       const int n = side ? nb2 : nb1;
       for (int k = 0; k < n; ++k) sum += p[k];
     }
-    const float other = __uint_as_float(lane_xor<1>(__float_as_uint(sum)));
+    const float other = lane_xor_f<1>(sum);
     if (side == 0 && bl < per && b0 + bl < B) cd[b0 + bl] = sum * (1.0f / (float)N) + other * (1.0f / (float)M);
     __syncthreads();
   }

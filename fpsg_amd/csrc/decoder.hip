@@ -39,6 +39,7 @@ inline size_t dec1_lds_bytes(int B, int P, bool bwd) {
   return ((size_t)3 * B * P + (size_t)kD1Tile * B + (bwd ? (size_t)kD1Waves * 64 * 12 : 0)) * sizeof(float);
 }
 
+// K9's own form, on ds_bpermute; its intended successor is the DPP wave_sum_f64 of fpsg_common.h (shadowed here)
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) {
@@ -53,12 +54,12 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 
 // sum over groups of `grp` consecutive lanes (grp a power of two <= 64); every lane of a group gets it
 __device__ __forceinline__ float group_sum(float v, int grp) {
-  if (grp > 1) v += __uint_as_float(lane_xor<1>(__float_as_uint(v)));
-  if (grp > 2) v += __uint_as_float(lane_xor<2>(__float_as_uint(v)));
-  if (grp > 4) v += __uint_as_float(lane_xor<4>(__float_as_uint(v)));
-  if (grp > 8) v += __uint_as_float(lane_xor<8>(__float_as_uint(v)));
-  if (grp > 16) v += __uint_as_float(lane_xor<16>(__float_as_uint(v)));
-  if (grp > 32) v += __uint_as_float(lane_xor<32>(__float_as_uint(v)));
+  if (grp > 1) v += lane_xor_f<1>(v);
+  if (grp > 2) v += lane_xor_f<2>(v);
+  if (grp > 4) v += lane_xor_f<4>(v);
+  if (grp > 8) v += lane_xor_f<8>(v);
+  if (grp > 16) v += lane_xor_f<16>(v);
+  if (grp > 32) v += lane_xor_f<32>(v);
   return v;
 }
 

@@ -22,27 +22,6 @@ constexpr int kProfileThreads = 256;
 constexpr int kProfileWaves = kProfileThreads / kWave;
 constexpr int kProfileInFlight = 4;                    // loads a thread issues before it uses the first
 
-__device__ __forceinline__ int profile_wave_add(int v) {
-  v += (int)lane_xor<1>((unsigned)v);
-  v += (int)lane_xor<2>((unsigned)v);
-  v += (int)lane_xor<4>((unsigned)v);
-  v += (int)lane_xor<8>((unsigned)v);
-  v += (int)lane_xor<16>((unsigned)v);
-  v += (int)lane_xor<32>((unsigned)v);
-  return v;
-}
-
-__device__ __forceinline__ float profile_wave_max(float v) {
-  // the operands are >= +0 and never NaN (profile_take), so the larger of two is the larger bit pattern too
-  v = __builtin_fmaxf(v, __uint_as_float(lane_xor<1>(__float_as_uint(v))));
-  v = __builtin_fmaxf(v, __uint_as_float(lane_xor<2>(__float_as_uint(v))));
-  v = __builtin_fmaxf(v, __uint_as_float(lane_xor<4>(__float_as_uint(v))));
-  v = __builtin_fmaxf(v, __uint_as_float(lane_xor<8>(__float_as_uint(v))));
-  v = __builtin_fmaxf(v, __uint_as_float(lane_xor<16>(__float_as_uint(v))));
-  v = __builtin_fmaxf(v, __uint_as_float(lane_xor<32>(__float_as_uint(v))));
-  return v;
-}
-
 // one element: fp32 `<=` against every threshold (NaN on either side: false), and the running maximum, which starts
 // at +0 and moves only on `>` -- a NaN and -0 never enter it
 __device__ __forceinline__ void profile_take(float v, const float (&tau)[FPSG_PROFILE_MAX_T],
@@ -87,8 +66,8 @@ __global__ __launch_bounds__(kProfileThreads) void dist_profile_kernel(const flo
   for (; i < n; i += kProfileThreads) profile_take(row[i], tau, cnt, mx);
 
 #pragma unroll
-  for (int t = 0; t < FPSG_PROFILE_MAX_T; ++t) cnt[t] = profile_wave_add(cnt[t]);
-  mx = profile_wave_max(mx);
+  for (int t = 0; t < FPSG_PROFILE_MAX_T; ++t) cnt[t] = wave_sum(cnt[t]);
+  mx = wave_max(mx);                                    // the operands are >= +0 and never NaN (profile_take)
   if ((tid & 63u) == 0) {
 #pragma unroll
     for (int t = 0; t < FPSG_PROFILE_MAX_T; ++t) s_cnt[wave][t] = cnt[t];

@@ -183,12 +183,12 @@ __global__ __launch_bounds__(kEcThreads) void edgeconv_fwd_grouped_kernel(
     constexpr int M = decltype(xor_tag)::value;
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
-      const float ob = __uint_as_float(lane_xor<M>(__float_as_uint(best[v])));
+      const float ob = lane_xor_f<M>(best[v]);
       const int oj = (int)lane_xor<M>((unsigned)bj[v]);
       const bool take = ob > best[v] || (ob == best[v] && oj < bj[v]);
       bj[v] = take ? oj : bj[v];
       best[v] = take ? ob : best[v];
-      tot[v] += __uint_as_float(lane_xor<M>(__float_as_uint(tot[v])));
+      tot[v] += lane_xor_f<M>(tot[v]);
     }
   };
 
@@ -244,8 +244,8 @@ __global__ __launch_bounds__(kEcThreads) void edgeconv_fwd_grouped_kernel(
   if (!part) return;
 #pragma unroll
   for (int v = 0; v < 4; ++v) {            // sum of squares: every group holds a share
-    if constexpr (G == 4) sumsq[v] += __uint_as_float(lane_xor<16>(__float_as_uint(sumsq[v])));
-    sumsq[v] += __uint_as_float(lane_xor<32>(__float_as_uint(sumsq[v])));
+    if constexpr (G == 4) sumsq[v] += lane_xor_f<16>(sumsq[v]);
+    sumsq[v] += lane_xor_f<32>(sumsq[v]);
   }
   if (grp == 0) {
 #pragma unroll
@@ -453,11 +453,11 @@ __global__ __launch_bounds__(kEcThreads) void edgeconv_bwd_grouped_kernel(
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
       if constexpr (G == 4) {
-        acc[v] += __uint_as_float(lane_xor<16>(__float_as_uint(acc[v])));
-        accq[v] += __uint_as_float(lane_xor<16>(__float_as_uint(accq[v])));
+        acc[v] += lane_xor_f<16>(acc[v]);
+        accq[v] += lane_xor_f<16>(accq[v]);
       }
-      acc[v] += __uint_as_float(lane_xor<32>(__float_as_uint(acc[v])));
-      accq[v] += __uint_as_float(lane_xor<32>(__float_as_uint(accq[v])));
+      acc[v] += lane_xor_f<32>(acc[v]);
+      accq[v] += lane_xor_f<32>(accq[v]);
     }
     if (grp == 0) {
       float dp[4], dq[4];

@@ -15,18 +15,12 @@ __device__ __forceinline__ float ex_cost(float ax, float ay, float az, float bx,
   return __builtin_amdgcn_sqrtf(fma_rn(dz, dz, fma_rn(dy, dy, dx * dx)));
 }
 
-template <int M>
-__device__ __forceinline__ float xor_f(float v) { return __uint_as_float(lane_xor<M>(__float_as_uint(v))); }
-
-template <int M>
-__device__ __forceinline__ int xor_i(int v) { return (int)lane_xor<M>((unsigned)v); }
-
 // (best value, its rank, second-best value) of two lanes: the lower (value, rank) wins; the second best is the smaller
 // of the loser's best and the winner's second best.
 template <int M>
 __device__ __forceinline__ void fold_best2(float& b1, int& r1, float& b2) {
-  const float o1 = xor_f<M>(b1), o2 = xor_f<M>(b2);
-  const int orr = xor_i<M>(r1);
+  const float o1 = lane_xor_f<M>(b1), o2 = lane_xor_f<M>(b2);
+  const int orr = lane_xor_i<M>(r1);
   if (o1 < b1 || (o1 == b1 && orr < r1)) {
     b2 = __builtin_fminf(b1, o2);
     b1 = o1;
@@ -36,15 +30,9 @@ __device__ __forceinline__ void fold_best2(float& b1, int& r1, float& b2) {
   }
 }
 
-template <int M>
-__device__ __forceinline__ void fold_minmax(float& lo, float& hi) {
-  lo = __builtin_fminf(lo, xor_f<M>(lo));
-  hi = __builtin_fmaxf(hi, xor_f<M>(hi));
-}
-
 __device__ __forceinline__ void fold_minmax_wave(float& lo, float& hi) {
-  fold_minmax<1>(lo, hi); fold_minmax<2>(lo, hi); fold_minmax<4>(lo, hi);
-  fold_minmax<8>(lo, hi); fold_minmax<16>(lo, hi); fold_minmax<32>(lo, hi);
+  lo = wave_min(lo);
+  hi = wave_max(hi);
 }
 
 // rotated tie-break: equal values between objects go to the lowest (j - i) mod N

@@ -28,9 +28,6 @@ constexpr int kEcThreads = 256;
 constexpr int kEcWaves = kEcThreads / 64;
 constexpr int kEcSumWaves = 16;                        // K12's waves: the cost and gap sums follow its order
 
-template <int M>
-__device__ __forceinline__ float fold_min(float v) { return __builtin_fminf(v, xor_f<M>(v)); }
-
 // T objects per lane: N <= 64 T.
 template <int T>
 __global__ __launch_bounds__(kEcThreads) void emd_cross_kernel(const float* __restrict__ xyz1,
@@ -212,8 +209,7 @@ __global__ __launch_bounds__(kEcThreads) void emd_cross_kernel(const float* __re
       for (int t = 0; t < T; ++t) {
         u = __builtin_fminf(u, ex_cost(xx, xy, xz, ox[t], oy[t], oz[t]) + price[lane + 64 * t]);
       }
-      u = fold_min<1>(u); u = fold_min<2>(u); u = fold_min<4>(u);
-      u = fold_min<8>(u); u = fold_min<16>(u); u = fold_min<32>(u);
+      u = wave_min(u);
       if (lane == 0) {
         int j = asg[i];
         if ((unsigned)j >= (unsigned)N) j = 0;         // never: the assignment is a permutation

@@ -37,18 +37,6 @@ struct ExpShape {
 // the length of a tree edge; the forward's penalised test and the backward's recompute it from the same bits
 __device__ __forceinline__ float exp_len(float d2) { return sqrtf(d2); }
 
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long w) {
-#define FPSG_EXP_MIN(M)                                                                         \
-  {                                                                                             \
-    const unsigned long long o = ((unsigned long long)lane_xor<M>((unsigned)(w >> 32)) << 32) | \
-                                 (unsigned long long)lane_xor<M>((unsigned)w);                  \
-    w = o < w ? o : w;                                                                          \
-  }
-  FPSG_EXP_MIN(1) FPSG_EXP_MIN(2) FPSG_EXP_MIN(4) FPSG_EXP_MIN(8) FPSG_EXP_MIN(16) FPSG_EXP_MIN(32)
-#undef FPSG_EXP_MIN
-  return w;
-}
-
 template <int V>
 __global__ __launch_bounds__(ExpShape<V>::kThreads) void expansion_fwd_kernel(
     const float* __restrict__ xyz, int P, int total, float lambda, int32_t* __restrict__ parent,

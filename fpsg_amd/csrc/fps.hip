@@ -23,25 +23,6 @@ namespace {
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
-template <int M>
-__device__ __forceinline__ unsigned long long fps_max_xor(unsigned long long v) {
-  const unsigned lo = lane_xor<M>((unsigned)v), hi = lane_xor<M>((unsigned)(v >> 32));
-  const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-  return o > v ? o : v;
-}
-
-// max over the aligned groups of G lanes (G a power of two up to 64); every lane of a group receives it
-template <int G>
-__device__ __forceinline__ unsigned long long fps_group_max(unsigned long long v) {
-  if (G > 1) v = fps_max_xor<1>(v);
-  if (G > 2) v = fps_max_xor<2>(v);
-  if (G > 4) v = fps_max_xor<4>(v);
-  if (G > 8) v = fps_max_xor<8>(v);
-  if (G > 16) v = fps_max_xor<16>(v);
-  if (G > 32) v = fps_max_xor<32>(v);
-  return v;
-}
-
 __device__ __forceinline__ float fps_readlane(float v, int lane) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
@@ -91,7 +72,7 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ xyz, i
       const unsigned long long key = ((unsigned long long)__float_as_uint(D[k]) << 32) | (nbase - (unsigned)(k * T));
       best = key > best ? key : best;
     }
-    const unsigned long long wbest = fps_group_max<64>(best);
+    const unsigned long long wbest = group_max_u64<64>(best);
     // the coordinates of this thread's best point (a select chain: a run-time register index would go to scratch)
     const int kb = (int)(~(unsigned)best >> LOG_T);
     float bx = x[0], by = y[0], bz = z[0];
@@ -117,7 +98,7 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ xyz, i
       asm volatile("" ::: "memory");
       const v4u sl = slot_kxy[buf][lane & (W - 1)];
       const float slz = slot_z[buf][lane & (W - 1)];
-      win = fps_group_max<W>(((unsigned long long)sl.y << 32) | sl.x);
+      win = group_max_u64<W>(((unsigned long long)sl.y << 32) | sl.x);
       // index = tid + k T: the winner's wave, whose slot lane `owner` has just read
       const unsigned wi = (unsigned)__builtin_amdgcn_readfirstlane((int)~(unsigned)win);
       const int owner = (int)((wi & (unsigned)(T - 1)) >> 6);

@@ -90,18 +90,99 @@ __device__ __forceinline__ unsigned lane_xor(unsigned v) {
   if (M == 16) return (unsigned)__builtin_amdgcn_ds_swizzle(x, (16 << 10) | 0x1F);         // bit mode: xor 16
   return (unsigned)__shfl_xor(x, 32, 64);
 }
+template <int M>
+__device__ __forceinline__ float lane_xor_f(float v) { return __uint_as_float(lane_xor<M>(__float_as_uint(v))); }
+template <int M>
+__device__ __forceinline__ int lane_xor_i(int v) { return (int)lane_xor<M>((unsigned)v); }
+// a 64-bit word: the two halves exchanged separately
+template <int M>
+__device__ __forceinline__ unsigned long long lane_xor64(unsigned long long v) {
+  const unsigned lo = lane_xor<M>((unsigned)v), hi = lane_xor<M>((unsigned)(v >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
 
-
-// Sum over the 64 lanes of a wave, every lane receives the total; a fixed balanced tree (deterministic).
+// Reductions over the 64 lanes of a wave, every lane receives the result: the xor butterfly over 1, 2, 4, 8, 16, 32, a
+// fixed balanced tree (deterministic).
 __device__ __forceinline__ float wave_sum(float v) {
-  v += __uint_as_float(lane_xor<1>(__float_as_uint(v)));
-  v += __uint_as_float(lane_xor<2>(__float_as_uint(v)));
-  v += __uint_as_float(lane_xor<4>(__float_as_uint(v)));
-  v += __uint_as_float(lane_xor<8>(__float_as_uint(v)));
-  v += __uint_as_float(lane_xor<16>(__float_as_uint(v)));
-  v += __uint_as_float(lane_xor<32>(__float_as_uint(v)));
+  v += lane_xor_f<1>(v);
+  v += lane_xor_f<2>(v);
+  v += lane_xor_f<4>(v);
+  v += lane_xor_f<8>(v);
+  v += lane_xor_f<16>(v);
+  v += lane_xor_f<32>(v);
   return v;
 }
+__device__ __forceinline__ int wave_sum(int v) {
+  v += lane_xor_i<1>(v);
+  v += lane_xor_i<2>(v);
+  v += lane_xor_i<4>(v);
+  v += lane_xor_i<8>(v);
+  v += lane_xor_i<16>(v);
+  v += lane_xor_i<32>(v);
+  return v;
+}
+// wave_sum on a double: the same butterfly, the two halves exchanged separately
+template <int M>
+__device__ __forceinline__ double lane_xor_d(double v) {
+  return __longlong_as_double((long long)lane_xor64<M>((unsigned long long)__double_as_longlong(v)));
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+  v += lane_xor_d<1>(v);
+  v += lane_xor_d<2>(v);
+  v += lane_xor_d<4>(v);
+  v += lane_xor_d<8>(v);
+  v += lane_xor_d<16>(v);
+  v += lane_xor_d<32>(v);
+  return v;
+}
+// fmaxf / fminf: a NaN lane is ignored
+__device__ __forceinline__ float wave_max(float v) {
+  v = __builtin_fmaxf(v, lane_xor_f<1>(v));
+  v = __builtin_fmaxf(v, lane_xor_f<2>(v));
+  v = __builtin_fmaxf(v, lane_xor_f<4>(v));
+  v = __builtin_fmaxf(v, lane_xor_f<8>(v));
+  v = __builtin_fmaxf(v, lane_xor_f<16>(v));
+  v = __builtin_fmaxf(v, lane_xor_f<32>(v));
+  return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+  v = __builtin_fminf(v, lane_xor_f<1>(v));
+  v = __builtin_fminf(v, lane_xor_f<2>(v));
+  v = __builtin_fminf(v, lane_xor_f<4>(v));
+  v = __builtin_fminf(v, lane_xor_f<8>(v));
+  v = __builtin_fminf(v, lane_xor_f<16>(v));
+  v = __builtin_fminf(v, lane_xor_f<32>(v));
+  return v;
+}
+
+// The same folds on a 64-bit word, e.g. (key << 32) | index: the minimum is an argmin with ties to the lower index.
+template <int M>
+__device__ __forceinline__ unsigned long long min_xor_u64(unsigned long long v) {
+  const unsigned long long o = lane_xor64<M>(v);
+  return o < v ? o : v;
+}
+template <int M>
+__device__ __forceinline__ unsigned long long max_xor_u64(unsigned long long v) {
+  const unsigned long long o = lane_xor64<M>(v);
+  return o > v ? o : v;
+}
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+  v = min_xor_u64<1>(v); v = min_xor_u64<2>(v); v = min_xor_u64<4>(v);
+  v = min_xor_u64<8>(v); v = min_xor_u64<16>(v); v = min_xor_u64<32>(v);
+  return v;
+}
+// max over the aligned groups of G lanes (G a power of two up to 64); every lane of a group receives it
+template <int G>
+__device__ __forceinline__ unsigned long long group_max_u64(unsigned long long v) {
+  if (G > 1) v = max_xor_u64<1>(v);
+  if (G > 2) v = max_xor_u64<2>(v);
+  if (G > 4) v = max_xor_u64<4>(v);
+  if (G > 8) v = max_xor_u64<8>(v);
+  if (G > 16) v = max_xor_u64<16>(v);
+  if (G > 32) v = max_xor_u64<32>(v);
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) { return group_max_u64<64>(v); }
 
 // Sums of four values over the 64 lanes, delivered in lane 63 (other lanes: partial sums): the row_shr / row_bcast DPP
 // tree -- six dependent adds per value, no LDS crossbar operation, the four chains interleaved so that a DPP operand

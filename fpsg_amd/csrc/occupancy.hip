@@ -42,19 +42,6 @@ __device__ __forceinline__ unsigned long long oc_key(float d, int lin) {
   return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)lin;
 }
 
-template <int M>
-__device__ __forceinline__ unsigned long long oc_min_xor(unsigned long long v) {
-  const unsigned lo = lane_xor<M>((unsigned)v), hi = lane_xor<M>((unsigned)(v >> 32));
-  const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-  return o < v ? o : v;
-}
-
-__device__ __forceinline__ unsigned long long oc_wave_min(unsigned long long v) {
-  v = oc_min_xor<1>(v); v = oc_min_xor<2>(v); v = oc_min_xor<4>(v);
-  v = oc_min_xor<8>(v); v = oc_min_xor<16>(v); v = oc_min_xor<32>(v);
-  return v;
-}
-
 __device__ __forceinline__ int oc_clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 __global__ __launch_bounds__(kOcThreads) void occupancy_kernel(const float* __restrict__ xyz, int S, int N, int r,
@@ -144,7 +131,7 @@ __global__ __launch_bounds__(kOcThreads) void occupancy_kernel(const float* __re
           const int ck = oc_clampi((int)__builtin_rintf(centre + uz * sl), 0, rm1);
           const int ckl = klo[ci * r + cj];
           if (ck >= ckl && ck <= rm1 - ckl) best = oc_key(oc_d(tx, ty, tz, ci, cj, ck), (ci * r + cj) * r + ck);
-          best = oc_wave_min(best);
+          best = wave_min_u64(best);
           const float U = __uint_as_float((unsigned)(best >> 32));   // +NaN pattern if none (never): window = grid
           // 2. the window of columns that can hold a node with d <= U (a superset: one node of margin)
           const float sU = __builtin_sqrtf(U);
@@ -188,7 +175,7 @@ __global__ __launch_bounds__(kOcThreads) void occupancy_kernel(const float* __re
             }
           }
         }
-        best = oc_wave_min(best);
+        best = wave_min_u64(best);
         if (lane == 0) cellbuf[fb_slot[e]] = (int)(unsigned)best;       // always a retained node: see step 1
       }
       __syncthreads();

@@ -4,12 +4,10 @@
 // graph.  The definitions are in include/fpsg_hip.h (K33) and DESIGN.md.
 //
 // Structure:
-//   * K33a, selection: K21's sweep with longer lists.  One wave per workgroup, grid (ceil(N / 64), B); a lane owns ONE
-//     query and sweeps every candidate of its cloud in ascending order, candidates staged through LDS in tiles of 1024
-//     (broadcast ds_read_b128 per coordinate).  The sorted top-K of (d2, j) lives in registers, K a template parameter
-//     (8, 16 or 32: the call's k rounded up; the first k slots of the sorted top-K ARE the top-k), every loop over it
-//     unrolled.  Ascending sweep + strict comparison = the lexicographic (d2, j) order.  The lists go to nbr_idx, or to
-//     the workspace when the caller does not want them.
+//   * K33a, selection: K21's sweep (self_knn_sweep of self_knn.h, described in repulsion.hip) with longer lists.  One
+//     wave per workgroup, grid (ceil(N / 64), B); a lane owns ONE query.  K is a template parameter (8, 16 or 32: the
+//     call's k rounded up; the first k slots of the sorted top-K ARE the top-k).  The lists go to nbr_idx, or to the
+//     workspace when the caller does not want them.
 //   * K33a, PCA: one thread per point reads its list back, gathers the neighbours, and works on offsets from the point
 //     itself (exact where the cloud sits far from the origin): mean, centred covariance, trace-scaled, eight cyclic
 //     Jacobi sweeps on the 3x3 (a fixed count), the column of the smallest diagonal entry, normalised; then the sign.
@@ -22,39 +20,21 @@
 //   * every index read from a list is checked against [0, N) before it is used; every trip count comes from N and k.
 #include <cmath>
 
-#include "chamfer_dist.h"
+#include "self_knn.h"
 
 namespace fpsg {
 namespace {
 
 constexpr int kPnThreads = 64;                                    // selection: one wave per workgroup
-constexpr int kPnTile = 1024;                                     // candidates per LDS tile
-constexpr int kPnPerThread = kPnTile / kPnThreads;
 constexpr int kPnPcaThreads = 256;
 constexpr int kPnJacobiSweeps = 8;
-
-// rep_insert of K21: (c, j) into the sorted list, the caller has checked c < d[K - 1]; strict comparisons, so on equal
-// distances the resident, which has the lower index, stays in front.
-template <int K>
-__device__ __forceinline__ void pn_insert(float (&d)[K], int (&ix)[K], float c, int j) {
-  bool lt[K];
-#pragma unroll
-  for (int s = 0; s < K; ++s) lt[s] = c < d[s];
-#pragma unroll
-  for (int s = K - 1; s >= 1; --s) {
-    ix[s] = lt[s - 1] ? ix[s - 1] : (lt[s] ? j : ix[s]);
-    d[s] = __builtin_amdgcn_fmed3f(d[s - 1], d[s], c);
-  }
-  ix[0] = lt[0] ? j : ix[0];
-  d[0] = lt[0] ? c : d[0];
-}
 
 template <int K>
 __global__ __launch_bounds__(kPnThreads) void pn_select_kernel(const float* __restrict__ xyz, int N, int k,
                                                                int32_t* __restrict__ nbr_idx) {
-  __shared__ __attribute__((aligned(16))) float sx[kPnTile];
-  __shared__ __attribute__((aligned(16))) float sy[kPnTile];
-  __shared__ __attribute__((aligned(16))) float sz[kPnTile];
+  __shared__ __attribute__((aligned(16))) float sx[kSelfKnnTile];
+  __shared__ __attribute__((aligned(16))) float sy[kSelfKnnTile];
+  __shared__ __attribute__((aligned(16))) float sz[kSelfKnnTile];
   const size_t b = blockIdx.y;
   const float* __restrict__ x = xyz + b * (size_t)N * 3;
   const int i = (int)blockIdx.x * kPnThreads + (int)threadIdx.x;
@@ -65,37 +45,7 @@ __global__ __launch_bounds__(kPnThreads) void pn_select_kernel(const float* __re
 
   float d[K];
   int ix[K];
-#pragma unroll
-  for (int s = 0; s < K; ++s) {
-    d[s] = INFINITY;
-    ix[s] = -1;
-  }
-
-  for (int j0 = 0; j0 < N; j0 += kPnTile) {                       // uniform trip count
-    __syncthreads();                                              // the previous tile has been read
-#pragma unroll
-    for (int u = 0; u < kPnPerThread; ++u) {                      // padding: NaN, which enters no list
-      const int t = (int)threadIdx.x + u * kPnThreads;
-      const int j = j0 + t;
-      const bool ok = j < N;
-      sx[t] = ok ? x[3 * (size_t)j + 0] : NAN;
-      sy[t] = ok ? x[3 * (size_t)j + 1] : NAN;
-      sz[t] = ok ? x[3 * (size_t)j + 2] : NAN;
-    }
-    __syncthreads();
-    const int groups = (min(kPnTile, N - j0) + 3) >> 2;
-    for (int g = 0; g < groups; ++g) {
-      const v4f X = *reinterpret_cast<const v4f*>(sx + 4 * g);
-      const v4f Y = *reinterpret_cast<const v4f*>(sy + 4 * g);
-      const v4f Z = *reinterpret_cast<const v4f*>(sz + 4 * g);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int j = j0 + 4 * g + c;
-        const float d2 = sq_dist(qx, qy, qz, X[c], Y[c], Z[c]);
-        if ((d2 < d[K - 1]) & (j != i)) pn_insert<K>(d, ix, d2, j);
-      }
-    }
-  }
+  self_knn_sweep<K, kPnThreads>(x, N, i, qx, qy, qz, d, ix, sx, sy, sz);     // every thread of the workgroup
 
   if (live) {
     int32_t* __restrict__ row = nbr_idx + (b * (size_t)N + (size_t)i) * (size_t)k;
@@ -278,35 +228,6 @@ __global__ __launch_bounds__(kRvThreads) void pn_reverse_kernel(const int32_t* _
   }
 }
 
-__device__ __forceinline__ unsigned long long pn_lane_xor64(unsigned long long w, int m) {
-  unsigned hi = (unsigned)(w >> 32), lo = (unsigned)w;
-  switch (m) {
-    case 1: hi = lane_xor<1>(hi); lo = lane_xor<1>(lo); break;
-    case 2: hi = lane_xor<2>(hi); lo = lane_xor<2>(lo); break;
-    case 4: hi = lane_xor<4>(hi); lo = lane_xor<4>(lo); break;
-    case 8: hi = lane_xor<8>(hi); lo = lane_xor<8>(lo); break;
-    case 16: hi = lane_xor<16>(hi); lo = lane_xor<16>(lo); break;
-    default: hi = lane_xor<32>(hi); lo = lane_xor<32>(lo); break;
-  }
-  return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned long long pn_wave_min(unsigned long long w) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) {
-    const unsigned long long o = pn_lane_xor64(w, m);
-    w = o < w ? o : w;
-  }
-  return w;
-}
-__device__ __forceinline__ unsigned long long pn_wave_max(unsigned long long w) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) {
-    const unsigned long long o = pn_lane_xor64(w, m);
-    w = o > w ? o : w;
-  }
-  return w;
-}
-
 constexpr int kOrMaxThreads = 1024;
 constexpr int kOrMaxWaves = kOrMaxThreads / kWave;
 
@@ -347,7 +268,7 @@ __global__ __launch_bounds__(kOrMaxThreads) void pn_orient_kernel(const float* _
       const unsigned long long w = ((unsigned long long)key[v] << 32) | (unsigned)v;
       best = w < best ? w : best;
     }
-    best = pn_wave_min(best);
+    best = wave_min_u64(best);
     if (lane == 0) red[wave] = best;
     __syncthreads();
     best = red[0];
@@ -363,7 +284,7 @@ __global__ __launch_bounds__(kOrMaxThreads) void pn_orient_kernel(const float* _
           top = w > top ? w : top;
         }
       }
-      top = pn_wave_max(top);
+      top = wave_max_u64(top);
       if (lane == 0) red[kOrMaxWaves + wave] = top;
       __syncthreads();
       top = red[kOrMaxWaves];

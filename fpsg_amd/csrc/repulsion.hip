@@ -4,15 +4,16 @@
 //
 // Structure:
 //   * forward: grid (ceil(N / 256), B), 256 threads; a lane owns ONE query point and sweeps every candidate j of its
-//     cloud in ascending order.  Candidates pass through LDS in tiles of 1024 (x, y, z as three arrays: every lane of a
-//     wave reads the same four candidates with one broadcast ds_read_b128 per coordinate).  The sorted top-k of
-//     (d2, j) lives in registers: a K-slot array, K a template parameter (1..8), every loop over it fully unrolled, no
-//     dynamic index.  The sweep is ascending in j, so a candidate enters only where d2 < the list's last d2 (strictly):
-//     an equal distance belongs to a higher index and loses the tie.  j == i is skipped by index.  After the sweep the
-//     lane writes its list and adds its K terms (a balanced tree over eight slots, absent ones +0), the wave sums them
-//     by the fixed tree, thread 0 adds the four wave sums as (w0 + w1) + (w2 + w3) and writes ONE partial per
-//     workgroup; a second, tiny launch adds a cloud's partials in ascending order and scales by 1 / (N k).  No
-//     atomics, nothing between workgroups inside a launch.
+//     cloud in ascending order: the sweep of self_knn.h (K33a calls it as self_knn_sweep; here its pieces, see the
+//     kernel).  Candidates pass through LDS in tiles of 1024 (x, y, z as three arrays: every lane of a wave reads the
+//     same four candidates with one broadcast ds_read_b128 per coordinate).  The sorted top-k of (d2, j) lives in
+//     registers: a K-slot array, K a template parameter (1..8), every loop over it fully unrolled, no dynamic index.
+//     The sweep is ascending in j, so a candidate enters only where d2 < the list's last d2 (strictly): an equal
+//     distance belongs to a higher index and loses the tie.  j == i is skipped by index.  After the sweep the lane
+//     writes its list and adds its K terms (a balanced tree over eight slots, absent ones +0), the wave sums them by
+//     the fixed tree, thread 0 adds the four wave sums as (w0 + w1) + (w2 + w3) and writes ONE partial per workgroup;
+//     a second, tiny launch adds a cloud's partials in ascending order and scales by 1 / (N k).  No atomics, nothing
+//     between workgroups inside a launch.
 //   * backward: the same grid and sweep in GATHER form.  The lane that owns point j adds its own k terms in list order
 //     (x_m gathered by index), then sweeps every i in ascending order -- x_i and i's k-th pair (d2, idx) staged through
 //     LDS -- and adds the reverse term wherever (d2(i, j), j) <= that pair lexicographically, i != j: exactly j in K(i),
@@ -21,14 +22,14 @@
 //     enters no list and no sum.  Every trip count comes from N and k; an index outside [0, N) is never dereferenced.
 #include <cmath>
 
-#include "chamfer_dist.h"
+#include "self_knn.h"
 
 namespace fpsg {
 namespace {
 
 constexpr int kRepThreads = 256;
 constexpr int kRepWaves = kRepThreads / kWave;
-constexpr int kRepTile = 1024;                                    // candidates per LDS tile
+constexpr int kRepTile = kSelfKnnTile;                            // candidates per LDS tile
 constexpr int kRepPerThread = kRepTile / kRepThreads;
 constexpr float kRepFloorD2 = 1e-12f;                             // below this squared distance: r = 1e-6, derivative 0
 constexpr float kRepFloorR = 1e-6f;
@@ -53,36 +54,6 @@ __device__ __forceinline__ float rep_slope(float d2, float ih2) {
   const float r = __builtin_amdgcn_sqrtf(d2);
   const float e = rep_exp(d2, ih2);
   return -(e * (0.5f * __builtin_amdgcn_rcpf(r)) - (e * r) * ih2);
-}
-
-// Puts (c, j) into the sorted list; the caller has checked c < d[K - 1].  Branch-free: slot s becomes the median of
-// (d[s - 1], d[s], c) -- d[s - 1] where c lands above it, c where it lands here, d[s] otherwise -- one v_med3_f32, and
-// its index follows the same two comparisons (strict: on equal distances the resident, which has the lower index, stays).
-template <int K>
-__device__ __forceinline__ void rep_insert(float (&d)[K], int (&ix)[K], float c, int j) {
-  bool lt[K];
-#pragma unroll
-  for (int s = 0; s < K; ++s) lt[s] = c < d[s];
-#pragma unroll
-  for (int s = K - 1; s >= 1; --s) {
-    ix[s] = lt[s - 1] ? ix[s - 1] : (lt[s] ? j : ix[s]);
-    d[s] = __builtin_amdgcn_fmed3f(d[s - 1], d[s], c);
-  }
-  ix[0] = lt[0] ? j : ix[0];
-  d[0] = lt[0] ? c : d[0];
-}
-
-// Loads candidates j0 .. j0 + kRepTile of cloud `x` into the tile (NaN past the end of the cloud).
-__device__ __forceinline__ void rep_stage_xyz(const float* __restrict__ x, int N, int j0, float* sx, float* sy, float* sz) {
-#pragma unroll
-  for (int u = 0; u < kRepPerThread; ++u) {
-    const int t = (int)threadIdx.x + u * kRepThreads;
-    const int j = j0 + t;
-    const bool ok = j < N;
-    sx[t] = ok ? x[3 * (size_t)j + 0] : NAN;
-    sy[t] = ok ? x[3 * (size_t)j + 1] : NAN;
-    sz[t] = ok ? x[3 * (size_t)j + 2] : NAN;
-  }
 }
 
 template <int K>
@@ -110,9 +81,11 @@ __global__ __launch_bounds__(kRepThreads) void repulsion_fwd_kernel(const float*
     ix[s] = -1;
   }
 
+  // self_knn_sweep<K, kRepThreads> of self_knn.h, written out: called as the helper, K = 2 takes one VGPR more (36
+  // for 35; the other K one fewer, a different instruction stream for all), so K21 keeps the loop it was measured with.
   for (int j0 = 0; j0 < N; j0 += kRepTile) {                      // every thread of the workgroup: uniform trip count
     __syncthreads();                                              // the previous tile has been read
-    rep_stage_xyz(x, N, j0, sx, sy, sz);
+    stage_xyz_tile<kRepThreads>(x, N, j0, sx, sy, sz);
     __syncthreads();
     const int groups = (min(kRepTile, N - j0) + 3) >> 2;
     for (int g = 0; g < groups; ++g) {
@@ -123,7 +96,7 @@ __global__ __launch_bounds__(kRepThreads) void repulsion_fwd_kernel(const float*
       for (int c = 0; c < 4; ++c) {
         const int j = j0 + 4 * g + c;
         const float d2 = sq_dist(qx, qy, qz, X[c], Y[c], Z[c]);
-        if ((d2 < d[K - 1]) & (j != i)) rep_insert<K>(d, ix, d2, j);
+        if ((d2 < d[K - 1]) & (j != i)) topk_insert<K>(d, ix, d2, j);
       }
     }
   }
@@ -195,7 +168,7 @@ __global__ __launch_bounds__(kRepThreads) void repulsion_bwd_kernel(const float*
 
   for (int i0 = 0; i0 < N; i0 += kRepTile) {
     __syncthreads();
-    rep_stage_xyz(x, N, i0, sx, sy, sz);
+    stage_xyz_tile<kRepThreads>(x, N, i0, sx, sy, sz);
 #pragma unroll
     for (int u = 0; u < kRepPerThread; ++u) {
       const int t = (int)threadIdx.x + u * kRepThreads;

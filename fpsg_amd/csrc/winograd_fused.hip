@@ -347,10 +347,10 @@ __global__ __launch_bounds__(kFusedThreads) void wino4_fused_c64_kernel(const fl
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float a0 = st0[r], a1 = st1[r];
-      a0 += __uint_as_float(lane_xor<1>(__float_as_uint(a0))); a1 += __uint_as_float(lane_xor<1>(__float_as_uint(a1)));
-      a0 += __uint_as_float(lane_xor<2>(__float_as_uint(a0))); a1 += __uint_as_float(lane_xor<2>(__float_as_uint(a1)));
-      a0 += __uint_as_float(lane_xor<4>(__float_as_uint(a0))); a1 += __uint_as_float(lane_xor<4>(__float_as_uint(a1)));
-      a0 += __uint_as_float(lane_xor<8>(__float_as_uint(a0))); a1 += __uint_as_float(lane_xor<8>(__float_as_uint(a1)));
+      a0 += lane_xor_f<1>(a0); a1 += lane_xor_f<1>(a1);
+      a0 += lane_xor_f<2>(a0); a1 += lane_xor_f<2>(a1);
+      a0 += lane_xor_f<4>(a0); a1 += lane_xor_f<4>(a1);
+      a0 += lane_xor_f<8>(a0); a1 += lane_xor_f<8>(a1);
       if (col == 0) {
         ulds[((wave * 4 + kk) * 4 + r) * 2] = a0;
         ulds[((wave * 4 + kk) * 4 + r) * 2 + 1] = a1;

@@ -17,7 +17,7 @@ import _mesh_ref as mref
 import _point_mesh_ref as pmref
 import _point_normals_ref as ref
 import test_surface_gpu as k31                    # its untrained model
-from fpsg_amd import meshes, normals
+from fpsg_amd import meshes, metrics, normals
 
 pytestmark = pytest.mark.gpu
 
@@ -67,6 +67,16 @@ def test_lists_on_ties_and_duplicates(gpu):
     _, _, idx = _estimate(gpu, x[None], 9)
     assert np.array_equal(idx[0], ref.neighbour_lists(x, 9))
     assert idx[0, :40, 0].tolist() == list(range(40, 80)) and idx[0, 40:, 0].tolist() == list(range(40))
+
+
+@pytest.mark.parametrize("N", [9, 65, 1030])         # the smallest cloud for k = 8; past K33a's 64 threads; past one tile
+def test_lists_are_the_repulsion_lists(gpu, N):
+    """One definition: K33a and K21 keep the lexicographic (d2, j) top-8 over the same sq_dist (csrc/self_knn.h)."""
+    x = torch.from_numpy(_random_clouds(2, N, 33)).to(gpu)
+    idx = normals.point_normals(x, 8, neighbors=True)[-1]
+    rep = metrics.repulsion_loss(x, k=8, return_info=True)[1]["idx"]
+    assert idx.shape == rep.shape == (2, N, 8)
+    assert torch.equal(idx, rep)
 
 
 # ---- (b) normals against float64 -------------------------------------------------------------------------------------
