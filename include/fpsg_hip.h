@@ -65,7 +65,8 @@ int fpsg_chamfer_fwd_variant(const float* xyz1, const float* xyz2, int B, int N,
  * 64*R rows x W*cpw*16 candidates leave 32-bit partial keys in the caller's workspace (a tile's exact minimum with
  * its six lowest mantissa bits replaced by where inside the tile it was found), a second launch re-evaluates the
  * named range of every tile whose truncated minimum equals the smallest one and so recovers the exact distances and
- * first-minimum indices.  Bit-identical results to fpsg_chamfer_fwd.
+ * first-minimum indices.  Bit-identical results to fpsg_chamfer_fwd.  Deterministic (no float atomics; the
+ * workspace's contents before the call do not matter).
  * ws: fpsg_chamfer_workspace_bytes(B,N,M,variant) bytes, 8-byte aligned.  variant: -1 automatic,
  * else (R==8 ? 100 : 0) + 10*W + cpw with R in {4,8}, W in {1,2,4}, cpw in 1..9.  The workspace size
  * is 0 when this form does not apply: N or M > 4096, or (variant -1) fewer than ~7 pairs of
@@ -146,7 +147,7 @@ int fpsg_chamfer_bwd_losses(const float* xyz1, const float* xyz2, const int32_t*
  * included), equal values -> lower index first.  ws: caller scratch of fpsg_knn_workspace_floats(B,C,N) floats,
  * 16-byte aligned (squared norms + a zero-padded, point-major, k-interleaved copy of x whose 16-byte pieces are the
  * MFMA operands of four channel steps).
- * Two kernels, identical results (bit for bit the oracle's):
+ * Two kernels, identical results (bit for bit the oracle's; deterministic, no atomics on global memory):
  *   - C <= 128 and k <= 24: the streaming kernel (knn_stream.hip) -- a workgroup owns 128 queries, the cloud's
  *     candidates pass once through LDS, a row keeps only the scores above a running lower bound of its k-th best;
  *   - otherwise (C <= 440, k <= 64): the score-tile kernel (knn.hip) -- 16 queries per workgroup, their scores
@@ -948,7 +949,8 @@ int fpsg_wino_filter_grad_transform(int m, const float* dU, int K, int C, float*
  * 7 = 256x128x16 in the same form.  Every other id (tile 8 or 9, anything >= 1000 or below -1) is refused on the host
  * with FPSG_E_SHAPE, and fpsg_gemm_split_workspace_floats returns 0 for it.
  * ws: fpsg_gemm_split_workspace_floats(...) floats (0 when the reduction is not split; then ws may be NULL); a split
- * reduction needs a dense output (ldc == N, sC == M*N).  One batch entry of each matrix must stay below 2 GiB. */
+ * reduction needs a dense output (ldc == N, sC == M*N).  One batch entry of each matrix must stay below 2 GiB.
+ * Both forms are deterministic (no float atomics). */
 size_t fpsg_gemm_split_workspace_floats(int batch, int M, int N, int K, int transB, int variant);
 int fpsg_gemm_split(const float* A, const float* B, float* C, int batch, int M, int N, int K, int lda, int ldb, int ldc,
                     long sA, long sB, long sC, int transB, int variant, float* ws, size_t ws_floats,
@@ -1190,9 +1192,9 @@ int fpsg_flat_swap(float* a, float* b, size_t n, fpsg_stream_t stream);
  *   f = the first face with C_f > t -- a face with q = 0 is never chosen;
  *   s = sqrt(u1); w0 = 1 - s, w1 = s (1 - u2), w2 = s u2;  p = (w0 a + w1 b) + w2 c per coordinate, fp32, no fma.
  * fpsg_mesh_cdf writes cdf; its workspace (fpsg_mesh_cdf_workspace_bytes, 8-byte aligned) holds the areas and block
- * sums.  fpsg_mesh_sample takes `total` = cdf[F-1], which the caller reads back from the device: total = 0 is refused
- * with FPSG_E_SHAPE and a message that names the cause, before any launch.  The kernel clamps what it reads from cdf
- * and faces into range, so a foreign cdf gives wrong samples and never an access outside the buffers.
+ * sums; deterministic.  fpsg_mesh_sample takes `total` = cdf[F-1], which the caller reads back from the device:
+ * total = 0 is refused with FPSG_E_SHAPE and a message that names the cause, before any launch.  The kernel clamps what
+ * it reads from cdf and faces into range, so a foreign cdf gives wrong samples and never an access outside the buffers.
  * Errors, all before any launch: FPSG_E_SHAPE for V, F or m < 1, total = 0 or > F 2^32, a workspace too small;
  * FPSG_E_LIMIT for F > FPSG_MESH_MAX_FACES; FPSG_E_NULL for a null pointer; FPSG_E_ALIGN for a misaligned one (cdf
  * and ws: 8 bytes).  fpsg_mesh_cdf_workspace_bytes returns 0 for a shape the entry refuses.
@@ -1237,6 +1239,8 @@ int fpsg_mesh_sample(const float* verts, int V, const int32_t* faces, int F, con
  * params (HOST pointer, 15 floats): ka[3], kd[3], ks[3], l[3], bg[3].
  * Workspace: fpsg_mesh_render_workspace_bytes (16-byte aligned): projected vertices, the z-buffer, the list of
  * triangles too large for one thread.
+ * Deterministic: the only atomics are the z-buffer's integer minimum and the counter of that list, whose order
+ * does not reach any output.  This holds for fpsg_mesh_render_materials and fpsg_mesh_render_smooth too.
  * Errors, all before any launch: FPSG_E_SHAPE for V, F, n_views, W or H < 1, ssaa outside 1..FPSG_RENDER_MAX_SSAA or
  * not a divisor of W and H, an ortho_scale not positive and finite, log2_shininess outside
  * 0..FPSG_RENDER_MAX_LOG2_SHININESS, a workspace too small; FPSG_E_LIMIT for W or H > FPSG_RENDER_MAX_SIZE, n_views >
@@ -1330,7 +1334,7 @@ int fpsg_mesh_render_materials(const float* verts, int V, const int32_t* faces, 
  *   ks_c spec, as K28 forms it from a base colour.
  * Resolve and image: K27's, per cloud and view.
  * Workspace: fpsg_points_render_workspace_bytes = 16 B n_views N bytes (16-byte aligned): one record per (cloud, view,
- * point).  There is no z-buffer in memory.
+ * point).  There is no z-buffer in memory.  Deterministic (integer LDS atomics only).
  * Errors, all before any launch or copy: FPSG_E_SHAPE for B, N, n_views, W or H < 1, ssaa not 1, 2 or 4 or not a divisor
  * of W and H, an ortho_scale or radius not positive and finite, R out of range, log2_shininess outside
  * 0..FPSG_RENDER_MAX_LOG2_SHININESS, a workspace too small; FPSG_E_LIMIT for N > FPSG_POINTS_MAX_N, W or H >

@@ -325,7 +325,11 @@ def test_a_threshold_that_never_clips_changes_no_bit(gpu, path):
         assert abs(float(opt_a.last_grad_norm) - want) <= 1e-5 * want, (path, it)
     assert torch.equal(opt_a.flat_exp_avg, opt_b.flat_exp_avg) and torch.equal(opt_a.flat_exp_avg_sq, opt_b.flat_exp_avg_sq)
     stats = opt_a.clip_stats()
-    assert stats["steps"] == 4 and stats["clipped"] == 0 and stats["nonfinite"] == 0 and stats["max_norm_seen"] >= want
+    assert stats["steps"] == 4 and stats["clipped"] == 0 and stats["nonfinite"] == 0
+    # the maximum is over the norms as the library rounds them to fp32: never below the last step's own, bit for bit, and
+    # below that step's float64 norm by at most that rounding (one fp32 ulp, 2^-23 relative: when the last step is the
+    # largest, `>= want` itself held only where the rounding went up)
+    assert stats["max_norm_seen"] >= float(opt_a.last_grad_norm) and stats["max_norm_seen"] >= want * (1.0 - 2.0 ** -23)
     assert opt_b.last_grad_norm is None and opt_b.clip_stats()["steps"] == 0
 
 
