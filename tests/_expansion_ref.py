@@ -5,11 +5,17 @@ CPU file checks, on the reference alone, that no edge of theirs sits at the pena
 import numpy as np
 import torch
 
-VALUE_P = (64, 128, 256)
+VALUE_P = (64, 128, 256, 512, 1024)                                   # 1, 2, 4, 8 and 16 vertices per lane
 VALUE_LAMBDAS = (1.0, 1.5, 2.0)
 # one seed per patch size, searched until `threshold_margin` (below) holds at all three lambdas for all four clouds
-VALUE_SEEDS = {64: 11, 128: 28, 256: 1}
+VALUE_SEEDS = {64: 11, 128: 28, 256: 1, 512: 27, 1024: 6}
 MARGIN = 1e-4
+
+
+def value_patches(P):
+    """Patches per cloud of the value tests: 16 up to ``P = 128``, 4 up to 512, 2 at 1024 (the float64 side stays at
+    seconds)."""
+    return 16 if P <= 128 else 4 if P <= 512 else 2
 
 
 def patches(x, P):
@@ -146,12 +152,11 @@ def threshold_margin(x, P, parent, lam):
 
 
 def value_clouds(P):
-    """The four clouds ``[4, N, 3]`` fp32 (CPU) of the value tests at patch size ``P``, ``N = 16 P`` up to ``P = 128``, else
-    ``4 P``: two unit-ball clouds, one ``tanh(randn)`` cloud (the decoder's range), and one "sheet" cloud whose patches are
-    smooth maps of a random 2-D sample scaled to 0.2 with ONE point moved 1.0 away -- every patch has a penalised edge."""
+    """The four clouds ``[4, N, 3]`` fp32 (CPU) of the value tests at patch size ``P``, ``N = value_patches(P) P``: two
+    unit-ball clouds, one ``tanh(randn)`` cloud (the decoder's range), and one "sheet" cloud whose patches are smooth maps of a random 2-D sample scaled to 0.2 with ONE point moved 1.0 away -- every patch has a penalised edge."""
     from conftest import unit_ball_clouds
     seed = VALUE_SEEDS[P]
-    K = 16 if P <= 128 else 4
+    K = value_patches(P)
     N = K * P
     g = torch.Generator().manual_seed(1000 * P + seed)
     ball = torch.from_numpy(unit_ball_clouds(np.random.default_rng(1000 * P + seed), 2, N)).float()

@@ -176,6 +176,19 @@ def test_pooled_variant_matches_unfused_chain(gpu, shape, mode):
     """conv_bn_act_pool == max_pool2d(K5(conv(x))) : pooled output BIT-equal (same arithmetic per
     element, max is exact); gradients agree to summation order (the pooled backward partitions its
     partial sums differently)."""
+    _pooled_variant_against_the_unfused_chain(gpu, shape, mode, "relu")
+
+
+# W a multiple of 4 (two windows a lane) and not (one): the pooled kernels' instantiations without an activation and
+# with the leaky one, which no network of the project takes
+@pytest.mark.parametrize("act", [None, ("leaky", 0.2)], ids=["none", "leaky"])
+@pytest.mark.parametrize("shape", [(37, 16, 28, 28), (20, 24, 30, 30)])
+@pytest.mark.parametrize("mode", ["train", "eval"])
+def test_pooled_variant_of_the_other_activations_matches_unfused_chain(gpu, shape, mode, act):
+    _pooled_variant_against_the_unfused_chain(gpu, shape, mode, act)
+
+
+def _pooled_variant_against_the_unfused_chain(gpu, shape, mode, act):
     from fpsg_amd.fused_bn import conv_bn_act, conv_bn_act_pool, _pool_eligible
     import copy
     torch.manual_seed(sum(shape))
@@ -192,8 +205,8 @@ def test_pooled_variant_matches_unfused_chain(gpu, shape, mode):
     x = torch.randn(*shape, device=gpu)
     x1, x2 = x.clone().requires_grad_(), x.clone().requires_grad_()
     assert _pool_eligible(conv._conv_forward(x, conv.weight, None), pool)
-    y1 = conv_bn_act_pool(conv, bn, pool, x1, "relu")
-    y2 = pool(conv_bn_act(conv2, bn2, x2, "relu"))
+    y1 = conv_bn_act_pool(conv, bn, pool, x1, act)
+    y2 = pool(conv_bn_act(conv2, bn2, x2, act))
     assert y1.shape == (N, C, H // 2, W // 2) and torch.equal(y1, y2)
     g = torch.randn_like(y1)
     y1.backward(g); y2.backward(g)

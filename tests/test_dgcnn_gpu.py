@@ -47,6 +47,11 @@ STREAM_SHAPES = [(1, 3, 16, 5), (1, 3, 31, 20), (2, 3, 129, 20), (9, 3, 300, 20)
                  (2, 4, 700, 24), (1, 1, 257, 3), (2, 2, 2048, 20), (17, 3, 255, 20), (1, 3, 24, 24),     # C = 1..4, k = N
                  (1, 64, 64, 20), (2, 64, 65, 1), (1, 64, 1000, 20), (1, 48, 257, 9), (1, 128, 33, 20), (2, 128, 200, 13),
                  (1, 100, 777, 20), (1, 17, 2048, 20), (10, 64, 256, 20)]
+# the score-tile instantiations knn_kernel<VPL, C4T, NW, PM> the shapes above leave out (tests/_dispatch.py): VPL 8 / 16 /
+# 32 for N up to 512 / up to 1024 / beyond; 33..64 and 65..128 channels without the point-major copy (C no multiple of
+# 16) and with it
+STREAM_SHAPES += [(1, 40, 65, 9), (1, 100, 130, 9), (1, 17, 600, 9), (1, 40, 600, 9), (1, 128, 600, 9),
+                  (1, 40, 1040, 9), (1, 100, 1040, 9), (1, 80, 1040, 9)]
 
 
 @pytest.mark.parametrize("B,C,N,k", STREAM_SHAPES)

@@ -57,6 +57,15 @@ def test_against_hungarian(gpu):
     _check_bracket(A, B, cost, gap, status, eps)
 
 
+def test_against_hungarian_n600(gpu):
+    """One pair inside emd_cross_kernel<16> (512 < N <= 1024), at a size that fills none of its 16 points per lane."""
+    rng = np.random.default_rng(150)
+    A = unit_ball_clouds(rng, 1, 600)
+    B = unit_ball_clouds(rng, 1, 600)
+    cost, gap, status, _, eps = _matrix(torch.from_numpy(A).to(gpu), torch.from_numpy(B).to(gpu))
+    _check_bracket(A, B, cost, gap, status, eps)
+
+
 def _same_as_k12(gpu, A, B, pairs, cost, gap, status, rounds, eps):
     from fpsg_amd.metrics import emd_exact
     for a, b in pairs:
@@ -69,14 +78,18 @@ def _same_as_k12(gpu, A, B, pairs, cost, gap, status, rounds, eps):
         assert abs(gap[a, b] - g12) <= 1e-6 * c12, (a, b, gap[a, b], g12)
 
 
-@pytest.mark.parametrize("N", [300, 512])
+@pytest.mark.parametrize("N", [300, 512, 257, 513, 1024, 1025])
 def test_same_trajectory_as_k12(gpu, N):
+    """Both ends of emd_cross_kernel<8> (257, 512) and <16> (513, 1024) and the first N of <32> (1025); two clouds a
+    side at the sizes that only mark a boundary."""
+    sets = 3 if N in (300, 512) else 2
     rng = np.random.default_rng(141 + N)
-    A = unit_ball_clouds(rng, 3, N)
-    B = unit_ball_clouds(rng, 3, N)
+    A = unit_ball_clouds(rng, sets, N)
+    B = unit_ball_clouds(rng, sets, N)
     cost, gap, status, rounds, eps = _matrix(torch.from_numpy(A).to(gpu), torch.from_numpy(B).to(gpu))
     assert (rounds > 0).all()
-    _same_as_k12(gpu, A, B, [(0, 0), (1, 2), (2, 1), (2, 2)], cost, gap, status, rounds, eps)
+    pairs = [(0, 0), (1, 2), (2, 1), (2, 2)] if sets == 3 else [(0, 0), (0, 1), (1, 0), (1, 1)]
+    _same_as_k12(gpu, A, B, pairs, cost, gap, status, rounds, eps)
 
 
 def test_same_trajectory_as_k12_n2048(gpu):

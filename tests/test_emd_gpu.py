@@ -94,18 +94,41 @@ def test_deterministic_and_self_distance(gpu):
 
 
 # ----------------------------------------------------------------- Sinkhorn form (sinkhorn=True)
-@pytest.mark.parametrize("B,N,M,eps", [(2, 300, 500, 0.5), (1, 2048, 2048, 0.0025), (3, 64, 1000, 0.05),
-                                       (2, 1, 7, 0.01), (1, 2500, 2100, 0.02)])
-def test_softmin_vs_oracle(gpu, oracle, B, N, M, eps):
-    from fpsg_amd.metrics import softmin
+# ceil(N / 128) * B >= 4 * 256: two owners per lane (softmin_kernel<2>), with a ragged last group
+SOFTMIN_TWO_OWNERS = [(1024, 70, 33, 0.05), (1024, 128, 129, 0.0025), (512, 129, 64, 0.5)]
+# ceil(max(N, M) / 128) * 4 * B >= 4 * 256: sinkhorn_step_kernel<2>, with unequal clouds that fill no group of 128
+LOOP_TWO_OWNERS = [(256, 100, 37), (256, 70, 129), (300, 1, 9)]
+
+
+def _softmin_inputs(B, N, M):
     rng = np.random.default_rng(N + M)
     x = unit_ball_clouds(rng, B, N)
     y = np.tanh(rng.standard_normal((B, M, 3)) * 0.5).astype(np.float32)
     h = (rng.standard_normal((B, M)) * 2 - np.log(M)).astype(np.float32)
+    return x, y, h
+
+
+@pytest.mark.parametrize("B,N,M,eps", [(2, 300, 500, 0.5), (1, 2048, 2048, 0.0025), (3, 64, 1000, 0.05),
+                                       (2, 1, 7, 0.01), (1, 2500, 2100, 0.02)] + SOFTMIN_TWO_OWNERS)
+def test_softmin_vs_oracle(gpu, oracle, B, N, M, eps):
+    from fpsg_amd.metrics import softmin
+    x, y, h = _softmin_inputs(B, N, M)
     got = softmin(torch.from_numpy(x).to(gpu), torch.from_numpy(y).to(gpu), torch.from_numpy(h).to(gpu), eps)
     exp = oracle.softmin(x, y, h, eps)
     # values are eps * O(10): compare on the scale of eps (v_exp_f32/v_log_f32 vs libm)
     np.testing.assert_allclose(got.cpu().numpy(), exp, rtol=2e-5, atol=2e-4 * eps * 10)
+
+
+@pytest.mark.parametrize("B,N,M,eps", SOFTMIN_TWO_OWNERS)
+def test_softmin_two_owners_per_lane_equals_one_bit_for_bit(gpu, B, N, M, eps):
+    """sinkhorn.hip: "identical results: an owner's sum is split over the waves the same way".  The whole batch takes
+    softmin_kernel<2>, its first 8 clouds alone take softmin_kernel<1>."""
+    from fpsg_amd.metrics import softmin
+    assert -(-N // 128) * B >= 4 * 256 > -(-N // 128) * 8
+    x, y, h = (torch.from_numpy(v).to(gpu) for v in _softmin_inputs(B, N, M))
+    whole = softmin(x, y, h, eps)
+    first = softmin(x[:8].contiguous(), y[:8].contiguous(), h[:8].contiguous(), eps)
+    assert torch.equal(whole[:8].contiguous().view(torch.int32), first.view(torch.int32))
 
 
 def test_sinkhorn_divergence(gpu, oracle):
@@ -165,15 +188,41 @@ def _unfused_loop(x, y, blur=0.05, scaling=0.5):
     return (b_x - a_x).mean(dim=1) + (a_y - b_y).mean(dim=1)
 
 
-@pytest.mark.parametrize("B,N,M", [(3, 512, 512), (2, 300, 700), (5, 2048, 2048), (1, 2500, 1000), (2, 1, 9)])
+def _loop_inputs(B, N, M):
+    rng = np.random.default_rng(N * 3 + M)
+    return unit_ball_clouds(rng, B, N), (unit_ball_clouds(rng, B, M) * 0.6 + 0.25).astype(np.float32)
+
+
+@pytest.mark.parametrize("B,N,M", [(3, 512, 512), (2, 300, 700), (5, 2048, 2048), (1, 2500, 1000), (2, 1, 9)]
+                         + LOOP_TWO_OWNERS)
 def test_fused_sinkhorn_loop_equals_unfused(gpu, B, N, M):
     from fpsg_amd.metrics import sinkhorn_divergence
-    rng = np.random.default_rng(N * 3 + M)
-    x = torch.from_numpy(unit_ball_clouds(rng, B, N)).to(gpu)
-    y = torch.from_numpy((unit_ball_clouds(rng, B, M) * 0.6 + 0.25).astype(np.float32)).to(gpu)
+    x, y = (torch.from_numpy(v).to(gpu) for v in _loop_inputs(B, N, M))
     got = sinkhorn_divergence(x, y)
     exp = _unfused_loop(x, y)
     np.testing.assert_allclose(got.cpu().numpy(), exp.cpu().numpy(), rtol=5e-5, atol=1e-7)
+
+
+@pytest.mark.parametrize("B,N,M", LOOP_TWO_OWNERS)
+def test_two_owner_sinkhorn_loop_vs_oracle_and_the_one_owner_form(gpu, oracle, B, N, M):
+    """sinkhorn_step_kernel<2> on ragged, unequal clouds: its first three clouds against the CPU restatement under
+    test_sinkhorn_divergence's bounds, and bit for bit against the same clouds run alone (sinkhorn_step_kernel<1>).
+    The diameter is passed, so the batch, the chunk and the restatement share one epsilon schedule."""
+    from fpsg_amd.metrics import sinkhorn_divergence
+    assert -(-max(N, M) // 128) * 4 * B >= 4 * 256 > -(-max(N, M) // 128) * 4 * 3
+    x, y = _loop_inputs(B, N, M)
+    pts = np.concatenate([x[:3].astype(np.float64).reshape(-1, 3), y[:3].astype(np.float64).reshape(-1, 3)])
+    diameter = float(np.linalg.norm(pts.max(0) - pts.min(0)))      # oracle.sinkhorn_epsilons' own, of the three clouds
+    tx, ty = torch.from_numpy(x).to(gpu), torch.from_numpy(y).to(gpu)
+    whole = sinkhorn_divergence(tx, ty, diameter=diameter)
+    chunk = sinkhorn_divergence(tx[:3].contiguous(), ty[:3].contiguous(), diameter=diameter)
+    assert torch.equal(whole[:3].contiguous().view(torch.int32), chunk.view(torch.int32))
+    exp = oracle.sinkhorn_divergence(x[:3], y[:3])
+    got = whole[:3].cpu().numpy()
+    dev_s = float(np.max(np.abs(got - exp) / np.abs(exp)))
+    print(f"sinkhorn_divergence B={B} N={N} M={M}: deviation {dev_s:.3e} (test_sinkhorn_divergence records 8.3e-8)")
+    np.testing.assert_allclose(got, exp, rtol=1e-5)
+    assert dev_s <= 10 * 8.3e-8, dev_s
 
 
 def test_sinkhorn_vs_independent_float64(gpu):

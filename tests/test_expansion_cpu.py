@@ -209,7 +209,7 @@ def test_value_clouds_have_minimal_trees_and_stay_clear_of_the_threshold(P):
     the kernel's penalised mask exactly.  A condition on the inputs, not a tolerance: the seeds in ``_expansion_ref.py``
     were chosen until it held.  The sheet cloud has a penalised edge in every patch."""
     x = ref.value_clouds(P)
-    K = 16 if P <= 128 else 4
+    K = ref.value_patches(P)
     assert tuple(x.shape) == (4, K * P, 3) and x.dtype == torch.float32
     par, d2, order = ref.prim(x, P)
     ref.check_tree(par, order, P)

@@ -61,9 +61,11 @@ def _in_range(parent, P):
 
 # ---- 1. the trees, bit for bit -----------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("P,K", [(P, K) for P in (2, 3, 63, 64, 65, 128, 129) for K in (1, 3)] + [(1024, 2)])
+@pytest.mark.parametrize("P,K", [(P, K) for P in (2, 3, 63, 64, 65, 128, 129) for K in (1, 3)] + [(1024, 2)]
+                         + [(P, 3) for P in (256, 257, 512, 513)])
 def test_trees_equal_the_float64_prim_on_exact_distances(gpu, P, K):
-    """63 / 64 / 65 and 128 / 129 cross the vertices-per-lane steps; at 1024 the three clouds run one at a time (B = 1)."""
+    """63 / 64 / 65, 128 / 129, 256 / 257 and 512 / 513 cross the vertices-per-lane steps; at 1024 the three clouds run one
+    at a time (B = 1)."""
     N = K * P
     p = _grid_clouds(N, 100 * P + K)
     batches = [p] if P < 1024 else [p[i:i + 1] for i in range(3)]
@@ -131,7 +133,7 @@ def test_value_and_gradient_against_float64(gpu, P, lam):
 
 # ---- 3. corners, exact ---------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("P", [2, 64, 100, 128, 1024])
+@pytest.mark.parametrize("P", [2, 64, 100, 128, 512, 1024])
 def test_every_point_identical(gpu, P):
     K = 2
     p = torch.tensor([0.3, -0.2, 0.7], device=gpu).expand(2, K * P, 3).contiguous()

@@ -13,6 +13,8 @@ from conftest import unit_ball_clouds
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 2048, 2048), (37, 2048, 512), (5, 15000, 2048), (3, 16384, 64), (64, 100, 100), (2, 1, 1), (4, 777, 333)]
+EDGE_SHAPES = ([(3, N, N) for N in (2, 63, 64)] + [(3, N, 64) for N in (65, 257, 1025, 2049, 4096)]
+               + [(3, N, 32) for N in (4097, 8192, 8193)])
 
 
 def _ball(B, N, seed):
@@ -44,6 +46,12 @@ def _cases():
         out.append((f"tanh-{B}-{N}-{n}", _tanh(B, N, 200 + N + B), n))
     out.append(("lattice", _lattice(), 2048))
     out.append(("repeated", _repeated(), 64))
+    # every fps_kernel<T, P> at both ends of its range of N (tests/_dispatch.py names these cases)
+    for B, N, n in EDGE_SHAPES:
+        out.append((f"ball-{B}-{N}-{n}", _ball(B, N, 100 + N + B), n))
+        out.append((f"tanh-{B}-{N}-{n}", _tanh(B, N, 200 + N + B), n))
+    out.append(("lattice-64", _lattice(3, 64, 8), 64))          # ties inside <64, 1>; fewer than 64 distinct points
+    out.append(("lattice-4096", _lattice(3, 4096, 9), 520))     # ties inside <1024, 4>; runs past the 512 distinct points
     return out
 
 

@@ -45,7 +45,8 @@ def _random_clouds(B, N, seed):
 
 
 # ---- (a) neighbour lists --------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("B,N,k", [(1, 4, 3), (3, 63, 8), (3, 64, 16), (2, 65, 32), (2, 257, 16), (1, 33, 32)])
+@pytest.mark.parametrize("B,N,k", [(1, 4, 3), (3, 63, 8), (3, 64, 16), (2, 65, 32), (2, 257, 16), (1, 33, 32),
+                                     (2, 70, 9), (2, 70, 17)])       # the first k of pn_select_kernel<16> and <32>
 def test_lists_equal_the_restatement(gpu, B, N, k):
     x = _random_clouds(B, N, 100 + N)
     _, _, idx = _estimate(gpu, x, k)

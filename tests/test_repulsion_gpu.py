@@ -56,8 +56,11 @@ def _run(p, k, h=0.03, up=None):
 
 # ---- 1. the neighbour lists, bit for bit -----------------------------------------------------------------------------
 
-@pytest.mark.parametrize("k", [1, 4, 8])
-@pytest.mark.parametrize("N", ["k+1", 63, 64, 65, 257, 1000])
+OTHER_K = (2, 3, 5, 6, 7)           # repulsion_fwd_kernel<K> / repulsion_bwd_kernel<K> are compiled for every K in 1..8
+
+
+@pytest.mark.parametrize("N,k", [(N, k) for k in (1, 4, 8) for N in ("k+1", 63, 64, 65, 257, 1000)]
+                         + [(N, k) for k in OTHER_K for N in ("k+1", 65)])
 def test_lists_equal_the_float64_full_sort_on_exact_distances(gpu, N, k):
     N = k + 1 if N == "k+1" else N
     p, half = _grid_clouds(N, 100 * k + N, gpu)
@@ -109,8 +112,7 @@ def _check_lists_valid_in_float64(p, idx, d2_32):
     assert bool((member[:, :, -1] <= (1 + 1e-5) * rest).all())
 
 
-@pytest.mark.parametrize("k", [1, 4, 8])
-@pytest.mark.parametrize("N", [65, 300, 2048])
+@pytest.mark.parametrize("N,k", [(N, k) for k in (1, 4, 8) for N in (65, 300, 2048)] + [(65, k) for k in OTHER_K])
 def test_value_and_gradient_against_float64(gpu, N, k):
     """Two unit-ball clouds and one tanh(randn) cloud (the decoder's range), h = 0.03 and 0.3.  The reference gets the
     KERNEL's lists, so a near-tie ordered differently in fp32 excludes no row.  Prints the measured deviations

@@ -25,6 +25,10 @@ def _apart(seed):
     return (0.2 * x).contiguous(), (0.2 * y + torch.tensor([1.5, 0.0, 0.0])).contiguous()
 
 
+# ceil(max(N, M) / 128) * 4 * B >= 4 * 256: sinkhorn_step_kernel<2> / sinkhorn_grad_kernel<2> on unequal clouds that fill
+# no group of 128 owners
+TWO_OWNERS_RAGGED = [(256, 100, 37), (256, 70, 129), (300, 1, 9)]
+
 # (id, clouds, diameter)
 PARITY = [
     ("one owner past a wave", lambda: ref.clouds(2, 65, 130, 1), None),
@@ -34,7 +38,8 @@ PARITY = [
     ("two LDS tiles", lambda: ref.clouds(1, 2100, 520, 5), None),
     ("two owners per lane", lambda: ref.clouds(64, 512, 512, 6), FIXED),
     ("clouds 1.5 apart", lambda: _apart(7), None),
-]
+] + [(f"two owners per lane, ragged {B}x{N}x{M}", lambda B=B, N=N, M=M: ref.clouds(B, N, M, 8), FIXED)
+     for B, N, M in TWO_OWNERS_RAGGED]
 
 
 def _loss_and_grads(x, y, gpu, diameter, weights=None):
@@ -61,7 +66,7 @@ def test_gradient_against_float64(gpu, what, make, diameter):
     assert ev <= BOUND, (what, ev)
 
 
-@pytest.mark.parametrize("B,N,M", [(3, 300, 257), (1, 2100, 520), (64, 512, 512)])
+@pytest.mark.parametrize("B,N,M", [(3, 300, 257), (1, 2100, 520), (64, 512, 512)] + TWO_OWNERS_RAGGED)
 def test_value_is_the_forward_entrys_bit_for_bit(gpu, B, N, M):
     from fpsg_amd.metrics import sinkhorn_divergence, sinkhorn_loss
     x, y = (t.to(gpu) for t in ref.clouds(B, N, M, 11))
@@ -75,6 +80,18 @@ def test_value_is_the_forward_entrys_bit_for_bit(gpu, B, N, M):
     assert torch.equal(sinkhorn_loss(x, y), sinkhorn_divergence(x, y))
     plain = sinkhorn_divergence(x.clone().requires_grad_(), y.clone().requires_grad_())
     assert plain.grad_fn is None and not plain.requires_grad
+
+
+@pytest.mark.parametrize("B,N,M", TWO_OWNERS_RAGGED)
+def test_two_owners_per_lane_equal_one_owner_bit_for_bit(gpu, B, N, M):
+    """The whole batch takes sinkhorn_step_kernel<2> and sinkhorn_grad_kernel<2>, its first three clouds alone take the
+    <1> forms; with a fixed diameter both calls share one epsilon schedule, and an owner's sums are split the same way."""
+    assert -(-max(N, M) // 128) * 4 * B >= 4 * 256 > -(-max(N, M) // 128) * 4 * 3
+    x, y = ref.clouds(B, N, M, 8)
+    out, gx, gy = _loss_and_grads(x, y, gpu, FIXED)
+    out3, gx3, gy3 = _loss_and_grads(x[:3].contiguous(), y[:3].contiguous(), gpu, FIXED)
+    for whole, chunk in ((out, out3), (gx, gx3), (gy, gy3)):
+        assert torch.equal(whole[:3].contiguous().view(torch.int32), chunk.view(torch.int32))
 
 
 def test_autograd_plumbing(gpu):

@@ -15,6 +15,9 @@ pytestmark = pytest.mark.gpu
 
 B = 3
 SIZES = (1, 2, 3, 64, 65, 100, 257, 2048)     # one point; below / at / past a wave; no power of two; the largest
+# both ends of every swd_kernel<P> the sizes above leave out or reach at one size only: <128> (65..128), <256>
+# (129..256, never reached above), <512> (257..512) and <1024> (513..1024, never reached above)
+SIZES += (128, 129, 256, 512, 513, 1024)
 GROUP = 8                                     # directions per workgroup: L = 8 is one group, L = 9 two
 N_DIRS = (1, 3, GROUP, GROUP + 1, 128)
 

@@ -232,6 +232,17 @@ def test_value_and_gradient_against_float64(gpu, kind, N, explicit):
     ((0.05, 0.1)), upstream gradient (1, 0.5) and (2): the issue's three clouds, each kind under the percentages that
     populate its balls; at N = 65 three explicit seeds and (0.2, 0.4, 0.8).  The reference gets the KERNEL's lists, so a
     near-tie decided differently in fp32 excludes nothing.  Prints the measured deviations (*Measured*)."""
+    _value_and_gradient_against_float64(gpu, kind, N, explicit, None)
+
+
+@pytest.mark.parametrize("cap", [64, 128, 256])
+def test_value_and_gradient_against_float64_at_every_cap(gpu, cap):
+    """The same comparison with the cap given, so that each ``uniform_fwd_kernel<V>`` (one, two and four members a lane:
+    tests/_dispatch.py) is held to the float64 value and gradient, not only to its lists."""
+    _value_and_gradient_against_float64(gpu, "sphere", 300, None, cap)
+
+
+def _value_and_gradient_against_float64(gpu, kind, N, explicit, cap):
     if kind == "sphere":
         p, up = _sphere(2, N, 7 * N, gpu), torch.tensor([1.0, 0.5], device=gpu)
         percent = tuple(4 * q for q in DEFAULT)
@@ -242,7 +253,7 @@ def test_value_and_gradient_against_float64(gpu, kind, N, explicit):
     if explicit is not None:
         seeds = torch.tensor([explicit] * p.size(0), device=gpu)
         percent = (0.2, 0.4, 0.8)
-    val, info, grad = _run(p, percent, 1.0, seeds, None, up)
+    val, info, grad = _run(p, percent, 1.0, seeds, cap, up)
     count64 = ref.ball_counts(p, info["seeds"], percent, 1.0)
     populated = int((count64 >= 2).sum())
     print(f"uniform {kind} N={N}: {count64.numel() - populated} of {count64.numel()} balls with c < 2, median c "

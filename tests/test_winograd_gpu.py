@@ -190,13 +190,27 @@ def test_full_size_layers_against_the_library_and_linearity(gpu, layer):
     ya.backward(g); yb.backward(g)
     assert float((xa.grad - xb.grad).abs().max()) <= 6e-5 * float(xb.grad.abs().max())
     assert float((wa.grad - wb.grad).abs().max()) <= 1e-4 * float(wb.grad.abs().max())
+    # against float64 on the CPU, on slices that keep it to milliseconds: image 0 / output channel 0 of y, image 0 /
+    # input channel 0 of dx, and the 3 x 3 filter (0, 0) of dw.  The first layers are the only shapes that reach the
+    # streaming-store forms of the transforms (36 C Ps floats beyond 300 MiB: tests/_dispatch.py).  Bounds: this
+    # file's yardstick (test_forward_and_gradients_match_conv2d), 4e-5 of the slice's scale for m = 4, 1e-4 for dw.
+    w64 = w.double().cpu()
+    y64 = F.conv2d(x1[:1].double().cpu(), w64[:1], None, 1, 1)
+    dx64 = F.conv2d(g[:1].double().cpu(), w64[:, :1].flip(2, 3).transpose(0, 1), None, 1, 1)
+    dw64 = F.conv2d(x1[:, :1].double().cpu().transpose(0, 1), g[:, :1].double().cpu().transpose(0, 1), None, 1, 1)
+    e_y, e_dx = _errs(ya.detach()[:1, :1], y64), _errs(xa.grad[:1, :1], dx64)
+    e_dw = _errs(wa.grad[:1, :1], dw64)
+    print(f"full-size layer {layer} vs float64 slices: y {e_y:.3e}, dx {e_dx:.3e}, dw {e_dw:.3e}")
+    assert e_y <= 4e-5 and e_dx <= 4e-5 and e_dw <= 1e-4, (layer, e_y, e_dx, e_dw)
     with torch.no_grad():
         lhs = wg.conv3x3(1.5 * x1 + x2, w)
         rhs = 1.5 * wg.conv3x3(x1, w) + wg.conv3x3(x2, w)
     assert float((lhs - rhs).abs().max()) <= 6e-5 * float(rhs.abs().max())
 
 
-@pytest.mark.parametrize("C,K,H,N", [(64, 64, 112, 6), (64, 128, 56, 6), (128, 128, 56, 6), (256, 256, 28, 24), (128, 256, 14, 90)])
+# (128, 128, 10, 200): planes too small for F(4x4), so the activated input transform of F(2x2) (tests/_dispatch.py)
+@pytest.mark.parametrize("C,K,H,N", [(64, 64, 112, 6), (64, 128, 56, 6), (128, 128, 56, 6), (256, 256, 28, 24), (128, 256, 14, 90),
+                                     (128, 128, 10, 200)])
 @pytest.mark.parametrize("mode", ["train", "eval"])
 def test_bn_relu_folded_into_next_conv_equals_two_ops(gpu, monkeypatch, C, K, H, N, mode):
     """``bn_relu_conv3x3(y, pre_bias, bn, w)`` -- BatchNorm + ReLU applied by the convolution's own input
