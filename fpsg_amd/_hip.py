@@ -26,6 +26,7 @@ _c_stream = ctypes.c_void_p
 SIGNATURES = {
     "fpsg_version": [],
     "fpsg_last_error": [],
+    "fpsg_stream_threshold_bytes": [],
     "fpsg_chamfer_fwd": [_c_f32p, _c_f32p, _c_int, _c_int, _c_int,
                          _c_f32p, _c_i32p, _c_f32p, _c_i32p, _c_stream],
     "fpsg_chamfer_bwd": [_c_f32p, _c_f32p, _c_i32p, _c_i32p, _c_f32p, _c_f32p,
@@ -271,7 +272,8 @@ SIGNATURES = {
     "fpsg_point_normals_orient": [_c_f32p, _c_f32p, _c_i32p, _c_int, _c_int, _c_int, _c_int, _c_f32p, _c_i32p,
                                   ctypes.c_void_p, ctypes.c_size_t, _c_stream],
 }
-_RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_grad_norm_workspace_bytes": ctypes.c_size_t,
+_RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_stream_threshold_bytes": ctypes.c_size_t,
+             "fpsg_grad_norm_workspace_bytes": ctypes.c_size_t,
 "fpsg_chamfer_workspace_bytes": ctypes.c_size_t,
              "fpsg_sinkhorn_workspace_floats": ctypes.c_size_t,
              "fpsg_sinkhorn_grad_workspace_floats": ctypes.c_size_t,
@@ -299,6 +301,17 @@ class FpsgHipError(RuntimeError):
     pass
 
 
+def bind(path: str) -> ctypes.CDLL:
+    """A handle of the library file at `path` with the signature table applied; every call gives a new handle.  The
+    package itself binds one file, through load(); the tests bind a second build of the same ABI next to it."""
+    lib = ctypes.CDLL(path)
+    for name, argtypes in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = _RESTYPES.get(name, ctypes.c_int)
+    return lib
+
+
 def load() -> ctypes.CDLL:
     """Loads the library once; raises (never falls back) when it is absent."""
     global _lib
@@ -310,12 +323,7 @@ def load() -> ctypes.CDLL:
                         f"{LIB_PATH} not found: build it with `make -C fpsg_amd/csrc` "
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). "
                         "fpsg_amd has no CPU or PyTorch fallback for its HIP ops.")
-                lib = ctypes.CDLL(LIB_PATH)
-                for name, argtypes in SIGNATURES.items():
-                    fn = getattr(lib, name)
-                    fn.argtypes = argtypes
-                    fn.restype = _RESTYPES.get(name, ctypes.c_int)
-                _lib = lib
+                _lib = bind(LIB_PATH)
     return _lib
 
 

@@ -1237,6 +1237,9 @@ int rows_segments(const char* fn, int ld, const int* seg_off, const int* seg_len
 }  // namespace
 }  // namespace fpsg
 
+// the threshold of beyond_cache() as this build was compiled (fpsg_common.h)
+extern "C" size_t fpsg_stream_threshold_bytes(void) { return (size_t)FPSG_NT_BYTES; }
+
 extern "C" size_t fpsg_bn_workspace_floats(int N, int C, int L) {
   if (N <= 0 || C <= 0 || L <= 0) return 0;
   return fpsg::plain_workspace(N, C, L).floats;

@@ -38,6 +38,10 @@ typedef void* fpsg_stream_t;
 
 int         fpsg_version(void);
 const char* fpsg_last_error(void);
+/* The byte size beyond which a pass takes its streaming (non-temporal) kernel form, as this build was compiled:
+ * 300 MiB in libfpsg_hip.so, 0 in the tests' second build libfpsg_hip_stream.so (every pass streams).  A
+ * compile-time constant; it tells a test which build it holds. */
+size_t      fpsg_stream_threshold_bytes(void);
 
 /* ---- K1: Chamfer sided distances ------------------------------------------------
  * Replaces kaolin.metrics.pointcloud.chamfer_distance (Kaolin 0.9.0, its CUDA

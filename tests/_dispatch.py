@@ -18,10 +18,11 @@ not a row, nor is a stage that an entry appends when an optional output is asked
                names ``cond`` reads, or is ``None``.
 
 A row with no case fails ``test_dispatch_cpu.py`` unless it carries ``uncovered``: the technical reason why no test of
-the suite can reach it (the instantiation sits behind the 300 MiB threshold of the streaming / non-temporal stores, or
-no argument of any entry selects it).  ``FILES_WITHOUT_A_CHOICE`` lists the sources whose entries each launch one fixed
-sequence of kernels.  ``profiles/dispatch/kernels.txt`` holds the kernel names of one ``rocprofv3 --kernel-trace
---stats`` run of exactly the cases named here.
+the suite can reach it (no argument of any entry selects it).  The streaming / non-temporal forms behind the 300 MiB
+threshold, ``NT = true``, are reached at small shapes through the second build of the library in which the threshold is
+compiled to 0 (fpsg_amd/csrc/Makefile, tests/test_streaming_forms_gpu.py).  ``FILES_WITHOUT_A_CHOICE`` lists the
+sources whose entries each launch one fixed sequence of kernels.  ``profiles/dispatch/kernels.txt`` holds the kernel
+names of ``rocprofv3 --kernel-trace --stats`` runs of exactly the cases named here (profiles/dispatch/notes.md).
 """
 
 ROWS = [
@@ -1256,8 +1257,7 @@ ROWS = [
         "entry": 'fpsg_wino_input_transform', "file": 'winograd.hip',
         "kernel": 'wino_input_kernel<4, false, true, false, false>',
         "lines": [
-            'else if ((size_t)36 * C * Ps * sizeof(float) > kStreamBytes) hipLaunchKernelGGL((wino_input_kernel<4, false, true>), grid, dim3(kWinoThreads), 0, static_cast<hipStream_t>(stream), x, C, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, V, nullptr, nullptr);',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * C * Ps * sizeof(float))) hipLaunchKernelGGL((wino_input_kernel<4, false, true>), grid, dim3(kWinoThreads), 0, static_cast<hipStream_t>(stream), x, C, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, V, nullptr, nullptr);',
         ],
         "when": 'm = 4 and 36 C Ps floats beyond 300 MiB',
         "cond": '36 * C * 37 * (-(-H // 4)) ** 2 * 4 > 300 << 20',
@@ -1269,8 +1269,7 @@ ROWS = [
         "entry": 'fpsg_wino_output_transform', "file": 'winograd.hip',
         "kernel": 'wino_output_kernel<4, false, false, true, false>',
         "lines": [
-            'else if ((size_t)36 * K * Ps * sizeof(float) > kStreamBytes) hipLaunchKernelGGL((wino_output_kernel<4, false, false, true>), grid, dim3(kWinoThreads), 0, hs, M, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, y, nullptr, nullptr);',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * K * Ps * sizeof(float))) hipLaunchKernelGGL((wino_output_kernel<4, false, false, true>), grid, dim3(kWinoThreads), 0, hs, M, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, y, nullptr, nullptr);',
         ],
         "when": 'm = 4 and 36 K Ps floats beyond 300 MiB',
         "cond": '36 * K * 37 * (-(-H // 4)) ** 2 * 4 > 300 << 20',
@@ -1282,8 +1281,7 @@ ROWS = [
         "entry": 'fpsg_wino_grad_transforms', "file": 'winograd.hip',
         "kernel": 'wino_input_kernel<4, false, true, false, true>',
         "lines": [
-            'else if ((size_t)36 * K * Ps * sizeof(float) > kStreamBytes) hipLaunchKernelGGL((wino_input_kernel<4, false, true, false, true>), grid, dim3(kWinoThreads), 0, hs, dy, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, V, nullptr, nullptr, dM);',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * K * Ps * sizeof(float))) hipLaunchKernelGGL((wino_input_kernel<4, false, true, false, true>), grid, dim3(kWinoThreads), 0, hs, dy, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, V, nullptr, nullptr, dM);',
         ],
         "when": 'm = 4 and 36 K Ps floats beyond 300 MiB',
         "cond": '36 * K * 37 * (-(-H // 4)) ** 2 * 4 > 300 << 20',
@@ -2297,31 +2295,137 @@ ROWS = [
                       'launches these two'),
     },
     {
-        "entry": 'fpsg_bn_act_fwd / fpsg_bn_act_bwd', "file": 'bnact.hip',
-        "kernel": 'bn_reduce_kernel<MODE, ACT, true>',
+        "entry": 'fpsg_bn_act_fwd', "file": 'bnact.hip',
+        "kernel": 'bn_reduce_kernel<0, 0, true>',
         "lines": [
             'if (act == kActRelu) FPSG_RED(kActRelu, true); else if (act == kActLeaky) FPSG_RED(kActLeaky, true); else FPSG_RED(kActNone, true);',
             'if (beyond_cache((size_t)N * C * L * sizeof(float))) {',
         ],
-        "when": 'N * C * L floats beyond 300 MiB',
+        "when": 'N * C * L floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[relu-37x16x56x56-train]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[leaky-5x9x8196-train]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[none-24x32x2048-train]', None),
+        ],
     },
     {
-        "entry": 'fpsg_bn_act_fwd / fpsg_bn_act_bwd / fpsg_bn_act_bwd_parts', "file": 'bnact.hip',
-        "kernel": 'bn_apply_kernel<MODE, ACT, true>',
+        "entry": 'fpsg_bn_act_bwd', "file": 'bnact.hip',
+        "kernel": 'bn_reduce_kernel<1, 1, true>',
+        "lines": [
+            'if (act == kActRelu) FPSG_RED(kActRelu, true); else if (act == kActLeaky) FPSG_RED(kActLeaky, true); else FPSG_RED(kActNone, true);',
+            'if (beyond_cache((size_t)N * C * L * sizeof(float))) {',
+        ],
+        "when": 'N * C * L floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
+        "cond": None,
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[relu-37x16x56x56-train]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[relu-37x16x56x56-eval]', None),
+        ],
+    },
+    {
+        "entry": 'fpsg_bn_act_bwd', "file": 'bnact.hip',
+        "kernel": 'bn_reduce_kernel<1, 2, true>',
+        "lines": [
+            'if (act == kActRelu) FPSG_RED(kActRelu, true); else if (act == kActLeaky) FPSG_RED(kActLeaky, true); else FPSG_RED(kActNone, true);',
+            'if (beyond_cache((size_t)N * C * L * sizeof(float))) {',
+        ],
+        "when": 'N * C * L floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
+        "cond": None,
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[leaky-5x9x8196-train]', None),
+        ],
+    },
+    {
+        "entry": 'fpsg_bn_act_bwd', "file": 'bnact.hip',
+        "kernel": 'bn_reduce_kernel<1, 0, true>',
+        "lines": [
+            'if (act == kActRelu) FPSG_RED(kActRelu, true); else if (act == kActLeaky) FPSG_RED(kActLeaky, true); else FPSG_RED(kActNone, true);',
+            'if (beyond_cache((size_t)N * C * L * sizeof(float))) {',
+        ],
+        "when": 'N * C * L floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
+        "cond": None,
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[none-24x32x2048-train]', None),
+        ],
+    },
+    {
+        "entry": 'fpsg_bn_act_fwd', "file": 'bnact.hip',
+        "kernel": 'bn_apply_kernel<0, 1, true>',
         "lines": [
             'if (act == kActRelu) FPSG_APP(kActRelu, true); else if (act == kActLeaky) FPSG_APP(kActLeaky, true); else FPSG_APP(kActNone, true);',
         ],
-        "when": 'N * C * L floats beyond 300 MiB',
+        "when": 'N * C * L floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[relu-37x16x56x56-train]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[relu-37x16x56x56-eval]', None),
+        ],
+    },
+    {
+        "entry": 'fpsg_bn_act_fwd', "file": 'bnact.hip',
+        "kernel": 'bn_apply_kernel<0, 2, true>',
+        "lines": [
+            'if (act == kActRelu) FPSG_APP(kActRelu, true); else if (act == kActLeaky) FPSG_APP(kActLeaky, true); else FPSG_APP(kActNone, true);',
+        ],
+        "when": 'N * C * L floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
+        "cond": None,
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[leaky-5x9x8196-train]', None),
+        ],
+    },
+    {
+        "entry": 'fpsg_bn_act_fwd', "file": 'bnact.hip',
+        "kernel": 'bn_apply_kernel<0, 0, true>',
+        "lines": [
+            'if (act == kActRelu) FPSG_APP(kActRelu, true); else if (act == kActLeaky) FPSG_APP(kActLeaky, true); else FPSG_APP(kActNone, true);',
+        ],
+        "when": 'N * C * L floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
+        "cond": None,
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[none-24x32x2048-train]', None),
+        ],
+    },
+    {
+        "entry": 'fpsg_bn_act_bwd / fpsg_bn_act_bwd_parts', "file": 'bnact.hip',
+        "kernel": 'bn_apply_kernel<1, 1, true>',
+        "lines": [
+            'if (act == kActRelu) FPSG_APP(kActRelu, true); else if (act == kActLeaky) FPSG_APP(kActLeaky, true); else FPSG_APP(kActNone, true);',
+        ],
+        "when": 'N * C * L floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
+        "cond": None,
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[relu-37x16x56x56-train]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[relu-37x16x56x56-eval]', None),
+            ('tests/test_streaming_forms_gpu.py::test_memory_contract_of_the_streaming_forms[bn_act_bwd_parts-sliced-vec-seg+4]', None),
+            ('tests/test_streaming_forms_gpu.py::test_memory_contract_of_the_streaming_forms[bn_act_bwd_parts-sliced-vec-batch3]', None),
+        ],
+    },
+    {
+        "entry": 'fpsg_bn_act_bwd / fpsg_bn_act_bwd_parts', "file": 'bnact.hip',
+        "kernel": 'bn_apply_kernel<1, 2, true>',
+        "lines": [
+            'if (act == kActRelu) FPSG_APP(kActRelu, true); else if (act == kActLeaky) FPSG_APP(kActLeaky, true); else FPSG_APP(kActNone, true);',
+        ],
+        "when": 'N * C * L floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
+        "cond": None,
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[leaky-5x9x8196-train]', None),
+            ('tests/test_streaming_forms_gpu.py::test_memory_contract_of_the_streaming_forms[bn_act_bwd_parts-sliced-vec-leaky]', None),
+        ],
+    },
+    {
+        "entry": 'fpsg_bn_act_bwd / fpsg_bn_act_bwd_parts', "file": 'bnact.hip',
+        "kernel": 'bn_apply_kernel<1, 0, true>',
+        "lines": [
+            'if (act == kActRelu) FPSG_APP(kActRelu, true); else if (act == kActLeaky) FPSG_APP(kActLeaky, true); else FPSG_APP(kActNone, true);',
+        ],
+        "when": 'N * C * L floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
+        "cond": None,
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_reduce_and_apply[none-24x32x2048-train]', None),
+            ('tests/test_streaming_forms_gpu.py::test_memory_contract_of_the_streaming_forms[bn_act_bwd_parts-sliced-vec-none]', None),
+        ],
     },
     {
         "entry": 'fpsg_bn_act_max_fwd', "file": 'bnact.hip',
@@ -2356,12 +2460,12 @@ ROWS = [
         "lines": [
             'else if (beyond_cache((size_t)N * C * L * sizeof(float))) hipLaunchKernelGGL((bn_reduce_ext_kernel<1, true>), grid, dim3(kBnThreads), 0, s, x, pre_bias, N, C, L, S, ws, ext);',
         ],
-        "when": 'training, N * C * L floats beyond 300 MiB',
+        "when": 'training, N * C * L floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_max_forward_and_backward[leaky-3x16x4736]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_max_forward_and_backward[relu-6x128x2048]', None),
+        ],
     },
     {
         "entry": 'fpsg_bn_act_max_fwd', "file": 'bnact.hip',
@@ -2468,12 +2572,12 @@ ROWS = [
         "lines": [
             'hipLaunchKernelGGL(beyond_cache((size_t)N * C * L * sizeof(float)) ? bn_max_apply_kernel<true> : bn_max_apply_kernel<false>,',
         ],
-        "when": 'N * C * L floats beyond 300 MiB',
+        "when": 'N * C * L floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_max_forward_and_backward[leaky-3x16x4736]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_max_forward_and_backward[relu-6x128x2048]', None),
+        ],
     },
     {
         "entry": 'fpsg_bn_act_pool_fwd', "file": 'bnact.hip',
@@ -2740,17 +2844,32 @@ ROWS = [
         ],
     },
     {
-        "entry": 'fpsg_bn_act_pool_fwd / fpsg_bn_act_pool_bwd', "file": 'bnact.hip',
-        "kernel": 'bn_pool_apply_kernel<MODE, 1, 2, true>',
+        "entry": 'fpsg_bn_act_pool_fwd', "file": 'bnact.hip',
+        "kernel": 'bn_pool_apply_kernel<0, 1, 2, true>',
         "lines": [
             'hipLaunchKernelGGL((bn_pool_apply_kernel<MODE, kActRelu, 2, true>), grid, dim3(kBnThreads), 0, s, x, dyp, chan, coef, pb,',
         ],
-        "when": 'W % 4 == 0, ReLU, N * C * H * W floats beyond 300 MiB',
+        "when": 'W % 4 == 0, ReLU, N * C * H * W floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_pooled_forward_and_backward[37x16x28x28-train]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_pooled_forward_and_backward[37x16x28x28-eval]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_pooled_forward_and_backward[8x64x56x56-train]', None),
+        ],
+    },
+    {
+        "entry": 'fpsg_bn_act_pool_bwd', "file": 'bnact.hip',
+        "kernel": 'bn_pool_apply_kernel<2, 1, 2, true>',
+        "lines": [
+            'hipLaunchKernelGGL((bn_pool_apply_kernel<MODE, kActRelu, 2, true>), grid, dim3(kBnThreads), 0, s, x, dyp, chan, coef, pb,',
+        ],
+        "when": 'W % 4 == 0, ReLU, N * C * H * W floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
+        "cond": None,
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_pooled_forward_and_backward[37x16x28x28-train]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_pooled_forward_and_backward[37x16x28x28-eval]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_pooled_forward_and_backward[8x64x56x56-train]', None),
+        ],
     },
     {
         "entry": 'fpsg_bn_act_pool_bwd', "file": 'bnact.hip',
@@ -2758,12 +2877,13 @@ ROWS = [
         "lines": [
             'hipLaunchKernelGGL((bn_pool_reduce_kernel<kActRelu, 2, true>), grid, dim3(kBnThreads), 0, s, x, dyp, chan, pb, N, C, H, W,',
         ],
-        "when": 'W % 4 == 0, ReLU, N * C * H * W floats beyond 300 MiB',
+        "when": 'W % 4 == 0, ReLU, N * C * H * W floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_bn_pooled_forward_and_backward[37x16x28x28-train]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_pooled_forward_and_backward[37x16x28x28-eval]', None),
+            ('tests/test_streaming_forms_gpu.py::test_bn_pooled_forward_and_backward[8x64x56x56-train]', None),
+        ],
     },
     # ---- winograd_fused.hip --------------------------------------------------------------------------------------
     {
@@ -2843,12 +2963,13 @@ ROWS = [
             ': (parts ? wino4_fused_c64_kernel<false, true, true> : wino4_fused_c64_kernel<false, false, true>))',
             'const bool nt = beyond_cache((size_t)N * K * H * W * sizeof(float));',
         ],
-        "when": 'statistics, no activation, y beyond 300 MiB',
+        "when": 'statistics, no activation, y beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_fused_winograd_convolution[plain-2x64x128x28x36]', None),
+            ('tests/test_streaming_forms_gpu.py::test_fused_winograd_convolution[plain-1x64x16x4x4]', None),
+            ('tests/test_streaming_forms_gpu.py::test_fused_winograd_convolution[plain-37x64x32x56x56]', None),
+        ],
     },
     {
         "entry": 'fpsg_wino_conv_fused_act', "file": 'winograd_fused.hip',
@@ -2857,12 +2978,13 @@ ROWS = [
             'nt ? (chan ? (parts ? wino4_fused_c64_kernel<true, true, true> : wino4_fused_c64_kernel<true, false, true>)',
             'const bool nt = beyond_cache((size_t)N * K * H * W * sizeof(float));',
         ],
-        "when": 'activated input, no statistics, y beyond 300 MiB',
+        "when": 'activated input, no statistics, y beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_fused_winograd_convolution[activated-2x64x128x28x36]', None),
+            ('tests/test_streaming_forms_gpu.py::test_fused_winograd_convolution[activated-1x64x16x4x4]', None),
+            ('tests/test_streaming_forms_gpu.py::test_fused_winograd_convolution[activated-37x64x32x56x56]', None),
+        ],
     },
     {
         "entry": 'fpsg_wino_conv_fused_stats', "file": 'winograd_fused.hip',
@@ -2871,12 +2993,13 @@ ROWS = [
             'nt ? (chan ? (parts ? wino4_fused_c64_kernel<true, true, true> : wino4_fused_c64_kernel<true, false, true>)',
             'const bool nt = beyond_cache((size_t)N * K * H * W * sizeof(float));',
         ],
-        "when": 'activated input and statistics, y beyond 300 MiB',
+        "when": 'activated input and statistics, y beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_fused_winograd_convolution[activated-2x64x128x28x36]', None),
+            ('tests/test_streaming_forms_gpu.py::test_fused_winograd_convolution[activated-1x64x16x4x4]', None),
+            ('tests/test_streaming_forms_gpu.py::test_fused_winograd_convolution[activated-37x64x32x56x56]', None),
+        ],
     },
     # ---- winograd_dw.hip -----------------------------------------------------------------------------------------
     {
@@ -2939,7 +3062,7 @@ ROWS = [
         "lines": [
             'else hipLaunchKernelGGL((wino_input_kernel<4, false>), grid, dim3(kWinoThreads), 0, static_cast<hipStream_t>(stream), x, C, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, V, nullptr, nullptr);',
             'inline bool ragged(int m, int H, int W) { return m == 4 && ((H | W) & 3) != 0; }',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * C * Ps * sizeof(float))) hipLaunchKernelGGL((wino_input_kernel<4, false, true>), grid, dim3(kWinoThreads), 0, static_cast<hipStream_t>(stream), x, C, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, V, nullptr, nullptr);',
         ],
         "when": 'm = 4, whole tiles, within 300 MiB',
         "cond": 'm == 4 and (H | W) & 3 == 0',
@@ -2979,15 +3102,13 @@ ROWS = [
         "entry": 'fpsg_wino_input_transform_act', "file": 'winograd.hip',
         "kernel": 'wino_input_kernel<4, true, true, false, false>',
         "lines": [
-            'else if ((size_t)36 * C * Ps * sizeof(float) > kStreamBytes) hipLaunchKernelGGL((wino_input_kernel<4, true, true>), grid, dim3(kWinoThreads), 0, static_cast<hipStream_t>(stream), x, C, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, V, chan, pre_bias);',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * C * Ps * sizeof(float))) hipLaunchKernelGGL((wino_input_kernel<4, true, true>), grid, dim3(kWinoThreads), 0, static_cast<hipStream_t>(stream), x, C, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, V, chan, pre_bias);',
         ],
-        "when": 'm = 4, whole tiles, 36 x channels x Ps floats beyond 300 MiB',
+        "when": 'm = 4, whole tiles, 36 x channels x Ps floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_winograd_activated_input_transform', None),
+        ],
     },
     {
         "entry": 'fpsg_wino_input_transform_act', "file": 'winograd.hip',
@@ -2995,7 +3116,7 @@ ROWS = [
         "lines": [
             'else hipLaunchKernelGGL((wino_input_kernel<4, true>), grid, dim3(kWinoThreads), 0, static_cast<hipStream_t>(stream), x, C, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, V, chan, pre_bias);',
             'inline bool ragged(int m, int H, int W) { return m == 4 && ((H | W) & 3) != 0; }',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * C * Ps * sizeof(float))) hipLaunchKernelGGL((wino_input_kernel<4, true, true>), grid, dim3(kWinoThreads), 0, static_cast<hipStream_t>(stream), x, C, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, V, chan, pre_bias);',
         ],
         "when": 'm = 4, whole tiles, within 300 MiB',
         "cond": 'm == 4 and (H | W) & 3 == 0',
@@ -3039,7 +3160,7 @@ ROWS = [
         "lines": [
             'else hipLaunchKernelGGL((wino_output_kernel<4, false>), grid, dim3(kWinoThreads), 0, hs, M, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, y, nullptr, nullptr);',
             'inline bool ragged(int m, int H, int W) { return m == 4 && ((H | W) & 3) != 0; }',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * K * Ps * sizeof(float))) hipLaunchKernelGGL((wino_output_kernel<4, false, false, true>), grid, dim3(kWinoThreads), 0, hs, M, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, y, nullptr, nullptr);',
         ],
         "when": 'm = 4, whole tiles, within 300 MiB',
         "cond": 'm == 4 and (H | W) & 3 == 0',
@@ -3080,15 +3201,14 @@ ROWS = [
         "entry": 'fpsg_wino_output_transform_stats', "file": 'winograd.hip',
         "kernel": 'wino_output_kernel<4, true, false, true, false>',
         "lines": [
-            'else if ((size_t)36 * K * Ps * sizeof(float) > kStreamBytes) hipLaunchKernelGGL((wino_output_kernel<4, true, false, true>), grid, dim3(kWinoThreads), 0, hs, M, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, y, bias, parts);',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * K * Ps * sizeof(float))) hipLaunchKernelGGL((wino_output_kernel<4, true, false, true>), grid, dim3(kWinoThreads), 0, hs, M, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, y, bias, parts);',
         ],
-        "when": 'm = 4, whole tiles, 36 x channels x Ps floats beyond 300 MiB',
+        "when": 'm = 4, whole tiles, 36 x channels x Ps floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_winograd_output_transform_with_statistics[37x32x28x28]', None),
+            ('tests/test_streaming_forms_gpu.py::test_winograd_output_transform_with_statistics[3x8x12x20]', None),
+        ],
     },
     {
         "entry": 'fpsg_wino_output_transform_stats', "file": 'winograd.hip',
@@ -3096,7 +3216,7 @@ ROWS = [
         "lines": [
             'else hipLaunchKernelGGL((wino_output_kernel<4, true>), grid, dim3(kWinoThreads), 0, hs, M, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, y, bias, parts);',
             'inline bool ragged(int m, int H, int W) { return m == 4 && ((H | W) & 3) != 0; }',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * K * Ps * sizeof(float))) hipLaunchKernelGGL((wino_output_kernel<4, true, false, true>), grid, dim3(kWinoThreads), 0, hs, M, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, y, bias, parts);',
         ],
         "when": 'm = 4, whole tiles, within 300 MiB',
         "cond": 'm == 4 and (H | W) & 3 == 0',
@@ -3136,15 +3256,14 @@ ROWS = [
         "entry": 'fpsg_wino_output_transform_bwd_stats', "file": 'winograd.hip',
         "kernel": 'wino_output_kernel<4, true, true, true, false>',
         "lines": [
-            'else if ((size_t)36 * K * Ps * sizeof(float) > kStreamBytes) hipLaunchKernelGGL((wino_output_kernel<4, true, true, true>), grid, dim3(kWinoThreads), 0, hs, M, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, y, pre_bias, parts, xpre, chan);',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * K * Ps * sizeof(float))) hipLaunchKernelGGL((wino_output_kernel<4, true, true, true>), grid, dim3(kWinoThreads), 0, hs, M, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, y, pre_bias, parts, xpre, chan);',
         ],
-        "when": 'm = 4, whole tiles, 36 x channels x Ps floats beyond 300 MiB',
+        "when": 'm = 4, whole tiles, 36 x channels x Ps floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_winograd_output_transform_with_backward_sums[37x32x28x28]', None),
+            ('tests/test_streaming_forms_gpu.py::test_winograd_output_transform_with_backward_sums[3x7x8x12]', None),
+        ],
     },
     {
         "entry": 'fpsg_wino_output_transform_bwd_stats', "file": 'winograd.hip',
@@ -3152,7 +3271,7 @@ ROWS = [
         "lines": [
             'else hipLaunchKernelGGL((wino_output_kernel<4, true, true>), grid, dim3(kWinoThreads), 0, hs, M, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, y, pre_bias, parts, xpre, chan);',
             'inline bool ragged(int m, int H, int W) { return m == 4 && ((H | W) & 3) != 0; }',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * K * Ps * sizeof(float))) hipLaunchKernelGGL((wino_output_kernel<4, true, true, true>), grid, dim3(kWinoThreads), 0, hs, M, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, y, pre_bias, parts, xpre, chan);',
         ],
         "when": 'm = 4, whole tiles, within 300 MiB',
         "cond": 'm == 4 and (H | W) & 3 == 0',
@@ -3192,15 +3311,14 @@ ROWS = [
         "entry": 'fpsg_wino_grad_output_transform', "file": 'winograd.hip',
         "kernel": 'wino_grad_output_kernel<4, true, false>',
         "lines": [
-            'else if ((size_t)36 * K * Ps * sizeof(float) > kStreamBytes) hipLaunchKernelGGL((wino_grad_output_kernel<4, true>), grid, dim3(kWinoThreads), 0, hs, dy, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, dM);',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * K * Ps * sizeof(float))) hipLaunchKernelGGL((wino_grad_output_kernel<4, true>), grid, dim3(kWinoThreads), 0, hs, dy, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, dM);',
         ],
-        "when": 'm = 4, whole tiles, 36 x channels x Ps floats beyond 300 MiB',
+        "when": 'm = 4, whole tiles, 36 x channels x Ps floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_winograd_gradient_transforms[37x40x28x28]', None),
+            ('tests/test_streaming_forms_gpu.py::test_winograd_gradient_transforms[1x3x4x4]', None),
+        ],
     },
     {
         "entry": 'fpsg_wino_grad_output_transform', "file": 'winograd.hip',
@@ -3208,7 +3326,7 @@ ROWS = [
         "lines": [
             'else hipLaunchKernelGGL((wino_grad_output_kernel<4>), grid, dim3(kWinoThreads), 0, hs, dy, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, dM);',
             'inline bool ragged(int m, int H, int W) { return m == 4 && ((H | W) & 3) != 0; }',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * K * Ps * sizeof(float))) hipLaunchKernelGGL((wino_grad_output_kernel<4, true>), grid, dim3(kWinoThreads), 0, hs, dy, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, dM);',
         ],
         "when": 'm = 4, whole tiles, within 300 MiB',
         "cond": 'm == 4 and (H | W) & 3 == 0',
@@ -3254,7 +3372,7 @@ ROWS = [
         "lines": [
             'else hipLaunchKernelGGL((wino_input_kernel<4, false, false, false, true>), grid, dim3(kWinoThreads), 0, hs, dy, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, V, nullptr, nullptr, dM);',
             'inline bool ragged(int m, int H, int W) { return m == 4 && ((H | W) & 3) != 0; }',
-            'constexpr size_t kStreamBytes = (size_t)300 << 20;',
+            'else if (beyond_cache((size_t)36 * K * Ps * sizeof(float))) hipLaunchKernelGGL((wino_input_kernel<4, false, true, false, true>), grid, dim3(kWinoThreads), 0, hs, dy, K, H, W, tiles_of(H, m), tiles_of(W, m), P, Ps, V, nullptr, nullptr, dM);',
         ],
         "when": 'm = 4, whole tiles, within 300 MiB',
         "cond": 'm == 4 and (H | W) & 3 == 0',
@@ -4192,12 +4310,12 @@ ROWS = [
             'if (parts && nt)',
             'const bool nt = beyond_cache((size_t)N * 64 * H * W * sizeof(float));      // y: 475 MB at 37 images, written once',
         ],
-        "when": 'parts given; y beyond 300 MiB',
+        "when": 'parts given; y beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_first_layer_forward[3x30x36]', None),
+            ('tests/test_streaming_forms_gpu.py::test_first_layer_forward[37x56x100]', None),
+        ],
     },
     {
         "entry": 'fpsg_conv_first_fwd', "file": 'conv_first.hip',
@@ -4207,12 +4325,12 @@ ROWS = [
             'else if (nt)',
             'const bool nt = beyond_cache((size_t)N * 64 * H * W * sizeof(float));      // y: 475 MB at 37 images, written once',
         ],
-        "when": 'no parts; y beyond 300 MiB',
+        "when": 'no parts; y beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_first_layer_forward[3x30x36]', None),
+            ('tests/test_streaming_forms_gpu.py::test_first_layer_forward[37x56x100]', None),
+        ],
     },
     # ---- decoder.hip ---------------------------------------------------------------------------------------------
     {
@@ -4235,12 +4353,15 @@ ROWS = [
         "lines": [
             'auto kern = beyond_cache((size_t)G * D * B * P * sizeof(float)) ? dec1_fwd_kernel<true> : dec1_fwd_kernel<false>;',
         ],
-        "when": 'G * D * B * P floats beyond 300 MiB',
+        "when": 'G * D * B * P floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_decoder_first_layer[g2d70b7p32-train-0]', None),
+            ('tests/test_streaming_forms_gpu.py::test_decoder_first_layer[g1d33b3p128-eval-1]', None),
+            ('tests/test_streaming_forms_gpu.py::test_decoder_first_layer[g2d40b130p4-train-1]', None),
+            ('tests/test_streaming_forms_gpu.py::test_decoder_first_layer[g1d96b16p128-train-2]', None),
+            ('tests/test_streaming_forms_gpu.py::test_decoder_first_layer[g2d70b7p32-train-accumulate-0]', None),
+        ],
     },
     {
         "entry": 'fpsg_dec1_bwd_ld', "file": 'decoder.hip',
@@ -4262,12 +4383,15 @@ ROWS = [
         "lines": [
             'auto kern = beyond_cache((size_t)G * D * B * P * sizeof(float)) ? dec1_bwd_kernel<true> : dec1_bwd_kernel<false>;',
         ],
-        "when": 'G * D * B * P floats beyond 300 MiB',
+        "when": 'G * D * B * P floats beyond 300 MiB; reached at small shapes in the zero-threshold build of the tests (build/libfpsg_hip_stream.so)',
         "cond": None,
-        "cases": [],
-        "uncovered": ('behind the byte threshold (the tensor beyond 300 MiB): no small shape reaches it, a '
-                      'full-size case is ruled out for the suite, and no kernel-level test with a reference runs '
-                      'this form at full size'),
+        "cases": [
+            ('tests/test_streaming_forms_gpu.py::test_decoder_first_layer[g2d70b7p32-train-0]', None),
+            ('tests/test_streaming_forms_gpu.py::test_decoder_first_layer[g1d33b3p128-eval-1]', None),
+            ('tests/test_streaming_forms_gpu.py::test_decoder_first_layer[g2d40b130p4-train-1]', None),
+            ('tests/test_streaming_forms_gpu.py::test_decoder_first_layer[g1d96b16p128-train-2]', None),
+            ('tests/test_streaming_forms_gpu.py::test_decoder_first_layer[g2d70b7p32-train-accumulate-0]', None),
+        ],
     },
     # ---- mesh_sample.hip -----------------------------------------------------------------------------------------
     {

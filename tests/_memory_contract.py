@@ -430,7 +430,7 @@ def bn_act_bwd_coef(lib, N, C, L):
     return Row(bufs, call, floats)
 
 
-def bn_act_bwd_parts(lib, N, C, L, n_parts=3):
+def bn_act_bwd_parts(lib, N, C, L, n_parts=3, act=1):
     g = _g(6)
     floats = lib.fpsg_bn_workspace_floats(N, C, L)
     bufs = _bn_bwd_in(g, N, C, L) + [inp("parts", _randn(g, C, n_parts, 2)), out("dx", F32, (N, C, L), 16),
@@ -438,8 +438,9 @@ def bn_act_bwd_parts(lib, N, C, L, n_parts=3):
                                      out("coef", F32, (3, C)), _W(floats, 4, 4)]
 
     def call(p, s, wsn):
-        return lib.fpsg_bn_act_bwd_parts(p["x"], p["pre_bias"], p["dy"], p["chan"], N, C, L, 1, 1, _f(0.0), p["dx"],
-                                         p["dgamma"], p["dbeta"], p["dpre_bias"], p["coef"], p["ws"], p["parts"], n_parts, s)
+        return lib.fpsg_bn_act_bwd_parts(p["x"], p["pre_bias"], p["dy"], p["chan"], N, C, L, 1, act,
+                                         _f(0.2 if act == 2 else 0.0), p["dx"], p["dgamma"], p["dbeta"], p["dpre_bias"],
+                                         p["coef"], p["ws"], p["parts"], n_parts, s)
     return Row(bufs, call, floats)
 
 
@@ -828,6 +829,25 @@ def _cases():
         add("fpsg_bn_act_max_fwd", tag, bn_max_fwd, *shape)
         add("fpsg_bn_act_max_bwd", tag, bn_max_bwd, *shape)
         add("fpsg_bn_act_max_bwd_coef", tag, bn_max_bwd, *shape, coef_only=True)
+    # sliced rows of whole 16-byte vectors (L % 4 == 0): the branch that loads and stores v4f, and the only one whose
+    # accesses carry the non-temporal hint in the streaming forms (tests/test_streaming_forms_gpu.py runs these rows on
+    # the second build); 4100 = a last segment of ONE vector, 5464 = 1366 vectors: a last trip that fills 86 of 256 lanes
+    vec, vec3 = (5, 3, 4100), (3, 2, 5464)
+    for shape, tag in ((vec, "sliced-vec-seg+4"), (vec3, "sliced-vec-batch3")):
+        add("fpsg_bn_act_fwd", tag, bn_act_fwd, *shape, 1)
+        add("fpsg_bn_stats", tag, bn_stats, *shape)
+        add("fpsg_bn_act_bwd", tag, bn_act_bwd, *shape)
+        add("fpsg_bn_act_bwd_coef", tag, bn_act_bwd_coef, *shape)
+        add("fpsg_bn_act_bwd_parts", tag, bn_act_bwd_parts, *shape)
+        add("fpsg_bn_act_max_fwd", tag, bn_max_fwd, *shape)
+        add("fpsg_bn_act_max_bwd", tag, bn_max_bwd, *shape)
+    add("fpsg_bn_act_fwd", "eval-sliced-vec", bn_act_fwd, *vec, 0)
+    add("fpsg_bn_act_bwd_parts", "sliced-vec-leaky", bn_act_bwd_parts, *vec, act=2)
+    add("fpsg_bn_act_bwd_parts", "sliced-vec-none", bn_act_bwd_parts, *vec, act=0)
+    # pooled rows with W % 4 == 0: two windows a lane (16-byte loads, 16-byte dx stores); 68 = 17 vectors a pooled row
+    for shape, tag in (((2, 3, 130, 68), "vec-items+1"), ((3, 2, 6, 12), "vec-batch3")):
+        add("fpsg_bn_act_pool_fwd", tag, bn_pool_fwd, *shape)
+        add("fpsg_bn_act_pool_bwd", tag, bn_pool_bwd, *shape)
     add("fpsg_bn_act_fwd", "eval-one-launch", bn_act_fwd, *small, 0)
     add("fpsg_bn_act_fwd", "eval-sliced", bn_act_fwd, *seg, 0)
     add("fpsg_bn_act_fwd", "chan-given-one-launch", bn_act_fwd, *small, 2)
@@ -930,3 +950,37 @@ def build(case, lib) -> Row:
         inner = row.call
         row.call = lambda p, s, wsn: inner(_Optional(p), s, wsn)
     return row
+
+
+def run_once(row, layout, scale, lib):
+    """One call of the row in `layout` (tests/_guarded.py): it returns 0, the guards and the pure inputs are unchanged;
+    gives the output bits."""
+    p = layout.ptrs()
+    if row.late:
+        for name, data in row.late(p).items():
+            layout.poke(name, data)
+    torch.cuda.synchronize()
+    rc = row.call(p, torch.cuda.current_stream().cuda_stream, row.ws_units * scale)
+    torch.cuda.synchronize()
+    assert rc == 0, f"[{layout.pattern}] returned {rc}: {(lib.fpsg_last_error() or b'').decode()}"
+    layout.check()
+    return layout.outputs()
+
+
+def five_runs(case, lib, gpu):
+    """The procedure of tests/test_memory_contract_gpu.py for one case, on the library handle `lib`: guarded arenas under
+    the three fills, the roomy layout, the first fill again; every output element bit-identical across the five."""
+    import _guarded as G
+    row = build(case, lib)
+    runs = []
+    for i, pattern in enumerate(G.PATTERNS):
+        runs.append((pattern, run_once(row, G.Arena(row.bufs, pattern, gpu, seed=17 + i), 1, lib)))
+    runs.append(("roomy", run_once(row, G.Roomy(row.bufs, gpu), 2, lib)))
+    runs.append(("ff again", run_once(row, G.Arena(row.bufs, G.PATTERNS[0], gpu), 1, lib)))
+    name0, ref = runs[0]
+    sizes = {b.name: torch.empty((), dtype=b.dtype).element_size() for b in row.bufs}
+    for name, outs in runs[1:]:
+        for buf, bits in outs.items():
+            at = G.first_difference(ref[buf], bits, sizes[buf])
+            assert at is None, f"output '{buf}' differs between the '{name0}' and '{name}' runs, first at element {at}"
+    return ref

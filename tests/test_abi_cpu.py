@@ -42,6 +42,7 @@ def test_binding_table_matches_header(lib):
 
 def test_version_and_argument_checks(lib):
     assert lib.fpsg_version() == 1
+    assert lib.fpsg_stream_threshold_bytes() == 300 << 20       # the shipped build: streaming forms beyond 300 MiB
     # null pointers / bad shapes are refused on the host, before any HIP call
     rc = lib.fpsg_chamfer_fwd(None, None, 1, 8, 8, None, None, None, None, None)
     assert rc == -1 and b"null pointer" in lib.fpsg_last_error()

@@ -13,9 +13,7 @@ The workspace may end in any state (its contents are unspecified); only its guar
 Every call is one the header documents as valid, with buffers of the documented size: nothing here is meant to fault.
 """
 import pytest
-import torch
 
-import _guarded as G
 import _memory_contract as T
 
 pytestmark = pytest.mark.gpu
@@ -27,30 +25,6 @@ def lib():
     return _hip.load()
 
 
-def _run(row, layout, scale, lib):
-    p = layout.ptrs()
-    if row.late:
-        for name, data in row.late(p).items():
-            layout.poke(name, data)
-    torch.cuda.synchronize()
-    rc = row.call(p, torch.cuda.current_stream().cuda_stream, row.ws_units * scale)
-    torch.cuda.synchronize()
-    assert rc == 0, f"[{layout.pattern}] returned {rc}: {(lib.fpsg_last_error() or b'').decode()}"
-    layout.check()
-    return layout.outputs()
-
-
 @pytest.mark.parametrize("case", T.CASES, ids=[c[0] for c in T.CASES])
 def test_memory_contract(gpu, lib, case):
-    row = T.build(case, lib)
-    runs = []
-    for i, pattern in enumerate(G.PATTERNS):
-        runs.append((pattern, _run(row, G.Arena(row.bufs, pattern, gpu, seed=17 + i), 1, lib)))
-    runs.append(("roomy", _run(row, G.Roomy(row.bufs, gpu), 2, lib)))
-    runs.append(("ff again", _run(row, G.Arena(row.bufs, G.PATTERNS[0], gpu), 1, lib)))
-    name0, ref = runs[0]
-    sizes = {b.name: torch.empty((), dtype=b.dtype).element_size() for b in row.bufs}
-    for name, outs in runs[1:]:
-        for buf, bits in outs.items():
-            at = G.first_difference(ref[buf], bits, sizes[buf])
-            assert at is None, f"output '{buf}' differs between the '{name0}' and '{name}' runs, first at element {at}"
+    T.five_runs(case, lib, gpu)     # the procedure above; tests/test_streaming_forms_gpu.py runs it on the second build
