@@ -10,20 +10,9 @@ import numpy as np
 import pytest
 import torch
 
+from _trajectory_ref import chamfer64 as _chamfer64, fixed_grids as _fixed_grids, pin_grids as _pin_grids
+
 pytestmark = pytest.mark.gpu
-
-
-def _fixed_grids(model, sizes, device):
-    return {b: model.pc_decoder.sample_grids(b, device, torch.Generator(device=device).manual_seed(100 + b))
-            for b in sizes}
-
-
-def _pin_grids(model, grids):
-    orig = model.pc_decoder.forward
-    model.pc_decoder.forward = lambda h, grid=None, generator=None, pack=None: orig(h, grid=grids[h.size(0)], pack=pack)
-    pair = model.pc_decoder.forward_pair        # the episode's two decodes side by side (its fallback calls .forward)
-    model.pc_decoder.forward_pair = lambda a, b, generator=None, pack=None, grids_=None: pair(
-        a, b, pack=pack, grids=(grids[a.size(0)], grids[b.size(0)]))
 
 
 def _record(name, payload):
@@ -35,14 +24,6 @@ def _record(name, payload):
     if os.path.isdir(out):
         with open(os.path.join(out, "parity_deviation.jsonl"), "a") as f:
             f.write(json.dumps({"test": name, **payload}) + "\n")
-
-
-def _chamfer64(p1, p2, w1=1.0, w2=1.0):
-    """Kaolin's chamfer_distance semantics (few_shot.py:57,110) in float64 torch, differentiable
-    through the arg-min: the 'truth' metric of the float64 run."""
-    d = (p1.unsqueeze(2) - p2.unsqueeze(1)).square().sum(-1)          # [B,N,M]
-    return w1 * d.min(dim=2)[0].mean(dim=1) + w2 * d.min(dim=1)[0].mean(dim=1)
-
 
 
 def _group_grad_distances(dev_model, cpu_model):
