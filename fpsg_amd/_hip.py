@@ -271,6 +271,10 @@ SIGNATURES = {
     "fpsg_point_normals_orient_workspace_bytes": [_c_int, _c_int, _c_int],
     "fpsg_point_normals_orient": [_c_f32p, _c_f32p, _c_i32p, _c_int, _c_int, _c_int, _c_int, _c_f32p, _c_i32p,
                                   ctypes.c_void_p, ctypes.c_size_t, _c_stream],
+    "fpsg_implicit_field": [_c_f32p, _c_f32p, _c_int, _c_int, _c_f32p, _c_f32p, _c_f32p, _c_int, _c_f32p, _c_f32p, _c_stream],
+    "fpsg_iso_classify": [_c_f32p, _c_int, _c_int, _c_i32p, _c_i32p, _c_stream],
+    "fpsg_iso_emit": [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+                      ctypes.c_longlong, _c_f32p, _c_i32p, ctypes.c_void_p, ctypes.c_void_p, _c_stream],
 }
 _RESTYPES = {"fpsg_last_error": ctypes.c_char_p, "fpsg_stream_threshold_bytes": ctypes.c_size_t,
              "fpsg_grad_norm_workspace_bytes": ctypes.c_size_t,

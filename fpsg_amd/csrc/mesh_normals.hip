@@ -1,4 +1,6 @@
-// mesh_normals.hip -- K31a: area-weighted vertex normals of B meshes that share their faces, for gfx950.  The definition
+// mesh_normals.hip -- mesh construction for gfx950: K31a, area-weighted vertex normals of B meshes that share their
+// faces, and the entries of K34 (implicit field of an oriented cloud, marching-tetrahedra isosurface; the kernels are in
+// iso_surface.h).  K31a's definition
 // is in include/fpsg_hip.h (K31) and DESIGN.md: the un-normalised cross products of the faces around a vertex, summed in
 // ascending face order and divided by the sum's length.
 //
@@ -7,6 +9,7 @@
 // The table is device memory that the entry cannot read, so the kernel trusts none of it: a slice is clamped into
 // [0, n], a face id outside [0, F) or a face with an index outside [0, V) is skipped.  A table that lies gives wrong
 // normals and never an access outside the arrays.
+#include "iso_surface.h"
 #include "render_common.h"
 
 namespace fpsg {
@@ -62,4 +65,74 @@ extern "C" int fpsg_mesh_vertex_normals(const float* verts, int B, int V, const 
   hipLaunchKernelGGL(mesh_vertex_normals_kernel, dim3((unsigned)((V + 255) / 256), (unsigned)B), dim3(256), 0,
                      static_cast<hipStream_t>(stream), verts, V, faces, F, offsets, corner_faces, n, normals);
   return launch_status("fpsg_mesh_vertex_normals");
+}
+
+// ---- K34 ----------------------------------------------------------------------------------------------------------------
+namespace fpsg {
+namespace {
+
+// K34's shape and limit checks, in the header's order; 0 when B clouds on G nodes per side pass
+int iso_grid_status(const char* who, int B, int G) {
+  FPSG_REQUIRE(B > 0 && G >= FPSG_ISO_MIN_GRID, FPSG_E_SHAPE, "%s: B must be positive and G at least %d (got %d,%d)", who,
+               FPSG_ISO_MIN_GRID, B, G);
+  FPSG_REQUIRE(G <= FPSG_ISO_MAX_GRID, FPSG_E_LIMIT, "%s: G <= %d is supported (got %d)", who, FPSG_ISO_MAX_GRID, G);
+  FPSG_REQUIRE((long long)B * G * G * G <= (long long)FPSG_ISO_MAX_NODES, FPSG_E_LIMIT,
+               "%s: B G^3 <= %d nodes are supported (got %d x %d^3)", who, FPSG_ISO_MAX_NODES, B, G);
+  return 0;
+}
+
+}  // namespace
+}  // namespace fpsg
+
+extern "C" int fpsg_implicit_field(const float* points, const float* normals, int B, int N, const float* origin,
+                                   const float* cell, const float* radius, int G, float* field, float* weight,
+                                   fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_REQUIRE(N > 0, FPSG_E_SHAPE, "fpsg_implicit_field: N must be positive (got %d)", N);
+  if (const int rc = iso_grid_status("fpsg_implicit_field", B, G)) return rc;
+  FPSG_REQUIRE(N <= FPSG_NORMALS_POINTS_MAX_N, FPSG_E_LIMIT, "fpsg_implicit_field: N <= %d is supported (got %d)",
+               FPSG_NORMALS_POINTS_MAX_N, N);
+  FPSG_REQUIRE_PTR(points); FPSG_REQUIRE_PTR(normals); FPSG_REQUIRE_PTR(origin); FPSG_REQUIRE_PTR(cell);
+  FPSG_REQUIRE_PTR(radius); FPSG_REQUIRE_PTR(field);
+  FPSG_REQUIRE(!misaligned4(weight), FPSG_E_ALIGN, "fpsg_implicit_field: 'weight' not 4-byte aligned");
+  const int side = (G + iso::kBrick - 1) / iso::kBrick;
+  hipLaunchKernelGGL(iso::implicit_field_kernel, dim3((unsigned)B * (unsigned)(side * side * side)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), points, normals, N, origin, cell, radius, G, side, field, weight);
+  return launch_status("fpsg_implicit_field");
+}
+
+extern "C" int fpsg_iso_classify(const float* field, int B, int G, int32_t* node_edges, int32_t* cell_tris,
+                                 fpsg_stream_t stream) {
+  using namespace fpsg;
+  if (const int rc = iso_grid_status("fpsg_iso_classify", B, G)) return rc;
+  FPSG_REQUIRE_PTR(field); FPSG_REQUIRE_PTR(node_edges); FPSG_REQUIRE_PTR(cell_tris);
+  const long long nodes = (long long)G * G * G, total = nodes * B;
+  hipLaunchKernelGGL(iso::iso_classify_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), field, G, nodes, total, node_edges, cell_tris);
+  return launch_status("fpsg_iso_classify");
+}
+
+extern "C" int fpsg_iso_emit(const float* field, const float* origin, const float* cell, int B, int G,
+                             const int64_t* edge_offset, const int64_t* tri_offset, long long n_verts, long long n_faces,
+                             float* verts, int32_t* faces, int64_t* vert_range, int64_t* face_range,
+                             fpsg_stream_t stream) {
+  using namespace fpsg;
+  FPSG_REQUIRE(n_verts >= 0 && n_faces >= 0, FPSG_E_SHAPE, "fpsg_iso_emit: n_verts and n_faces must not be negative "
+               "(got %lld,%lld)", n_verts, n_faces);
+  if (const int rc = iso_grid_status("fpsg_iso_emit", B, G)) return rc;
+  const long long nodes = (long long)G * G * G, total = nodes * B;
+  FPSG_REQUIRE_PTR(field); FPSG_REQUIRE_PTR(origin); FPSG_REQUIRE_PTR(cell); FPSG_REQUIRE_PTR(edge_offset);
+  FPSG_REQUIRE_PTR(tri_offset);
+  if (n_verts > 0) FPSG_REQUIRE_PTR(verts);
+  if (n_faces > 0) FPSG_REQUIRE_PTR(faces);
+  FPSG_REQUIRE(!misaligned4(verts) && !misaligned4(faces), FPSG_E_ALIGN, "fpsg_iso_emit: 'verts' or 'faces' not 4-byte aligned");
+  FPSG_REQUIRE(((reinterpret_cast<uintptr_t>(edge_offset) | reinterpret_cast<uintptr_t>(tri_offset) |
+                 reinterpret_cast<uintptr_t>(vert_range) | reinterpret_cast<uintptr_t>(face_range)) & 7u) == 0,
+               FPSG_E_ALIGN, "fpsg_iso_emit: the 64-bit arrays must be 8-byte aligned");
+  hipLaunchKernelGGL(iso::iso_emit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), field, origin, cell, B, G, nodes, total,
+                     reinterpret_cast<const long long*>(edge_offset), reinterpret_cast<const long long*>(tri_offset),
+                     n_verts, n_faces, verts, faces, reinterpret_cast<long long*>(vert_range),
+                     reinterpret_cast<long long*>(face_range));
+  return launch_status("fpsg_iso_emit");
 }

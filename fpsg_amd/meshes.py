@@ -1149,3 +1149,61 @@ def write_shapenet_lists(root: str, output: str, train_classes=None, test_classe
         with open(os.path.join(output, name), "w") as f:
             f.write("\n".join(rows))
     return {"train": len(train), "test": len(test), "classes": written}
+
+
+# -------------------------------------------------------------------------------------------- K34: checks of a mesh
+def mesh_topology(faces, n_verts: int) -> dict:
+    """What kind of surface the triangles ``faces [F,3]`` on ``n_verts`` vertices are, on the host in numpy -> a dict:
+
+    - ``"edges"``: the undirected edges;
+    - ``"boundary_edges"``: edges of one triangle; ``"nonmanifold_edges"``: edges of more than two;
+    - ``"inconsistent_edges"``: edges of two triangles that run along them in the same direction (opposed windings);
+    - ``"euler"``: ``n_verts - edges + F``, 2 for a sphere, 0 for a torus (every vertex counts, used or not);
+    - ``"components"``: the connected components of the triangles (two triangles connect through a shared vertex);
+    - ``"watertight"``: at least one triangle and none of the three kinds of edges above: a closed, consistently
+      oriented manifold surface.
+
+    ``ValueError`` for a shape other than ``[F,3]``, a non-integer type or an index outside ``[0, n_verts)``."""
+    f = np.asarray(faces.detach().cpu() if isinstance(faces, torch.Tensor) else faces)
+    if f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+        raise ValueError(f"expected integer [F,3] faces, got {f.dtype} {f.shape}")
+    if isinstance(n_verts, bool) or int(n_verts) != n_verts or int(n_verts) < 0:
+        raise ValueError(f"n_verts must be a non-negative integer, got {n_verts}")
+    V, f = int(n_verts), f.astype(np.int64)
+    if f.size and (f.min() < 0 or f.max() >= V):
+        raise ValueError(f"face indices must be in [0, {V}), got {int(f.min())}..{int(f.max())}")
+    a, b = f.reshape(-1), f[:, (1, 2, 0)].reshape(-1)                  # the directed edges a -> b
+    key = np.minimum(a, b) * max(V, 1) + np.maximum(a, b)
+    uniq, inverse, count = np.unique(key, return_inverse=True, return_counts=True)
+    forward = np.bincount(inverse, weights=(a < b), minlength=len(uniq))
+    inconsistent = int(((count == 2) & (forward != 1)).sum())
+    label = np.arange(V, dtype=np.int64)                               # components: the smallest vertex id reachable
+    while f.size:
+        low = label[f].min(axis=1)
+        new = label.copy()
+        np.minimum.at(new, f.reshape(-1), np.repeat(low, 3))
+        new = new[new]                                                 # pointer jumping
+        if np.array_equal(new, label):
+            break
+        label = new
+    boundary, nonmanifold = int((count == 1).sum()), int((count > 2).sum())
+    return {"edges": len(uniq), "boundary_edges": boundary, "nonmanifold_edges": nonmanifold,
+            "inconsistent_edges": inconsistent, "euler": V - len(uniq) + len(f),
+            "components": len(np.unique(label[f[:, 0]])) if f.size else 0,
+            "watertight": bool(len(f) and not boundary and not nonmanifold and not inconsistent)}
+
+
+def mesh_volume(verts, faces) -> float:
+    """The signed volume a closed mesh encloses, ``sum a . (b x c) / 6`` over its triangles in float64 on the host:
+    positive for a mesh that is counter-clockwise seen from outside, negative when its normals look inward.  For an
+    open mesh the number depends on the origin."""
+    v = np.asarray(verts.detach().cpu() if isinstance(verts, torch.Tensor) else verts, dtype=np.float64)
+    f = np.asarray(faces.detach().cpu() if isinstance(faces, torch.Tensor) else faces)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError(f"expected [V,3] vertices, got {v.shape}")
+    if f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+        raise ValueError(f"expected integer [F,3] faces, got {f.dtype} {f.shape}")
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f"face indices must be in [0, {len(v)}), got {int(f.min())}..{int(f.max())}")
+    f = f.astype(np.int64)
+    return float((v[f[:, 0]] * np.cross(v[f[:, 1]], v[f[:, 2]])).sum() / 6.0)

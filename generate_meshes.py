@@ -23,6 +23,12 @@ and ``<output>/metrics.json``.  With ``--normal_consistency`` each line also end
 (``meshes.mesh_normal_consistency``: the cloud's normals by K33 over ``--normals_k`` neighbours against the faces'
 normals, on the same samples), each class row of ``metrics.json`` gets ``"normal_consistency"`` and the report
 ``"normals_k"``.
+
+With ``--implicit_grid G`` (4..256; default 0: off) every query is also reconstructed as ONE closed surface from its
+generated cloud -- the lattice's vertices, with normals by K33 oriented along ``--sample_up`` -- by an implicit field on
+``G`` nodes per side and marching tetrahedra (K34, ``fpsg_amd.reconstruct``): ``<item>_q<k>_surface.obj`` with vertex
+normals.  With ``--metrics`` a second line per class, ``Class: <name> [surface] -- P2S: ..; S2P: ..; Mesh CD: ..; Mesh
+HD: ..; Watertight: <share>``, and a ``"surface"`` block in ``metrics.json``.  Without the flag nothing changes.
 """
 from __future__ import annotations
 
@@ -56,6 +62,9 @@ def build_parser():
                    help="With --metrics: also the normal consistency of mesh and cloud (K33 + K32 + K26 + K1), 'NC';")
     g.add_argument("--normals_k", type=int, default=None, metavar="K",
                    help="With --normal_consistency: neighbours per point for the cloud's normals, 3..32 [default: 16];")
+    g.add_argument("--implicit_grid", type=int, default=0, metavar="G",
+                   help="Also reconstruct every query's cloud as one closed surface on G nodes per side, 4..256 (K34): "
+                        "<item>_q<k>_surface.obj, and with --metrics a [surface] line per class [default: 0 = off];")
     return p
 
 
@@ -72,6 +81,8 @@ def main(opt) -> int:
         surface.regular_grid(opt.grid)
     except ValueError as e:
         raise SystemExit(f"--grid: {e}") from None
+    if opt.implicit_grid != 0 and not 4 <= opt.implicit_grid <= 256:
+        raise SystemExit(f"--implicit_grid must be 0 (off) or from 4 to 256, got {opt.implicit_grid}")
     if opt.max_items < 0:
         raise SystemExit("--max_items must not be negative")
     if opt.metrics_samples is not None and not opt.metrics:
@@ -102,11 +113,14 @@ def main(opt) -> int:
 
     g = opt.grid
     n_patches = model.pc_decoder.num_clusters * model.pc_decoder.num_nodes
+    if opt.implicit_grid and not 17 <= n_patches * g * g <= 16384:
+        raise SystemExit(f"--implicit_grid takes clouds of 17 to 16384 points (K33), --grid {g} gives {n_patches * g * g}")
     materials = patch_materials(n_patches)
     face_material = surface.patch_face_material(g, n_patches)
     table = faces = None
     items, first_layer = 0, "-"
     per_class, samples = {}, opt.metrics_samples          # --metrics: class -> one row of four means per item
+    surface_class = {}                                    # --implicit_grid: class -> [P2S, S2P, CD, HD, watertight] per query
     for item, sample in enumerate(dl_test):
         if opt.max_items and item >= opt.max_items:
             break
@@ -140,6 +154,20 @@ def main(opt) -> int:
                     nc = meshes.mesh_normal_consistency(verts[k], faces, clouds[k], k=normals_k, n_samples=samples, u=u)
                     rows[-1].append(nc["normal_consistency"])
             per_class.setdefault(str(sample["class"][0]), []).append([sum(col) / len(col) for col in zip(*rows)])
+        if opt.implicit_grid:
+            from fpsg_amd.reconstruct import reconstruct_surface
+            closed = reconstruct_surface(verts, grid=opt.implicit_grid, up=getattr(opt, "sample_up", "z"), vertex_normals=True)
+            draws = torch.Generator().manual_seed(item)    # a stream of its own: the lattice meshes' numbers stay
+            for k, (sv, sf, sn) in enumerate(closed):
+                meshes.write_obj_mesh(os.path.join(folder, f"{item:05d}_q{k}_surface.obj"), sv, sf, normals=sn)
+                if opt.metrics:
+                    u = torch.rand((samples, 3), generator=draws, dtype=torch.float32)
+                    tight = float(meshes.mesh_topology(sf, sv.size(0))["watertight"])
+                    if sf.size(0):                         # a cloud without a surface has no distances
+                        acc = meshes.mesh_accuracy(sv, sf, clouds[k], n_samples=samples, u=u)
+                        surface_class.setdefault(str(sample["class"][0]), []).append([acc[n] for n in METRIC_KEYS] + [tight])
+                    else:
+                        surface_class.setdefault(str(sample["class"][0]), []).append([float("nan")] * 4 + [tight])
         items += 1
     kernels = f"decoder first layer {first_layer}, normals K31a" + ("" if opt.no_sheet else ", views K31b + K29")
     if opt.metrics:
@@ -152,11 +180,20 @@ def main(opt) -> int:
             means = [sum(col) / len(col) for col in zip(*per_class[name])]
             report["classes"][name] = dict(zip(keys, means), items=len(per_class[name]))
             print(f"Class: {name} -- " + "; ".join(f"{label}: {v}" for label, v in zip(labels, means)))
+            if opt.implicit_grid:
+                rows = surface_class[name]
+                means = [sum(col) / len(col) for col in zip(*rows)]
+                report.setdefault("surface", {"grid": opt.implicit_grid, "classes": {}})["classes"][name] = dict(
+                    zip(METRIC_KEYS + ("watertight",), means), meshes=len(rows))
+                print(f"Class: {name} [surface] -- " + "; ".join(f"{label}: {v}" for label, v in
+                                                                  zip(METRIC_LABELS + ("Watertight",), means)))
         os.makedirs(opt.output, exist_ok=True)
         with open(os.path.join(opt.output, "metrics.json"), "w") as f:
             json.dump(report, f, indent=1, sort_keys=True)
             f.write("\n")
         kernels += ", distances K32 + K26 + K1" + (", normals K33" if opt.normal_consistency else "")
+    if opt.implicit_grid:
+        kernels += f", surfaces K33 + K34 on {opt.implicit_grid}^3"
     print(f"{opt.output}: {items} items x {n_query} queries, {n_patches * g * g} vertices and "
           f"{n_patches * 2 * (g - 1) ** 2} faces per mesh ({kernels})")
     return 0

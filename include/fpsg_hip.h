@@ -1574,6 +1574,73 @@ int fpsg_point_normals_orient(const float* xyz, const float* normals_in, const i
                               int axis, float* normals_out, int32_t* parent, void* ws, size_t ws_bytes,
                               fpsg_stream_t stream);
 
+/* ---- K34: surface reconstruction from an oriented cloud (implicit field, marching-tetrahedra isosurface) -----------
+ * One closed, consistently oriented triangle mesh from a cloud with normals (K33's, or any): an implicit-moving-least-
+ * squares field of signed tangent-plane distances on a regular grid (Kolluri 2005; Shen et al. 2004) with a compactly
+ * supported polynomial weight, and the zero level set of that field by marching tetrahedra on the Kuhn split of the
+ * cells.  The definition below is the specification (parity UNPINNED).  All pointers are device memory.
+ * All arithmetic in fp32 with every operation rounded on its own (no fma), divisions correctly rounded; max(x, 0)
+ * returns 0 when x is NaN (fmaxf).
+ *
+ * K34a, fpsg_implicit_field.  Inputs: points, normals [B,N,3] fp32; origin [B,3], cell [B], radius [B] fp32 (device
+ * memory: no host read); G nodes per side.  Outputs: field [B,G,G,G] fp32; weight [B,G,G,G] fp32 or NULL.
+ *   Node (i,j,k) of cloud b is field[b][i][j][k] and lies at x = origin + (float)i * cell per axis (the multiply, then
+ *   the add).  inv = 1 / (radius * radius), once per cloud.  From num = den = +0, over the points j in ascending order:
+ *     d  = x - p_j per component;   d2 = (dx*dx + dy*dy) + dz*dz;   t = max(1 - d2*inv, 0);   w = (t*t)*t;
+ *     s  = (dx*nx + dy*ny) + dz*nz;   num = num + w*s;   den = den + w.
+ *   A point with a non-finite coordinate or normal component contributes nothing.
+ *   field = den > 0 ? num / den : NaN (the quiet NaN 0x7fc00000);   weight = den.
+ *   The weight is a polynomial of the squared distance: no exp, no sqrt, and a point outside a node's ball contributes
+ *   exactly +0, so the kernel skips the points whose ball cannot reach a brick of FPSG_FIELD_BRICK^3 nodes (a test
+ *   that is conservative in floating point; iso_surface.h derives its margin) without changing a bit.  This holds for
+ *   a radius whose square and its reciprocal are normal fp32 numbers and for products w*s that do not overflow;
+ *   outside that the values are unspecified (never an access outside the arrays).  The cloud passes through LDS in
+ *   tiles of FPSG_FIELD_TILE points.  One launch; no atomics, nothing passes between workgroups.
+ *
+ * K34b, fpsg_iso_classify and fpsg_iso_emit.  Input: field [B,G,G,G] (K34a's, or any).
+ *   A node is inside when field < 0; 0, -0 and NaN are not inside.  Every cell (its lowest corner (i,j,k), i,j,k < G-1)
+ *   is split into six tetrahedra: for the permutations (a,b,c) of the axes (0 = i, 1 = j, 2 = k) in lexicographic order
+ *   012, 021, 102, 120, 201, 210, the corners in path order 000, +e_a, +e_a+e_b, 111.  The split is the same in every
+ *   cell, so neighbouring cells agree on every face diagonal.
+ *   A grid edge belongs to its lower node and has one of 7 classes, the step (di,dj,dk) in the order 100, 010, 001, 110,
+ *   101, 011, 111.  It is active when both ends are finite and exactly one is inside; flags = the bit set of a node's
+ *   active owned classes.  An active edge carries one vertex: t = f0 / (f0 - f1) from the owner toward the far node, the
+ *   coordinate x0 + t * cell on the axes the class steps along and x0 on the others (x0 the owner's node position).
+ *   A tetrahedron emits triangles only when its four corners are finite.  With the path corners numbered 0..3, inside
+ *   ones i < j < .. and outside ones k < l < ..: one inside: the triangle (i,k),(i,l),(i,m) on its three edges; three
+ *   inside: (i,k),(j,k),(m,k) on the outside corner's edges; two inside: the quad (i,k),(i,l),(j,l),(j,k) as
+ *   [(i,k),(i,l),(j,l)] and [(i,k),(j,l),(j,k)].  Where the normal of a triangle so listed (corners at their unit-cube
+ *   positions, vertices at the edge midpoints) does not look from the inside corners' centroid toward the outside
+ *   corners', the last two vertices of each triangle of the case are exchanged: the mesh is counter-clockwise seen
+ *   from outside, its normals look toward positive field.  The 6 x 16 table is generated from this rule at compile time.
+ *   fpsg_iso_classify writes node_edges [B,G^3] int32 (popcount(flags), 0..7) and cell_tris [B,G^3] int32 (the triangles
+ *   of the cell whose lowest corner is the node, 0..12; 0 where i, j or k is G-1).  The caller turns both into exclusive
+ *   64-bit offsets over all B G^3 nodes (edge_offset, tri_offset) and sizes the outputs by the totals n_verts, n_faces.
+ *   fpsg_iso_emit recomputes the flags from the field and writes, packed over the clouds, verts [n_verts,3] fp32 in
+ *   ascending node order, then class order, and faces [n_faces,3] int32 in ascending cell, tetrahedron, then table
+ *   order; an edge's vertex id is edge_offset[owner] + popcount(flags[owner] & ((1 << class) - 1)) minus the cloud's
+ *   own first offset, so indices are local to their cloud.  vert_range, face_range [B+1] int64 (or NULL): cloud b owns
+ *   verts[vert_range[b] : vert_range[b+1]] and faces[face_range[b] : face_range[b+1]].  Offsets that lie give a wrong
+ *   mesh, never a write outside [0, n_verts) x [0, n_faces).  verts or faces may be NULL when its count is 0.
+ *   One thread per node in both kernels; no atomics; bitwise the same on every run.
+ *
+ * Errors, all on the host before any HIP call, in this order: FPSG_E_SHAPE for B or N < 1, G < FPSG_ISO_MIN_GRID, a
+ * negative n_verts or n_faces; FPSG_E_LIMIT for G > FPSG_ISO_MAX_GRID, B G^3 >
+ * FPSG_ISO_MAX_NODES or N > FPSG_NORMALS_POINTS_MAX_N; FPSG_E_NULL for a null pointer other than weight, vert_range,
+ * face_range (and verts, faces with a zero count); FPSG_E_ALIGN for a misaligned pointer (the int64 arrays: 8 bytes).
+ */
+#define FPSG_ISO_MIN_GRID 2
+#define FPSG_ISO_MAX_GRID 256
+#define FPSG_ISO_MAX_NODES (1 << 28)
+#define FPSG_FIELD_BRICK 8
+#define FPSG_FIELD_TILE 256
+int fpsg_implicit_field(const float* points, const float* normals, int B, int N, const float* origin, const float* cell,
+                        const float* radius, int G, float* field, float* weight, fpsg_stream_t stream);
+int fpsg_iso_classify(const float* field, int B, int G, int32_t* node_edges, int32_t* cell_tris, fpsg_stream_t stream);
+int fpsg_iso_emit(const float* field, const float* origin, const float* cell, int B, int G, const int64_t* edge_offset,
+                  const int64_t* tri_offset, long long n_verts, long long n_faces, float* verts, int32_t* faces,
+                  int64_t* vert_range, int64_t* face_range, fpsg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
